@@ -10,6 +10,7 @@ the exact-Gram arithmetic, one stream instead of two: `summary`, the LAST key of
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts N rank processes itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                 # also writes the last timed step's reconstruction to DIR/*.npy
 
 One "step" = one full reconstruction pass (x0 = Phi^T y, max_iter+1 f-calls, final all-gather) over
 one synthetic batch of `--batch-per-gpu` measurements per GPU (SURVEY 8(d) C3 recipe: Bernoulli(0.5)
@@ -265,7 +266,41 @@ def parse_args(argv=None):
                     help="test rig for a one-GPU box: all ranks on cuda:0, gloo collective (real engine, real sharding; not a measurement)")
     ap.add_argument("--plumbing-selftest", action="store_true",
                     help="CPU + gloo + a stub engine: exercises launcher/sharding/all-gather only (no GPU, no reconstruction)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (fp32; at most 64 MB in all, a fixed "
+                         "seeded sample of the measurements beyond that), to compare two builds output for output on the same inputs")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(directory, outputs, seed=0):
+    """--dump-outputs: one DIR/<name>.npy per array of `outputs` (float32 / float64 as returned).  An array above its share of the
+    DUMP_BYTES_MAX budget is cut to a fixed, seeded sample along its leading (measurement) axis - or of its elements, where one measurement
+    alone is too large - and DIR/<name>_sample_index.npy (float64) names what was kept."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    budget = (DUMP_BYTES_MAX - 4096 * len(outputs)) // max(len(outputs), 1)     # (the .npy headers inside the 64 MB too)
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float32)
+        idx = None
+        if a.nbytes > budget:
+            rng = np.random.default_rng(seed)
+            per = a.nbytes // max(a.shape[0], 1)
+            if per + 8 <= budget:                                                 # (8 bytes: the float64 index of a kept row)
+                idx = np.sort(rng.choice(a.shape[0], size=budget // (per + 8), replace=False))
+                a = a[idx]
+            else:
+                idx = np.sort(rng.choice(a.size, size=budget // (a.itemsize + 8), replace=False))
+                a = a.reshape(-1)[idx]
+            np.save(os.path.join(directory, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def build_engine(args, dev, conv64=None, f22_calls="args", denoiser=None, **over):
@@ -385,7 +420,7 @@ def run_rank(args):
         timing_on[0] = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        rec = step()
     fence()
     elapsed = time.perf_counter() - t0
     local_elapsed = elapsed
@@ -395,6 +430,10 @@ def run_rank(args):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received from the last timed step: the (M,H,W,B) reconstruction (all-gathered over the ranks)
+        dump_outputs(args.dump_outputs, {"reconstruction": rec})
+    del rec
 
     # N > 1: what proves, on the first hardware run, that the collective library saw N ranks on N different devices - gathered once,
     # outside the timed region

@@ -161,6 +161,46 @@ def test_bench_strong_scaling_mode_two_ranks():
     assert rec["allgather_bytes_per_step"] == 2 * 3 * 16 * 12 * 8 * 4
 
 
+def test_bench_dump_outputs_two_ranks(tmp_path):
+    """`--dump-outputs DIR`: rank 0 writes the last timed step's all-gathered (M,H,W,B) result as DIR/reconstruction.npy (fp32), the same
+    bits on every run with the same arguments (the stub engine returns Phi^T y of bench.make_batch: checked against it); `--steps 0` is refused."""
+    import subprocess
+    import sys
+    import numpy as np
+    from conftest import ROOT
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    dumps = []
+    for i, steps in enumerate(("1", "3")):
+        d = tmp_path / f"run{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-selftest", "--global-batch", "5",
+                              "--size", "16x12x8", "--steps", steps, "--warmup", "0", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=300, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert sorted(os.listdir(d)) == ["reconstruction.npy"]
+        dumps.append(np.load(d / "reconstruction.npy"))
+    y, Phi, _ = bench.make_batch(0, 5, 16, 12, 8, 1234, torch.device("cpu"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (5, 16, 12, 8)
+    assert np.array_equal(dumps[0], dumps[1]) and np.array_equal(dumps[0], (y.unsqueeze(-1) * Phi).numpy())
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--plumbing-selftest", "--steps", "0"],
+                         capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_bench_dump_outputs_keeps_to_64_mb(tmp_path):
+    """An output above the budget is cut to a fixed, seeded sample of whole measurements, named by <name>_sample_index.npy."""
+    import numpy as np
+    import bench
+    t = torch.arange(40 * 256 * 256 * 8, dtype=torch.float32).reshape(40, 256, 256, 8)      # 84 MB
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"reconstruction": t})
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64_000_000
+    a, idx = np.load(tmp_path / "a" / "reconstruction.npy"), np.load(tmp_path / "a" / "reconstruction_sample_index.npy")
+    assert a.dtype == np.float32 and idx.dtype == np.float64 and a.shape[1:] == (256, 256, 8) and len(idx) == a.shape[0] > 20
+    assert np.array_equal(a, t.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(a, np.load(tmp_path / "b" / "reconstruction.npy"))
+
+
 def test_bench_config3_eight_ranks_global_batch_64():
     """The only N > 1 the target machine has is 8, and BASELINE config 3 is 64 measurements over 8 GPUs: the launcher starting EIGHT ranks,
     their rendezvous on one port, the shard bounds, the gather bytes and the reaping, end to end (gloo, stub engine, 8 CPU processes -
