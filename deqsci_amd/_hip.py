@@ -66,12 +66,13 @@ SIGNATURES = {
     "deqsci_ffdnet_head_p32": [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr, _int, _ptr],
     "deqsci_ffdnet_tail_p32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr],
     "deqsci_conv3x3_c1_to_64_sp16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr, _ptr],
+    "deqsci_ssim_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
 }
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
-                 "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes")
+                 "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -107,6 +108,8 @@ def load():
     lib.deqsci_gram_bytes.argtypes = [_i64]
     lib.deqsci_gram_ref_bytes.restype = ctypes.c_size_t
     lib.deqsci_gram_ref_bytes.argtypes = [_i64, _i64]
+    lib.deqsci_ssim_workspace_bytes.restype = _i64
+    lib.deqsci_ssim_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _int]
     _lib = lib
     return lib
 
@@ -1267,6 +1270,39 @@ def conv3x3_c64(x, weights, bias=None, relu=True, out=None, policy="fast", chain
     if kind == "f44":
         return conv3x3_c64_winograd44(x, weights.f44, bias, relu, out, out_blk=chain)
     return conv3x3_c64_winograd(x, weights.f22, bias, relu, out)
+
+
+# ----------------------------------------------------------------------------- evaluation metric (csrc/ssim.hip)
+SSIM_MODES = {"same": 0, "valid": 1}
+
+
+def ssim_window_ok(window):
+    return isinstance(window, int) and 3 <= window <= 15 and window % 2 == 1
+
+
+def ssim_frames(x, y, layout=LAYOUT_HWB, window=11, mode="same", clamp_x=False):
+    """Per-frame mean SSIM of x against y (the reference's pytorch_ssim._ssim per frame: Gaussian window, sigma 1.5, zero padding) ->
+    (M, B) float64 on the device.  x, y: (M,H,W,B) for LAYOUT_HWB, (M,B,H,W) for LAYOUT_BHW, fp32 on one HIP device.  mode "same" = the
+    mean over all H*W map values, "valid" = over the values whose window lies inside the image.  clamp_x: x clamped to [0,1] first.
+    The workspace comes from torch's caching allocator; the launches go to the current stream."""
+    if tuple(x.shape) != tuple(y.shape) or x.dim() != 4:
+        raise DeqsciHipError(f"ssim: x {tuple(x.shape)} and y {tuple(y.shape)} must be the same 4-d shape")
+    if mode not in SSIM_MODES:
+        raise ValueError(f"ssim mode must be one of {sorted(SSIM_MODES)}, got {mode!r}")
+    if not ssim_window_ok(window):
+        raise ValueError(f"ssim window must be an odd integer in 3..15, got {window!r}")
+    M, H, W, B = _dims(layout, x.shape)
+    out = torch.empty((M, B), device=x.device, dtype=torch.float64)
+    if M == 0 or B == 0:
+        return out
+    nbytes = load().deqsci_ssim_workspace_bytes(M, H, W, B, layout)
+    if nbytes < 0:
+        _check(int(nbytes), "ssim_workspace_bytes")
+    ws = torch.empty((max(int(nbytes), 8),), device=x.device, dtype=torch.uint8)
+    with _dev(x):
+        _check(load().deqsci_ssim_f32(_p(x, "x"), _p(y, "y"), out.data_ptr(), M, H, W, B, layout, window, SSIM_MODES[mode],
+                                      1 if clamp_x else 0, ws.data_ptr(), _stream()), "ssim")
+    return out
 
 
 # ----------------------------------------------------------------------------- measurement helpers (bench.py)

@@ -8,6 +8,7 @@ Every flag of the reference parses (so its test_*.sh command lines run unchanged
 --sigma) are accepted and ignored, and `--inference False` is refused: training is outside this build.
 `--gpu_ids a,b,..` with more than one id is this build's addition: one process per listed GPU, every clip's
 measurements sharded over them (deqsci_amd.distributed), rank 0 prints and writes the PNGs.
+`--ssim` (also this build's) adds the per-clip SSIM and a 'Total Average SSIM' line (window 11, `--ssim_mode same|valid`).
 """
 import argparse
 import os
@@ -69,6 +70,12 @@ def parser():
                    help="(this build) clip: a clip's measurements as ONE engine batch instead of the reference's one-by-one schedule (implied by "
                         "more than one --gpu_ids entry, which shards them); all: the measurements of all clips of one frame size as one batch "
                         "(the three shipped clips: one call of eight measurements - what the device is fastest at)")
+    p.add_argument('--ssim', action='store_true',
+                   help="(this build) also report SSIM (the reference's pytorch_ssim per frame, window 11, on the device): per clip and a "
+                        "'Total Average SSIM' line after the PSNR lines")
+    p.add_argument('--ssim_mode', default=None, choices=['same', 'valid'],
+                   help="(this build) same (default) = the mean over the whole zero-padded SSIM map, as pytorch_ssim; valid = over the "
+                        "map values whose window lies inside the frame.  Implies --ssim")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
     ignored.add_argument('--n_epochs', default=80)
     ignored.add_argument('--batch_size', type=int, default=1)
@@ -99,17 +106,24 @@ def run(args):
         print('loaded dict!')
         os.makedirs(args.savepath, exist_ok=True)
     images = {}
+    ssim = bool(args.ssim or args.ssim_mode)
 
     def on_clip(r):
         if rank == 0:
             images.update(png_payloads(r, args.savepath))
-            print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
+            if ssim:
+                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
+            else:
+                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
     t0 = time.time()
     avg, results = evaluate(deq, SCITestDataset(args.testpath), device=dev, on_clip=on_clip,
-                            batch="all" if args.batch_measurements == "all" else bool(args.batch_measurements or world > 1))
+                            batch="all" if args.batch_measurements == "all" else bool(args.batch_measurements or world > 1),
+                            ssim=ssim, ssim_mode=args.ssim_mode or "same")
     dt = time.time() - t0
     if rank == 0:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
+        if ssim:
+            print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
         for path, img in images.items():
             write_png(path, img)
         n = sum(r.frames for r in results)

@@ -10,6 +10,7 @@ printed lines and PNG naming (ibid. :152-205) on top of the two.
 
     load_test_data / SCITestDataset   utils/sci_dataloader.py:241-274 (MATLAB v5 files, sorted file order)
     psnr                              skimage.metrics.peak_signal_noise_ratio for float input, data range 1
+    ssim / clip_ssim                  pytorch_ssim._ssim per frame (this build's addition: the reference harness reports PSNR only)
     frame_payload                     the float image the reference hands to cv2.imwrite (ibid. :19-21)
 """
 import math
@@ -78,6 +79,29 @@ def clip_psnr(rec, gt, ids):
     return [10.0 * math.log10(1.0 / float(v)) for v in mse.cpu()]
 
 
+def ssim(rec, gt, window=11):
+    """SSIM of one frame (H,W) against its ground truth: the reference's pytorch_ssim on a (1,1,H,W) image.  Device tensors go through
+    the HIP kernel, anything else through the float64 restatement (deqsci_amd.pytorch_ssim.ssim_float64)."""
+    from . import _hip, pytorch_ssim
+    if isinstance(rec, torch.Tensor) and rec.is_cuda:
+        g = torch.as_tensor(gt).to(rec.device, torch.float32)
+        return float(_hip.ssim_frames(_hip.f32c(rec.detach())[None, None], g.contiguous()[None, None], _hip.LAYOUT_BHW, window)[0, 0])
+    a = torch.as_tensor(np.asarray(rec, dtype=np.float32))[None, None]
+    b = torch.as_tensor(np.asarray(gt, dtype=np.float32))[None, None]
+    return float(pytorch_ssim.ssim_float64(a, b, window))
+
+
+def clip_ssim(rec, gt, ids, mode="same"):
+    """SSIM of every scored measurement of a clip, the twin of clip_psnr: rec (M,H,W,B) on its device, gt (H,W,B*Mall) on the host.
+    rec is clamped to [0,1] as for the PSNR; per measurement the mean over its B frames of the per-frame SSIM (window 11, mode "same" or
+    "valid"), computed where rec lives, so that only M scalars cross PCIe."""
+    from . import _hip
+    B = rec.shape[-1]
+    g = torch.stack([torch.as_tensor(gt[..., B * m:B * (m + 1)]) for m in ids]).to(rec.device, torch.float32).contiguous()
+    per = _hip.ssim_frames(_hip.f32c(rec.detach()), g, _hip.LAYOUT_HWB, 11, mode, clamp_x=True)
+    return [float(v) for v in per.mean(dim=1).cpu()]
+
+
 def frame_payload(frame):
     """One reconstructed frame (H,W) -> the (H,W,1) float image in [0,255] that goes to the PNG writer."""
     return (frame.detach().clamp(0, 1).cpu().numpy() * 255.)[:, :, None]
@@ -104,10 +128,15 @@ class ClipResult:
     frames: int = 0
     seconds: float = 0.0
     info: dict = field(default_factory=dict)
+    ssim: list | None = None          # per measurement, the mean SSIM over its B frames (only when asked for)
 
     @property
     def mean_psnr(self):
         return sum(self.psnr) / len(self.psnr)
+
+    @property
+    def mean_ssim(self):
+        return None if self.ssim is None else sum(self.ssim) / len(self.ssim)
 
 
 def as_clip(sample):
@@ -138,10 +167,11 @@ def _residuals(deep_eq_module, n):
     return [r] * n, (info or {})
 
 
-def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None):
+def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same"):
     """All scored measurements of one clip through `deep_eq_module.forward(y, Phi, Phi_sum, initial_point=, train_flag=False)`.
     batch=True: one call with y (M,H,W) and the shared mask (1,H,W,B); batch=False: M calls of batch 1 (the reference's
-    schedule).  With a process group the measurements are sharded over its ranks and all-gathered."""
+    schedule).  With a process group the measurements are sharded over its ranks and all-gathered.  ssim=True: also the
+    per-measurement SSIM (clip_ssim, after the timed part)."""
     import time
     clip = as_clip(clip)
     Phi = clip['mask'].to(device)[None].contiguous()                  # (1,H,W,B)
@@ -178,16 +208,17 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     dt = time.perf_counter() - t0
     ps = clip_psnr(rec, clip['gt'], ids)
     return ClipResult(name=clip['file'], rec=rec, psnr=ps, res=res, frames=B * len(ids), seconds=dt,
-                      info={"measurements": ids, "batched": bool(batch)})
+                      info={"measurements": ids, "batched": bool(batch)},
+                      ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None)
 
 
-def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None):
+def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same"):
     """The scored measurements of SEVERAL clips of one frame size as ONE engine batch, every measurement with its own clip's mask
     ((M,H,W,B) masks: nothing couples the measurements of a batch - alpha, residual, the ranges of the split-fp16 activations are all per
     measurement - so a measurement's reconstruction is the one it gets in any other batch, bit for bit).  What the reference's loop over
     clips and measurements (training/sci_equilibrium_training.py:157,171) becomes when the device wants eight measurements per call: the
     three shipped clips (1 + 1 + 6 measurements) are one call.  -> [ClipResult] in the clips' order; a clip's `seconds` is its share of
-    the call by frames."""
+    the call by frames.  ssim=True: also the per-measurement SSIM, as in reconstruct_clip."""
     import time
     clips = [as_clip(c) for c in clips]
     ids = [scored_measurements(c['file'], c['meas'].shape[-1]) for c in clips]
@@ -213,22 +244,24 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None)
     for c, i in zip(clips, ids):
         r = rec[a:a + len(i)]
         out.append(ClipResult(name=c['file'], rec=r, psnr=clip_psnr(r, c['gt'], i), res=list(res[a:a + len(i)]), frames=B * len(i),
-                              seconds=dt * len(i) / y.shape[0], info={"measurements": i, "batched": "all"}))
+                              seconds=dt * len(i) / y.shape[0], info={"measurements": i, "batched": "all"},
+                              ssim=clip_ssim(r, c['gt'], i, ssim_mode) if ssim else None))
         a += len(i)
     return out
 
 
-def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None):
+def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same"):
     """-> (mean over clips of the clip's mean PSNR, [ClipResult]).  batch: False = one measurement per call (the reference's schedule),
     True = a clip's measurements per call, "all" = the measurements of consecutive clips of one frame size per call
-    (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements)."""
+    (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements).  ssim=True fills every ClipResult.ssim
+    (window 11, ssim_mode "same" or "valid"); the mean over clips of the clip's mean SSIM is then sum(r.mean_ssim ...) / len(results)."""
     results = []
     if batch == "all":
         pending = []
 
         def flush():
             if pending:
-                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group):
+                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group, ssim=ssim, ssim_mode=ssim_mode):
                     results.append(r)
                     if on_clip is not None:
                         on_clip(r)
@@ -241,7 +274,7 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
         flush()
         return sum(r.mean_psnr for r in results) / len(results), results
     for sample in clips:
-        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group)
+        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group, ssim=ssim, ssim_mode=ssim_mode)
         results.append(r)
         if on_clip is not None:
             on_clip(r)
@@ -260,13 +293,14 @@ def png_payloads(result, prefix=""):
 
 
 def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, verbose=True, save_image=True,
-                    device="cuda", records=None, batch_measurements=False):
+                    device="cuda", records=None, batch_measurements=False, ssim=False):
     """Adapter with the reference's signature (training/sci_equilibrium_training.py:152): returns
     (average PSNR, {png path: float image}); prints one line per clip and the total; writes the PNGs.
     Default = the reference's schedule, one measurement per call (:171-181); batch_measurements="all" hands the measurements of all clips of
     one frame size to the engine as ONE batch (the three shipped clips: one call of eight); batch_measurements=True hands a clip's
     measurements to the engine as one batch (faster; on the chaotic FFDNet + Anderson @180 clip a different - equally valid -
-    realisation, because the FFDNet head kernel is chosen by launch size)."""
+    realisation, because the FFDNet head kernel is chosen by launch size).  ssim=True (this build's addition): every record gains "ssim",
+    every clip line '  SSIM: %.4f' and a 'Total Average SSIM' line follows the PSNR total; the return value is unchanged."""
     images = {}
 
     def on_clip(r):
@@ -274,11 +308,18 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
         if records is not None:
             for i, m in enumerate(r.info["measurements"]):
                 records.append({"id": f"{r.name}:{m}", "psnr": r.psnr[i], "res": r.res[i], "rec": r.rec[i:i + 1].cpu()})
+                if ssim:
+                    records[-1]["ssim"] = r.ssim[i]
         if verbose:
-            print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
-    avg, _ = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip)
+            if ssim:
+                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
+            else:
+                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
+    avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim)
     if verbose:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
+        if ssim:
+            print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
     if save_image:
         for path, img in images.items():
             write_png(path, img)

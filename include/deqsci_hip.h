@@ -347,6 +347,20 @@ int deqsci_ffdnet_head_p32(const float* x, const void* w_packed, const float* si
 int deqsci_ffdnet_tail_p32(const void* x_p32, const void* w_packed, float* out, int64_t n, int64_t H, int64_t W,
                            int w_exp, const float* in_amax, int in_exp, deqsci_stream_t stream);
 
+/* ---- evaluation metric (not on the reconstruction path) ----
+ * S1+S2  per-frame mean SSIM of x against y (pytorch_ssim._ssim of the reference: Gaussian window `window`, sigma 1.5, zero
+ *     padding of window/2, C1 = 0.01^2, C2 = 0.03^2), one float64 per (measurement, frame): out is (M, B), out[m*B + f].
+ *     x and y are (M,H,W,B) (layout HWB) or (M,B,H,W) (layout BHW), fp32, 4-byte aligned; out and workspace 8-byte aligned.
+ *     window: odd, 3..15.  valid = 0: mean over all H*W map values ("same", the reference's size_average); valid = 1: mean over
+ *     the (H-window+1) x (W-window+1) map values whose window lies inside the image (-2 if there are none).  clamp_x != 0: x is
+ *     clamped to [0,1] on load (NaN kept).  A NaN in a frame makes that frame's value NaN.  Deterministic (fixed summation
+ *     order, no atomics).  M = 0 or B = 0: nothing is launched.  workspace = deqsci_ssim_workspace_bytes(...) bytes, no
+ *     initialisation needed; out and workspace must not overlap x, y or each other (-4).  The workspace query returns
+ *     DEQSCI_ERR_* (< 0) for invalid sizes or layout. */
+int64_t deqsci_ssim_workspace_bytes(int64_t M, int64_t H, int64_t W, int64_t B, int layout);
+int deqsci_ssim_f32(const float* x, const float* y, double* out, int64_t M, int64_t H, int64_t W, int64_t B,
+                    int layout, int window, int valid, int clamp_x, void* workspace, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
