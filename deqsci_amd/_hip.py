@@ -20,6 +20,7 @@ _LIB_PATH = os.environ.get("DEQSCI_HIP_LIB") or os.path.join(os.path.dirname(os.
 _lib = None
 
 _i64, _int, _f32, _ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+_f64 = ctypes.c_double
 
 # name -> argtypes; the single source of truth for tests/test_cabi_exports.py too
 SIGNATURES = {
@@ -67,12 +68,15 @@ SIGNATURES = {
     "deqsci_ffdnet_tail_p32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr],
     "deqsci_conv3x3_c1_to_64_sp16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr, _ptr],
     "deqsci_ssim_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _ptr, _ptr],
+    "deqsci_gaptv_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _f64, _f64, _f64, _int, _ptr, _ptr, _ptr],
+    "deqsci_tv_chambolle_f32": [_ptr, _ptr, _i64, _i64, _i64, _f64, _f64, _int, _f64, _ptr, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
 }
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
-                 "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes")
+                 "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
+                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -110,6 +114,10 @@ def load():
     lib.deqsci_gram_ref_bytes.argtypes = [_i64, _i64]
     lib.deqsci_ssim_workspace_bytes.restype = _i64
     lib.deqsci_ssim_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _int]
+    lib.deqsci_gaptv_workspace_bytes.restype = _i64
+    lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+    lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
+    lib.deqsci_tv_chambolle_workspace_bytes.argtypes = [_i64, _i64, _i64]
     _lib = lib
     return lib
 
@@ -1303,6 +1311,58 @@ def ssim_frames(x, y, layout=LAYOUT_HWB, window=11, mode="same", clamp_x=False):
         _check(load().deqsci_ssim_f32(_p(x, "x"), _p(y, "y"), out.data_ptr(), M, H, W, B, layout, window, SSIM_MODES[mode],
                                       1 if clamp_x else 0, ws.data_ptr(), _stream()), "ssim")
     return out
+
+
+# ----------------------------------------------------------------------------- GAP-TV (csrc/tv.hip)
+def _stop_buffer(shape, device, want):
+    return torch.empty(shape, device=device, dtype=torch.int32) if want else None
+
+
+def gaptv(y, phi, phi_sum, maxiter=40, step=1.0, weight=0.3, eps=2e-4, n_iter_max=30, return_stop=False):
+    """The reference's GAP_TV_rec per measurement with skimage 0.17.2's denoise_tv_chambolle (multichannel, tau 1/6): y (bsz,H,W),
+    Phi (bsz,H,W,B) or (1,H,W,B) (shared), Phi_sum (bsz,H,W) or (1,H,W), fp32 on one HIP device -> (bsz,H,W,B) fp32, and with
+    return_stop=True also the (bsz, maxiter, B) int32 stop indices (n_iter_max where the early stop never fired).  State in fp64; the
+    launches go to the current stream, the workspace comes from torch's caching allocator."""
+    if y.dim() != 3 or phi.dim() != 4 or phi_sum.dim() != 3:
+        raise DeqsciHipError(f"gaptv: y (bsz,H,W), Phi (bsz,H,W,B), Phi_sum (bsz,H,W) expected, got {tuple(y.shape)}, "
+                             f"{tuple(phi.shape)}, {tuple(phi_sum.shape)}")
+    bsz, H, W = y.shape
+    B = phi.shape[-1]
+    if phi.shape[0] != phi_sum.shape[0] and min(phi.shape[0], phi_sum.shape[0]) == 1:     # one shared, the other per measurement
+        phi, phi_sum = phi.expand(bsz, -1, -1, -1).contiguous(), phi_sum.expand(bsz, -1, -1).contiguous()
+    shared = _phi_shared(phi, bsz)
+    if tuple(phi.shape[1:3]) != (H, W) or tuple(phi_sum.shape[1:]) != (H, W) or phi_sum.shape[0] != phi.shape[0]:
+        raise DeqsciHipError(f"gaptv: y {tuple(y.shape)}, Phi {tuple(phi.shape)} and Phi_sum {tuple(phi_sum.shape)} do not match")
+    if not isinstance(maxiter, int) or maxiter < 0 or not isinstance(n_iter_max, int) or n_iter_max < 1:
+        raise DeqsciHipError(f"gaptv: maxiter >= 0 and n_iter_max >= 1 must be integers, got {maxiter!r}, {n_iter_max!r}")
+    out = torch.empty((bsz, H, W, B), device=y.device, dtype=torch.float32)
+    stop = _stop_buffer((bsz, maxiter, B), y.device, return_stop)
+    nbytes = int(load().deqsci_gaptv_workspace_bytes(bsz, H, W, B))
+    _check(min(nbytes, 0), "gaptv_workspace_bytes")
+    with _dev(y):
+        ws = torch.empty((max(nbytes, 16),), device=y.device, dtype=torch.uint8)
+        _check(load().deqsci_gaptv_f32(_p(y, "y"), _p(phi, "Phi"), _p(phi_sum, "Phi_sum"), out.data_ptr(), bsz, H, W, B, shared, maxiter,
+                                       float(step), float(weight), float(eps), n_iter_max, None if stop is None else stop.data_ptr(),
+                                       ws.data_ptr(), _stream()), "gaptv")
+    return (out, stop) if return_stop else out
+
+
+def tv_chambolle(image, weight=0.1, eps=2e-4, n_iter_max=200, tau=0.25, return_stop=False):
+    """skimage 0.17.2's _denoise_tv_chambolle_nd on every plane of image (n,H,W) fp32 on a HIP device, with an explicit tau (1/4 for
+    a 2-D array, 1/6 for a (1,H,W) one) -> (n,H,W) fp32 (fp64 inside), and with return_stop=True also the (n,) int32 stop indices."""
+    if image.dim() != 3:
+        raise DeqsciHipError(f"tv_chambolle: image must be (n,H,W), got {tuple(image.shape)}")
+    n, H, W = image.shape
+    out = torch.empty((n, H, W), device=image.device, dtype=torch.float32)
+    stop = _stop_buffer((n,), image.device, return_stop)
+    nbytes = int(load().deqsci_tv_chambolle_workspace_bytes(n, H, W))
+    _check(min(nbytes, 0), "tv_chambolle_workspace_bytes")
+    with _dev(image):
+        ws = torch.empty((max(nbytes, 16),), device=image.device, dtype=torch.uint8)
+        _check(load().deqsci_tv_chambolle_f32(_p(image, "image"), out.data_ptr(), n, H, W, float(weight), float(eps), int(n_iter_max),
+                                              float(tau), None if stop is None else stop.data_ptr(), ws.data_ptr(), _stream()),
+               "tv_chambolle")
+    return (out, stop) if return_stop else out
 
 
 # ----------------------------------------------------------------------------- measurement helpers (bench.py)

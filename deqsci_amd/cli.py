@@ -9,6 +9,8 @@ Every flag of the reference parses (so its test_*.sh command lines run unchanged
 `--gpu_ids a,b,..` with more than one id is this build's addition: one process per listed GPU, every clip's
 measurements sharded over them (deqsci_amd.distributed), rank 0 prints and writes the PNGs.
 `--ssim` (also this build's) adds the per-clip SSIM and a 'Total Average SSIM' line (window 11, `--ssim_mode same|valid`).
+`--init_point gaptv` starts the DEQ from GAP-TV (the reference's commented-out initial point) instead of At(y, Phi); `--baseline gaptv`
+reconstructs by GAP-TV alone, with no DEQ (both this build's; deqsci_amd.gaptv).
 """
 import argparse
 import os
@@ -76,6 +78,12 @@ def parser():
     p.add_argument('--ssim_mode', default=None, choices=['same', 'valid'],
                    help="(this build) same (default) = the mean over the whole zero-padded SSIM map, as pytorch_ssim; valid = over the "
                         "map values whose window lies inside the frame.  Implies --ssim")
+    p.add_argument('--init_point', default='At', choices=['At', 'gaptv'],
+                   help="(this build) the DEQ's starting point: At (default) = At(y, Phi), the reference's initial_point; gaptv = GAP-TV, 40 "
+                        "iterations, step 1, TV weight 0.3 (the reference's commented-out initialiser), timed as part of the reconstruction")
+    p.add_argument('--baseline', default=None, choices=['gaptv'],
+                   help="(this build) reconstruct by the classical baseline alone, no DEQ: gaptv = GAP-TV (40 iterations, step 1, TV weight "
+                        "0.3).  The same clip lines, totals, PNGs and --ssim handling")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
     ignored.add_argument('--n_epochs', default=80)
     ignored.add_argument('--batch_size', type=int, default=1)
@@ -93,17 +101,20 @@ def parser():
 def run(args):
     """One rank (or the only process): build, evaluate every clip, rank 0 reports."""
     rank, world, _, dev = distributed.init_from_env("nccl")
-    loadpath = args.loadpath or checkpoint.shipped(SHIPPED[args.denoiser])
-    _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev)
-    opts = {}
-    if args.conv64 != 'auto':
-        opts["conv64"] = args.conv64
-    if args.anderson_arith != 'reference':
-        opts["anderson_arith"] = args.anderson_arith
-    if opts:
-        deq.engine_options = opts
+    deq = None
+    if args.baseline is None:
+        loadpath = args.loadpath or checkpoint.shipped(SHIPPED[args.denoiser])
+        _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev)
+        opts = {}
+        if args.conv64 != 'auto':
+            opts["conv64"] = args.conv64
+        if args.anderson_arith != 'reference':
+            opts["anderson_arith"] = args.anderson_arith
+        if opts:
+            deq.engine_options = opts
     if rank == 0:
-        print('loaded dict!')
+        if deq is not None:
+            print('loaded dict!')
         os.makedirs(args.savepath, exist_ok=True)
     images = {}
     ssim = bool(args.ssim or args.ssim_mode)
@@ -118,7 +129,8 @@ def run(args):
     t0 = time.time()
     avg, results = evaluate(deq, SCITestDataset(args.testpath), device=dev, on_clip=on_clip,
                             batch="all" if args.batch_measurements == "all" else bool(args.batch_measurements or world > 1),
-                            ssim=ssim, ssim_mode=args.ssim_mode or "same")
+                            ssim=ssim, ssim_mode=args.ssim_mode or "same", init=args.init_point,
+                            method="deq" if args.baseline is None else args.baseline)
     dt = time.time() - t0
     if rank == 0:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)

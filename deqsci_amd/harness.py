@@ -12,6 +12,8 @@ printed lines and PNG naming (ibid. :152-205) on top of the two.
     psnr                              skimage.metrics.peak_signal_noise_ratio for float input, data range 1
     ssim / clip_ssim                  pytorch_ssim._ssim per frame (this build's addition: the reference harness reports PSNR only)
     frame_payload                     the float image the reference hands to cv2.imwrite (ibid. :19-21)
+    init="gaptv" / method="gaptv"     the DEQ started from GAP-TV (utils/cg_utils.py:234, commented out there) / GAP-TV alone
+                                      (this build's additions, deqsci_amd.gaptv)
 """
 import math
 import os
@@ -167,11 +169,29 @@ def _residuals(deep_eq_module, n):
     return [r] * n, (info or {})
 
 
-def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same"):
+def _start(init, y, Phi, Phi_sum):
+    """The DEQ's starting point: "At" = initial_point (the reference's), "gaptv" = initial_point_gaptv (its commented-out one)."""
+    with torch.no_grad():
+        if init == "At":
+            return operators.initial_point(y, Phi, Phi_sum, None)
+        if init == "gaptv":
+            return operators.initial_point_gaptv(y, Phi, Phi_sum, None)
+    raise ValueError(f"init must be 'At' or 'gaptv', got {init!r}")
+
+
+def _check_method(method, init):
+    if method not in ("deq", "gaptv"):
+        raise ValueError(f"method must be 'deq' or 'gaptv', got {method!r}")
+    if init not in ("At", "gaptv"):
+        raise ValueError(f"init must be 'At' or 'gaptv', got {init!r}")
+
+
+def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same", init="At", method="deq"):
     """All scored measurements of one clip through `deep_eq_module.forward(y, Phi, Phi_sum, initial_point=, train_flag=False)`.
     batch=True: one call with y (M,H,W) and the shared mask (1,H,W,B); batch=False: M calls of batch 1 (the reference's
     schedule).  With a process group the measurements are sharded over its ranks and all-gathered.  ssim=True: also the
-    per-measurement SSIM (clip_ssim, after the timed part)."""
+    per-measurement SSIM (clip_ssim, after the timed part).  init: the DEQ's start, "At" (default) or "gaptv" (GAP-TV, timed with the
+    reconstruction).  method="gaptv": GAP-TV alone, no DEQ (deep_eq_module is not used; res is None)."""
     import time
     clip = as_clip(clip)
     Phi = clip['mask'].to(device)[None].contiguous()                  # (1,H,W,B)
@@ -179,10 +199,12 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     ids = scored_measurements(clip['file'], clip['meas'].shape[-1])
     y = clip['meas'].to(device).permute(2, 0, 1)[ids].contiguous()    # (M,H,W)
     Phi_sum = operators.phi_sum(Phi)
+    _check_method(method, init)
 
     def run(y_part, Phi_part):
-        with torch.no_grad():
-            x0 = operators.initial_point(y_part, Phi_part, Phi_sum, None)
+        if method == "gaptv":
+            return _start("gaptv", y_part, Phi_part, Phi_sum), [None] * y_part.shape[0]
+        x0 = _start(init, y_part, Phi_part, Phi_sum)
         rec = deep_eq_module.forward(y_part, Phi_part, Phi_sum, initial_point=x0, train_flag=False)
         res, _ = _residuals(deep_eq_module, y_part.shape[0])
         return rec.detach(), res
@@ -212,13 +234,13 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
                       ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None)
 
 
-def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same"):
+def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same", init="At", method="deq"):
     """The scored measurements of SEVERAL clips of one frame size as ONE engine batch, every measurement with its own clip's mask
     ((M,H,W,B) masks: nothing couples the measurements of a batch - alpha, residual, the ranges of the split-fp16 activations are all per
     measurement - so a measurement's reconstruction is the one it gets in any other batch, bit for bit).  What the reference's loop over
     clips and measurements (training/sci_equilibrium_training.py:157,171) becomes when the device wants eight measurements per call: the
     three shipped clips (1 + 1 + 6 measurements) are one call.  -> [ClipResult] in the clips' order; a clip's `seconds` is its share of
-    the call by frames.  ssim=True: also the per-measurement SSIM, as in reconstruct_clip."""
+    the call by frames.  ssim=True: also the per-measurement SSIM; init and method as in reconstruct_clip."""
     import time
     clips = [as_clip(c) for c in clips]
     ids = [scored_measurements(c['file'], c['meas'].shape[-1]) for c in clips]
@@ -226,11 +248,14 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
     y = torch.cat([c['meas'].to(device).permute(2, 0, 1)[i] for c, i in zip(clips, ids)]).contiguous()                        # (M,H,W)
     B = Phi.shape[-1]
     res = []
+    _check_method(method, init)
 
     def run(y_part, Phi_part):
         Ps = operators.phi_sum(Phi_part)
-        with torch.no_grad():
-            x0 = operators.initial_point(y_part, Phi_part, Ps, None)
+        if method == "gaptv":
+            res.extend([None] * y_part.shape[0])
+            return _start("gaptv", y_part, Phi_part, Ps)
+        x0 = _start(init, y_part, Phi_part, Ps)
         rec = deep_eq_module.forward(y_part, Phi_part, Ps, initial_point=x0, train_flag=False)
         res.extend(_residuals(deep_eq_module, y_part.shape[0])[0])
         return rec.detach()
@@ -250,18 +275,22 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
     return out
 
 
-def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same"):
+def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same", init="At",
+             method="deq"):
     """-> (mean over clips of the clip's mean PSNR, [ClipResult]).  batch: False = one measurement per call (the reference's schedule),
     True = a clip's measurements per call, "all" = the measurements of consecutive clips of one frame size per call
     (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements).  ssim=True fills every ClipResult.ssim
-    (window 11, ssim_mode "same" or "valid"); the mean over clips of the clip's mean SSIM is then sum(r.mean_ssim ...) / len(results)."""
+    (window 11, ssim_mode "same" or "valid"); the mean over clips of the clip's mean SSIM is then sum(r.mean_ssim ...) / len(results).
+    init: the DEQ's start, "At" (default) or "gaptv"; method="gaptv": reconstruct by GAP-TV alone (deep_eq_module may be None)."""
+    _check_method(method, init)
+    kw = dict(ssim=ssim, ssim_mode=ssim_mode, init=init, method=method)
     results = []
     if batch == "all":
         pending = []
 
         def flush():
             if pending:
-                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group, ssim=ssim, ssim_mode=ssim_mode):
+                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group, **kw):
                     results.append(r)
                     if on_clip is not None:
                         on_clip(r)
@@ -274,7 +303,7 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
         flush()
         return sum(r.mean_psnr for r in results) / len(results), results
     for sample in clips:
-        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group, ssim=ssim, ssim_mode=ssim_mode)
+        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group, **kw)
         results.append(r)
         if on_clip is not None:
             on_clip(r)
@@ -293,14 +322,15 @@ def png_payloads(result, prefix=""):
 
 
 def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, verbose=True, save_image=True,
-                    device="cuda", records=None, batch_measurements=False, ssim=False):
+                    device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq"):
     """Adapter with the reference's signature (training/sci_equilibrium_training.py:152): returns
     (average PSNR, {png path: float image}); prints one line per clip and the total; writes the PNGs.
     Default = the reference's schedule, one measurement per call (:171-181); batch_measurements="all" hands the measurements of all clips of
     one frame size to the engine as ONE batch (the three shipped clips: one call of eight); batch_measurements=True hands a clip's
     measurements to the engine as one batch (faster; on the chaotic FFDNet + Anderson @180 clip a different - equally valid -
     realisation, because the FFDNet head kernel is chosen by launch size).  ssim=True (this build's addition): every record gains "ssim",
-    every clip line '  SSIM: %.4f' and a 'Total Average SSIM' line follows the PSNR total; the return value is unchanged."""
+    every clip line '  SSIM: %.4f' and a 'Total Average SSIM' line follows the PSNR total; the return value is unchanged.  init="gaptv"
+    starts the DEQ from GAP-TV, method="gaptv" reconstructs by GAP-TV alone (both this build's additions, as in evaluate)."""
     images = {}
 
     def on_clip(r):
@@ -315,7 +345,8 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
                 print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
             else:
                 print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
-    avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim)
+    avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim, init=init,
+                            method=method)
     if verbose:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
         if ssim:

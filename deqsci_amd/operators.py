@@ -3,6 +3,7 @@
     A_torch_(x, Phi)  -> y      utils/cg_utils.py:85-90     (K1)
     At_torch_(y, Phi) -> x      utils/cg_utils.py:124-129   (K2)
     initial_point(y, Phi, Phi_sum, gt)   utils/cg_utils.py:228-229
+    initial_point_gaptv(y, Phi, Phi_sum, gt)   the GAP-TV start commented out at utils/cg_utils.py:234
     phi_sum(Phi)                 training/sci_equilibrium_training.py:162-163
     LinearOperator / SCIOperator operators/operator.py:3-14 (API type; SCIOperator is the working
                                  subclass the reference's `measurement_sci` stub :34-42 never became)
@@ -31,6 +32,13 @@ def At_torch_(y, Phi):
 def initial_point(y, Phi, Phi_sum=None, gt=None):
     """x0 = At(y, Phi); Phi_sum and gt are accepted and ignored, as in the reference."""
     return At_torch_(y, Phi)
+
+
+def initial_point_gaptv(y, Phi, Phi_sum, gt=None):
+    """x0 = GAP_TV_rec(y, Phi, Phi_sum, gt, A_, At_, maxiter=40, step_size=1, tv_weight=0.3): the reference's commented-out start
+    (deqsci_amd.gaptv; prints the PSNR line when gt has the output's shape, silent for gt=None)."""
+    from .gaptv import GAP_TV_rec
+    return GAP_TV_rec(y, Phi, Phi_sum, gt, A_torch_, At_torch_, maxiter=40, step_size=1, tv_weight=0.3)
 
 
 def phi_sum(Phi):

@@ -361,6 +361,27 @@ int64_t deqsci_ssim_workspace_bytes(int64_t M, int64_t H, int64_t W, int64_t B, 
 int deqsci_ssim_f32(const float* x, const float* y, double* out, int64_t M, int64_t H, int64_t W, int64_t B,
                     int layout, int window, int valid, int clamp_x, void* workspace, deqsci_stream_t stream);
 
+/* ---- GAP-TV: a classical baseline and the DEQ's other starting point (not on the DEQ's path) ----
+ * T0-T3  the reference's GAP_TV_rec (utils/cg_utils.py:207-224) with scikit-image 0.17.2's denoise_tv_chambolle
+ *     (multichannel, each frame a (1,H,W) channel: tau = 1/6), per measurement - a batch of bsz measurements gives what bsz calls
+ *     of one give, bit for bit.  y (bsz,H,W), Phi (bsz,H,W,B) or (1,H,W,B) when phi_shared != 0, Phi_sum (bsz,H,W) or (1,H,W):
+ *     fp32, 4-byte aligned; out (bsz,H,W,B) fp32.  maxiter GAP iterations of step `step`, each followed by at most n_iter_max
+ *     Chambolle iterations of weight `weight` that stop early when |E_prev - E| < eps E_init.  State in fp64.  B <= 128.
+ *     stop: NULL or (bsz, maxiter, B) int32, the Chambolle iteration each (measurement, GAP iteration, frame) stopped at, or
+ *     n_iter_max if the early stop never fired.  maxiter = 0 returns At(y, Phi).  workspace = deqsci_gaptv_workspace_bytes(...)
+ *     bytes, 16-byte aligned, no initialisation needed; out, stop and workspace must not overlap the inputs or each other (-4).
+ *     Launches 2 + maxiter (1 + n_iter_max) kernels and one memset on `stream`; no host synchronisation.
+ * T0,T2,T3  deqsci_tv_chambolle_f32: the Chambolle denoiser alone on n planes image (n,H,W) fp32 -> out (n,H,W) fp32 with an
+ *     explicit tau (1/4 for a 2-D array, 1/6 for a (1,H,W) channel); stop NULL or (n,) int32 as above.  The workspace queries
+ *     return DEQSCI_ERR_* (< 0) for invalid sizes. */
+int64_t deqsci_gaptv_workspace_bytes(int64_t bsz, int64_t H, int64_t W, int64_t B);
+int deqsci_gaptv_f32(const float* y, const float* phi, const float* phi_sum, float* out, int64_t bsz, int64_t H, int64_t W,
+                     int64_t B, int phi_shared, int maxiter, double step, double weight, double eps, int n_iter_max, int* stop,
+                     void* workspace, deqsci_stream_t stream);
+int64_t deqsci_tv_chambolle_workspace_bytes(int64_t n, int64_t H, int64_t W);
+int deqsci_tv_chambolle_f32(const float* image, float* out, int64_t n, int64_t H, int64_t W, double weight, double eps,
+                            int n_iter_max, double tau, int* stop, void* workspace, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */

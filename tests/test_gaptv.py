@@ -1,0 +1,433 @@
+"""GAP-TV: the kernels of csrc/tv.hip through the C ABI, _hip.gaptv / _hip.tv_chambolle, deqsci_amd.gaptv, the harness and the CLI.
+
+Yardsticks: (a) the float64 restatement of skimage 0.17.2's denoise_tv_chambolle (deqsci_amd.gaptv.tv_chambolle_float64, and a batched
+copy in this file for the large planes); (b) tests/golden/gaptv.npz, the reference's own GAP_TV_rec with the restatement of
+tests/golden/make_gaptv_golden.py in place of skimage (tests/golden/make_gaptv_golden.py).  A stop decision may only differ where the
+restated stop-test margin is below 1e-9 eps E_init (the order of the energy sums is not numpy's); nothing here comes that close."""
+import ctypes
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN, ROOT, rel_l2
+
+TIE = 1e-9
+EPS = 2e-4
+CLIPS = (("drop8", [0]), ("runner8", [0]), ("traffic", list(range(6))))
+
+
+def golden():
+    return np.load(os.path.join(GOLDEN, "gaptv.npz"))
+
+
+def small_case():
+    """The seeded case of gaptv.npz (restated from tests/golden/make_gaptv_golden.py: numpy's fixed RandomState stream, float64
+    arithmetic rounded to float32 once) -> y (1,37,53), Phi (1,37,53,8) float32 numpy."""
+    H, W, B = 37, 53, 8
+    rs = np.random.RandomState(20261016)
+    x = rs.random_sample((1, H, W, B))
+    x = (x + np.roll(x, 1, axis=1) + np.roll(x, 1, axis=2)) / 3.0
+    Phi = rs.random_sample((1, H, W, B)).astype(np.float32)
+    y = np.sum(x * Phi, axis=3).astype(np.float32)
+    sha = hashlib.sha256(y.tobytes() + Phi.tobytes()).hexdigest()[:16]
+    assert sha == str(golden()["small_sha"]), "the seeded inputs changed: numpy's RandomState stream is not what made the golden"
+    return y, Phi
+
+
+def phi_sum_np(Phi):
+    """Phi_sum as the golden's maker formed it (torch.sum over the frames in float32, zeros replaced by one)."""
+    s = torch.sum(torch.from_numpy(Phi), axis=3)
+    s[s == 0] = 1
+    return s.numpy()
+
+
+CROP = (slice(None), slice(104, 152), slice(96, 160), slice(None))       # the window of a (1,256,256,8) output kept in gaptv.npz
+
+
+def frames(rec):
+    """(8, 2) float64: per frame of a (1,H,W,8) output, the sum and the sum of squares of its float32 values (as gaptv.npz stores)."""
+    r = np.asarray(rec, dtype=np.float32)[0].astype(np.float64)
+    return np.stack([r.sum(axis=(0, 1)), (r * r).sum(axis=(0, 1))], axis=1)
+
+
+def matches_golden(rec, gd, key, tol):
+    """rec (1,256,256,8) against the reference's output `key` of gaptv.npz: rel-L2 in the stored window, per-frame sums and sums of squares
+    of the full frames to the same relative tolerance."""
+    rec = np.asarray(rec, dtype=np.float32)
+    assert rel_l2(rec[CROP], gd[key + "_crop"]) < tol
+    want = gd[key + "_frames"]
+    assert (np.abs(frames(rec) - want) / np.abs(want)).max() < tol
+
+
+def load_clip(clip):
+    from deqsci_amd.harness import load_test_data
+    return load_test_data(os.path.join(ROOT, "data", "test_gray", f"{clip}_cacti.mat"))
+
+
+def image(shape, seed):
+    """A smooth picture plus noise in about [0,1] (float32, CPU): TV has something to remove and the stop fires at various iterations."""
+    g = torch.Generator().manual_seed(seed)
+    n, H, W = shape
+    hh = torch.linspace(0, 3, H)[:, None]
+    ww = torch.linspace(0, 5, W)[None, :]
+    base = 0.5 + 0.3 * torch.sin(hh + ww) * torch.cos(0.7 * ww - hh)
+    return (base[None] + 0.1 * torch.randn(n, H, W, generator=g)).float()
+
+
+def tv_planes_float64(x, weight, eps, n_iter_max, tau):
+    """The restatement batched over planes x (n,H,W) (each plane on its own, frozen at its stop) -> (out, stop, tie) where tie is the
+    smallest |margin| / (eps E_init) over the plane's stop tests."""
+    img = x.double()
+    n, H, W = img.shape
+    ph, pw = torch.zeros_like(img), torch.zeros_like(img)
+    d = torch.zeros_like(img)
+    res = img.clone()
+    stop = torch.full((n,), n_iter_max, dtype=torch.int32)
+    tie = torch.full((n,), float("inf"), dtype=torch.float64)
+    active = torch.ones(n, dtype=torch.bool)
+    E_init = E_prev = None
+    for i in range(n_iter_max):
+        if i > 0:
+            d = -(ph + pw)
+            d[:, 1:, :] += ph[:, :-1, :]
+            d[:, :, 1:] += pw[:, :, :-1]
+            out = img + d
+        else:
+            out = img
+        res[active] = out[active]
+        E = (d ** 2).sum(dim=(1, 2))
+        gh, gw = torch.zeros_like(img), torch.zeros_like(img)
+        gh[:, :-1, :] = out[:, 1:, :] - out[:, :-1, :]
+        gw[:, :, :-1] = out[:, :, 1:] - out[:, :, :-1]
+        norm = torch.sqrt(gh ** 2 + gw ** 2)
+        E = (E + weight * norm.sum(dim=(1, 2))) / float(H * W)
+        den = norm * (tau / weight) + 1.
+        ph, pw = (ph - tau * gh) / den, (pw - tau * gw) / den
+        if i == 0:
+            E_init, E_prev = E.clone(), E.clone()
+            continue
+        margin = (E_prev - E).abs() - eps * E_init
+        tie = torch.where(active, torch.minimum(tie, margin.abs() / (eps * E_init)), tie)
+        fire = active & ((E_prev - E).abs() < eps * E_init)
+        stop[fire] = i
+        active = active & ~fire
+        E_prev = torch.where(active, E, E_prev)
+        if not active.any():
+            break
+    return res, stop, tie
+
+
+# ----------------------------------------------------------------------------- CPU
+def test_restatement_invariants():
+    from deqsci_amd.gaptv import denoise_tv_chambolle, tv_chambolle_float64
+    c = torch.full((1, 9, 11), 0.37, dtype=torch.float64)
+    assert torch.equal(denoise_tv_chambolle(c, 0.3), c)                                  # a constant image: nothing to remove
+    x = image((1, 23, 31), 1).double()
+    assert torch.equal(denoise_tv_chambolle(x, 0.3, n_iter_max=1), x)                   # n_iter_max=1: the first iteration's out
+    a = denoise_tv_chambolle(x, 0.3, n_iter_max=50)                                      # (1,H,W): tau 1/6
+    b = denoise_tv_chambolle(x[0], 0.3, n_iter_max=50)                                   # (H,W): tau 1/4
+    assert not torch.allclose(a[0], b, rtol=0, atol=1e-9)
+    assert torch.equal(a, tv_chambolle_float64(x, 0.3, n_iter_max=50))
+    # multichannel: every channel on its own
+    xs = torch.stack([image((23, 31, 1), s)[..., 0] for s in (2, 3, 4)], dim=-1).double()       # (23,31,3)
+    m = denoise_tv_chambolle(xs, 0.3, n_iter_max=50, multichannel=True)
+    for c_ in range(3):
+        assert torch.equal(m[..., c_], tv_chambolle_float64(xs[..., c_].contiguous(), 0.3, n_iter_max=50))
+    assert denoise_tv_chambolle(x.float(), 0.3).dtype == torch.float32
+    with pytest.raises(TypeError):
+        denoise_tv_chambolle(torch.zeros(4, 4, dtype=torch.int64))
+
+
+def test_batched_test_restatement_matches_the_package_one():
+    from deqsci_amd.gaptv import tv_chambolle_float64
+    x = image((3, 19, 27), 5)
+    out, stop, _ = tv_planes_float64(x, 0.3, EPS, 60, 1. / 6.)
+    for q in range(3):
+        o, s, _ = tv_chambolle_float64(x[q][None], 0.3, EPS, 60, return_stop=True)
+        assert int(stop[q]) == s and rel_l2(out[q].numpy(), o[0].numpy()) < 1e-14
+
+
+def test_cpu_gaptv_matches_golden_small_case(capsys):
+    from deqsci_amd import A_torch_, At_torch_, GAP_TV_rec
+    from deqsci_amd.gaptv import gaptv_float64
+    gd = golden()
+    y, Phi = small_case()
+    Ps = phi_sum_np(Phi)
+    f, stop = gaptv_float64(torch.from_numpy(y), torch.from_numpy(Phi), torch.from_numpy(Ps), 5, 1, 0.3, return_stop=True)
+    assert rel_l2(f.numpy(), gd["small_rec64"]) < 1e-12
+    assert np.array_equal(stop.numpy(), gd["small_stop"][0])
+    out = GAP_TV_rec(torch.from_numpy(y), torch.from_numpy(Phi), torch.from_numpy(Ps), None, A_torch_, At_torch_, 5, 1, 0.3)
+    assert out.dtype == torch.float32 and out.shape == (1, 37, 53, 8)
+    small_rec = gd["small_rec64"].astype(np.float32)                                   # the reference's float32 result
+    assert rel_l2(out.numpy(), small_rec) < 1e-7
+    assert capsys.readouterr().out == ""                                                # gt=None: silent
+    gt = torch.from_numpy(small_rec) + 0.01
+    GAP_TV_rec(torch.from_numpy(y), torch.from_numpy(Phi), torch.from_numpy(Ps), gt, A_torch_, At_torch_, 5, 1, 0.3)
+    assert capsys.readouterr().out == "GAP-TV: PSNR = 40.00 dB\n"
+    GAP_TV_rec(torch.from_numpy(y), torch.from_numpy(Phi), torch.from_numpy(Ps), gt[..., :4], A_torch_, At_torch_, 5, 1, 0.3)
+    assert capsys.readouterr().out == ""                                                # a gt of another shape: no line
+    with pytest.raises(ValueError):
+        GAP_TV_rec(torch.from_numpy(y), torch.from_numpy(Phi), torch.from_numpy(Ps), None, At_torch_, A_torch_, 5, 1, 0.3)
+
+
+@pytest.mark.slow
+def test_cpu_gaptv_matches_golden_drop8():
+    from deqsci_amd import A_torch_, At_torch_, GAP_TV_rec
+    gd = golden()
+    d = load_clip("drop8")
+    Phi = d["mask"][None]
+    out, stop = GAP_TV_rec(torch.from_numpy(d["meas"][..., 0][None].copy()), torch.from_numpy(Phi), torch.from_numpy(phi_sum_np(Phi)),
+                           None, A_torch_, At_torch_, 40, 1, 0.3, return_stop=True)
+    matches_golden(out.numpy(), gd, "rec_drop8_0", 1e-6)
+    assert np.array_equal(stop[0].numpy(), gd["stop"][0])
+
+
+def test_gaptv_exports_and_argument_validation_without_a_gpu():
+    from deqsci_amd import _hip
+    lib = _hip.load()
+    for name in ("deqsci_gaptv_f32", "deqsci_tv_chambolle_f32"):
+        assert name in _hip.SIGNATURES
+    for name in ("deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes"):
+        assert name in _hip.OTHER_EXPORTS
+    n = lib.deqsci_gaptv_workspace_bytes(8, 256, 256, 8)
+    N = 8 * 8 * 256 * 256 * 8
+    assert n >= 6 * N + 8 * 256 * 256 * 8 and n % 16 == 0
+    assert lib.deqsci_gaptv_workspace_bytes(1, 4, 4, 129) == -4                      # B > 128
+    assert lib.deqsci_gaptv_workspace_bytes(1, 0, 4, 8) == -2 and lib.deqsci_tv_chambolle_workspace_bytes(-1, 4, 4) == -2
+    assert lib.deqsci_tv_chambolle_workspace_bytes(0, 4, 4) >= 0
+    buf = (ctypes.c_float * 256)()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    q = p + 512
+    assert lib.deqsci_gaptv_f32(None, p, p, q, 1, 2, 2, 8, 1, 40, 1.0, 0.3, 2e-4, 30, None, q, None) == -1
+    assert lib.deqsci_gaptv_f32(p, p, p, q, 1, 2, 2, 8, 1, 40, 1.0, 0.0, 2e-4, 30, None, q, None) == -2          # weight 0
+    assert lib.deqsci_gaptv_f32(p, p, p, q, 1, 2, 2, 8, 1, 40, 1.0, 0.3, 2e-4, 0, None, q, None) == -2            # n_iter_max 0
+    assert lib.deqsci_gaptv_f32(p, p, p, q, 1, 2, 2, 8, 1, 40, 1.0, 0.3, 2e-4, 30, None, q + 4, None) == -3        # workspace alignment
+    assert lib.deqsci_tv_chambolle_f32(None, q, 1, 4, 4, 0.3, 2e-4, 30, 0.25, None, q, None) == -1
+    assert lib.deqsci_tv_chambolle_f32(p, q, 1, 4, 4, 0.3, 2e-4, 30, -1.0, None, q, None) == -2                   # tau <= 0
+    assert lib.deqsci_tv_chambolle_f32(p, p, 1, 4, 4, 0.3, 2e-4, 30, 0.25, None, q, None) == -4                   # in place
+    assert lib.deqsci_tv_chambolle_f32(p, q, 0, 4, 4, 0.3, 2e-4, 30, 0.25, None, q, None) == 0                    # nothing to do
+
+
+def test_cli_gaptv_flags_parse_and_default_path(monkeypatch, capsys, tmp_path):
+    from deqsci_amd import cli
+    a = cli.parser().parse_args([])
+    assert a.init_point == "At" and a.baseline is None
+    a = cli.parser().parse_args(["--init_point", "gaptv", "--baseline", "gaptv"])
+    assert a.init_point == "gaptv" and a.baseline == "gaptv"
+    for bad in (["--init_point", "admm"], ["--baseline", "admm"]):
+        with pytest.raises(SystemExit):
+            cli.parser().parse_args(bad)
+    # what run() hands the harness (no GPU here: the pipeline and evaluate are stand-ins)
+    calls = []
+
+    class R:
+        name, mean_psnr, mean_ssim, frames = "x.mat", 30.0, None, 8
+
+    def fake_eval(deq, clips, **kw):
+        calls.append((deq, kw))
+        kw["on_clip"](R())
+        return 30.0, [R()]
+    monkeypatch.setattr(cli.distributed, "init_from_env", lambda backend: (0, 1, 0, "cpu"))
+    monkeypatch.setattr(cli, "build_pipeline", lambda *a, **k: (None, "DEQ"))
+    monkeypatch.setattr(cli, "evaluate", fake_eval)
+    monkeypatch.setattr(cli, "SCITestDataset", lambda path: [])
+    monkeypatch.setattr(cli, "png_payloads", lambda r, p: {})
+    args = cli.parser().parse_args(["--savepath", str(tmp_path) + "/"])
+    cli.run(args)
+    out = capsys.readouterr().out.splitlines()
+    assert calls[-1][0] == "DEQ" and calls[-1][1]["init"] == "At" and calls[-1][1]["method"] == "deq"
+    assert out[0] == "loaded dict!" and out[1] == "['x.mat']   PSNR: 30.00 dB"
+    cli.run(cli.parser().parse_args(["--baseline", "gaptv", "--savepath", args.savepath]))
+    out = capsys.readouterr().out.splitlines()
+    assert calls[-1][0] is None and calls[-1][1]["method"] == "gaptv" and out[0] == "['x.mat']   PSNR: 30.00 dB"
+    cli.run(cli.parser().parse_args(["--init_point", "gaptv", "--savepath", args.savepath]))
+    assert calls[-1][0] == "DEQ" and calls[-1][1]["init"] == "gaptv" and calls[-1][1]["method"] == "deq"
+
+
+def test_harness_rejects_unknown_init_and_method():
+    from deqsci_amd import harness
+    with pytest.raises(ValueError):
+        harness.evaluate(None, [], init="admm")
+    with pytest.raises(ValueError):
+        harness.evaluate(None, [], method="admm")
+
+
+# ----------------------------------------------------------------------------- GPU
+DEV = "cuda"
+TV_SHAPES = [(1, 7, 9, 1), (1, 37, 53, 8), (2, 256, 256, 8), (1, 512, 512, 16)]      # (bsz,H,W,B): bsz*B planes of (1,H,W), tau 1/6
+TV_CASES = [(s, w, 30) for s in TV_SHAPES for w in (0.05, 0.3, 1.0)] + [(s, 0.3, n) for s in TV_SHAPES for n in (1, 200)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,weight,n_iter_max", TV_CASES)
+def test_tv_kernel_vs_float64_restatement(shape, weight, n_iter_max):
+    from deqsci_amd import _hip
+    bsz, H, W, B = shape
+    x = image((bsz * B, H, W), 100 + H + B)
+    want, wstop, tie = tv_planes_float64(x, weight, EPS, n_iter_max, 1. / 6.)
+    got, stop = _hip.tv_chambolle(x.to(DEV), weight, EPS, n_iter_max, 1. / 6., return_stop=True)
+    keep = tie >= TIE
+    assert keep.any()
+    assert torch.equal(stop.cpu()[keep], wstop[keep]), (stop.cpu(), wstop)
+    assert rel_l2(got.cpu()[keep].numpy(), want[keep].numpy()) < 1e-7
+    if n_iter_max == 1:
+        assert torch.equal(got.cpu(), x) and (stop.cpu() == 1).all()
+
+
+@pytest.mark.gpu
+def test_denoise_tv_chambolle_device_shapes():
+    from deqsci_amd.gaptv import denoise_tv_chambolle
+    x = image((1, 40, 60), 7)
+    for arr, mc in ((x[0], False), (x, False), (x[..., None], True), (x.permute(1, 2, 0).repeat(1, 1, 3), True)):
+        got = denoise_tv_chambolle(arr.to(DEV), 0.3, n_iter_max=100, multichannel=mc)
+        want = denoise_tv_chambolle(arr.double(), 0.3, n_iter_max=100, multichannel=mc)
+        assert got.shape == arr.shape and got.dtype == torch.float32
+        assert rel_l2(got.cpu().numpy(), want.numpy()) < 1e-7
+    with pytest.raises(NotImplementedError):
+        denoise_tv_chambolle(torch.zeros(2, 8, 8, device=DEV), 0.3)                      # a 3-D TV coupling two planes
+
+
+def _clip_inputs(clip, ms):
+    d = load_clip(clip)
+    Phi = torch.from_numpy(d["mask"][None].copy())
+    y = torch.from_numpy(np.ascontiguousarray(d["meas"][..., ms].transpose(2, 0, 1)))
+    return d, y, Phi
+
+
+@pytest.mark.gpu
+def test_device_gaptv_vs_golden():
+    """The reference (gaptv.npz): stops of all 8 measurements, PSNRs, the kept window and frame sums of drop8:0 and traffic:0; the full
+    frames of those two against the float64 restatement (whose agreement with the reference the CPU tests establish)."""
+    from deqsci_amd import A_torch_, At_torch_, GAP_TV_rec, phi_sum
+    from deqsci_amd.gaptv import gaptv_float64
+    from deqsci_amd.harness import clip_psnr
+    gd = golden()
+    stops, psnrs = [], []
+    for clip, ms in CLIPS:
+        d, y, Phi = _clip_inputs(clip, ms)
+        dPhi = Phi.to(DEV)
+        out, stop = GAP_TV_rec(y.to(DEV), dPhi, phi_sum(dPhi), None, A_torch_, At_torch_, 40, 1, 0.3, return_stop=True)
+        stops.append(stop.cpu().numpy())
+        psnrs += clip_psnr(out, d["gt"], ms)
+        if clip in ("drop8", "traffic"):
+            got = out[:1].cpu().numpy()
+            matches_golden(got, gd, f"rec_{clip}_0", 1e-6)
+            want = gaptv_float64(y[:1], Phi, torch.from_numpy(phi_sum_np(Phi.numpy())), 40, 1, 0.3)
+            assert rel_l2(got, want.float().numpy()) < 1e-6
+    stops = np.concatenate(stops)
+    keep = gd["tie"] >= TIE
+    assert keep.all() or keep.mean() > 0.99
+    assert np.array_equal(stops[keep], gd["stop"][keep])
+    assert np.abs(np.array(psnrs) - gd["psnr"]).max() < 1e-3, (psnrs, gd["psnr"])
+
+
+@pytest.mark.gpu
+def test_batch_is_bit_identical_to_single_calls_and_repeatable():
+    from deqsci_amd import _hip, phi_sum
+    ys, Phis = [], []
+    for clip, ms in CLIPS:
+        _, y, Phi = _clip_inputs(clip, ms)
+        ys.append(y)
+        Phis.append(Phi.expand(len(ms), -1, -1, -1))
+    y = torch.cat(ys).to(DEV)
+    Phi = torch.cat(Phis).contiguous().to(DEV)                                           # (8,H,W,B): every measurement its own mask
+    Ps = phi_sum(Phi)
+    out8, stop8 = _hip.gaptv(y, Phi, Ps, return_stop=True)
+    again, stop_again = _hip.gaptv(y, Phi, Ps, return_stop=True)
+    assert torch.equal(out8, again) and torch.equal(stop8, stop_again)
+    for m in range(8):
+        o, s = _hip.gaptv(y[m:m + 1].contiguous(), Phi[m:m + 1].contiguous(), Ps[m:m + 1].contiguous(), return_stop=True)
+        assert torch.equal(o, out8[m:m + 1]) and torch.equal(s, stop8[m:m + 1]), m
+
+
+@pytest.mark.gpu
+def test_zero_phi_sum_pixel_gives_finite_output():
+    from deqsci_amd import _hip, phi_sum
+    y, Phi = small_case()
+    Phi = Phi.copy()
+    Phi[0, 10, 20, :] = 0                                                                  # Phi_sum 0 -> 1 at one pixel
+    Phi[0, :, 0, :] = 0                                                                    # and along a whole column
+    dPhi = torch.from_numpy(Phi).to(DEV)
+    Ps = phi_sum(dPhi)
+    assert float(Ps[0, 10, 20]) == 1.0
+    out = _hip.gaptv(torch.from_numpy(y).to(DEV), dPhi, Ps, maxiter=5)
+    assert torch.isfinite(out).all()
+
+
+@pytest.mark.gpu
+def test_bad_shape_or_dtype_raises():
+    from deqsci_amd import _hip
+    y = torch.zeros(1, 8, 8, device=DEV)
+    Phi = torch.ones(1, 8, 8, 4, device=DEV)
+    Ps = torch.full((1, 8, 8), 4.0, device=DEV)
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.gaptv(y.double(), Phi, Ps)
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.gaptv(y, Phi[:, :7], Ps)
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.gaptv(y, Phi, Ps[0])
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.gaptv(y.cpu(), Phi.cpu(), Ps.cpu())                                          # no host fallback in the binding
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.gaptv(y, torch.ones(1, 8, 8, 129, device=DEV), Ps)                          # B > 128
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.tv_chambolle(torch.zeros(8, 8, device=DEV))
+    with pytest.raises(_hip.DeqsciHipError):
+        _hip.tv_chambolle(torch.zeros(1, 8, 8, device=DEV, dtype=torch.float16))
+
+
+@pytest.mark.gpu
+def test_deq_from_gaptv_start_vs_golden():
+    from deqsci_amd import checkpoint, initial_point_gaptv, phi_sum
+    from deqsci_amd.cli import build_pipeline
+    from deqsci_amd.harness import clip_psnr
+    gd = golden()
+    d, y, Phi = _clip_inputs("drop8", [0])
+    _, deq = build_pipeline("SimpleCNN", checkpoint.shipped("cnn"), and_maxiters=10)
+    dy, dPhi = y.to(DEV), Phi.to(DEV)
+    Ps = phi_sum(dPhi)
+    with torch.no_grad():
+        x0 = initial_point_gaptv(dy, dPhi, Ps)
+    rec = deq.forward(dy, dPhi, Ps, initial_point=x0, train_flag=False)
+    matches_golden(rec.detach().cpu().numpy(), gd, "deq_rec", 1e-4)
+    assert abs(clip_psnr(rec, d["gt"], [0])[0] - float(gd["deq_psnr"])) < 0.01
+
+
+def _cli(tmp_path, *extra):
+    env = dict(os.environ)
+    env.pop("LOCAL_RANK", None)
+    cmd = [sys.executable, "-m", "deqsci_amd.cli", "--denoiser", "SimpleCNN", "--and_maxiters", "10", "--testpath",
+           os.path.join(ROOT, "data", "test_gray") + "/", "--savepath", str(tmp_path) + "/"] + list(extra)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return out.stdout.splitlines()
+
+
+def _total(lines):
+    t = [ln for ln in lines if ln.startswith("--------------------------------- Total Average PSNR: ")]
+    assert len(t) == 1, lines
+    return float(t[0].split(": ")[-1].split()[0])
+
+
+@pytest.mark.gpu
+def test_cli_baseline_gaptv(tmp_path):
+    gd = golden()
+    lines = _cli(tmp_path, "--baseline", "gaptv", "--ssim")
+    assert "loaded dict!" not in lines
+    clip_lines = [ln for ln in lines if ln.startswith("['")]
+    assert len(clip_lines) == 3 and all("  PSNR: " in ln and "  SSIM: " in ln for ln in clip_lines)
+    assert abs(_total(lines) - float(np.mean(gd["clip_mean_psnr"]))) < 0.01
+    assert sum("Total Average SSIM" in ln for ln in lines) == 1
+    assert len([f for f in os.listdir(tmp_path) if f.endswith(".png")]) == 8 * 8
+
+
+@pytest.mark.gpu
+def test_cli_init_point_gaptv(tmp_path):
+    lines = _cli(tmp_path, "--init_point", "gaptv", "--batch_measurements", "all")
+    assert lines[0] == "loaded dict!" and len([ln for ln in lines if ln.startswith("['")]) == 3
+    assert 15.0 < _total(lines) < 50.0
