@@ -18,6 +18,7 @@ build does not - DESIGN.md section 5.)
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _hip, operators
@@ -27,6 +28,12 @@ TV_ITERS = 30                      # n_iter_max of the reference's call (cg_util
 
 
 # ----------------------------------------------------------------------------- float64 restatement (CPU path and test yardstick)
+def sqrt_float64(x):
+    """The correctly rounded square root of a float64 CPU tensor, as numpy's and the device's.  (torch's vectorised CPU sqrt is not:
+    with AVX-512 it is one ulp off on about 0.7 % of uniform inputs.)"""
+    return torch.from_numpy(np.sqrt(x.contiguous().numpy()))
+
+
 def tv_chambolle_float64(image, weight=0.1, eps=TV_EPS, n_iter_max=200, return_stop=False):
     """skimage 0.17.2 _denoise_tv_chambolle_nd on one array of any dimension, in float64 torch, every operation in skimage's order.
     -> out (float64), and with return_stop=True also (stop iteration or n_iter_max, margin |E_prev - E| - eps E_init of the last
@@ -61,7 +68,7 @@ def tv_chambolle_float64(image, weight=0.1, eps=TV_EPS, n_iter_max=200, return_s
         sq = g[0] ** 2
         for ax in range(1, ndim):
             sq = sq + g[ax] ** 2
-        norm = torch.sqrt(sq)
+        norm = sqrt_float64(sq)
         E += weight * float(norm.sum())
         norm = norm * (tau / weight)
         norm = norm + 1.
@@ -78,6 +85,30 @@ def tv_chambolle_float64(image, weight=0.1, eps=TV_EPS, n_iter_max=200, return_s
     return (out, stop, margin) if return_stop else out
 
 
+def frame_sum_float64(t):
+    """np.sum(t, axis=-1) for a float64 tensor, in numpy's pairwise_sum order: fewer than 8 terms left to right (from 0.); up to 128,
+    eight running sums r_k over k, k + 8, ... folded ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the n % 8 last terms in
+    order; above 128, the two halves split at n2 = n // 2 rounded down to a multiple of 8, each summed the same way, then added."""
+    n = t.shape[-1]
+    if n > 128:
+        n2 = n // 2
+        n2 -= n2 % 8
+        return frame_sum_float64(t[..., :n2]) + frame_sum_float64(t[..., n2:])
+    if n < 8:
+        s = t[..., 0] + 0.
+        b = 1
+    else:
+        r = [t[..., k] for k in range(8)]
+        b = 8
+        while b + 8 <= n:
+            r = [r[k] + t[..., b + k] for k in range(8)]
+            b += 8
+        s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for k in range(b, n):
+        s = s + t[..., k]
+    return s
+
+
 def gaptv_float64(y, Phi, Phi_sum, maxiter, step_size, tv_weight, eps=TV_EPS, n_iter_max=TV_ITERS, return_stop=False):
     """The reference's GAP_TV_rec in float64 torch for ONE measurement: y (1,H,W), Phi (1,H,W,B), Phi_sum (1,H,W) float32 ->
     (1,H,W,B) float64, and with return_stop=True also the (maxiter, B) stop indices."""
@@ -86,19 +117,7 @@ def gaptv_float64(y, Phi, Phi_sum, maxiter, step_size, tv_weight, eps=TV_EPS, n_
     y1 = torch.zeros(y.shape, dtype=torch.float64)
     stops = torch.zeros((maxiter, Phi.shape[-1]), dtype=torch.int32)
     for it in range(maxiter):
-        t = f * Phi64
-        fb = t[..., 0]                                             # np.sum(..., axis=3): numpy's pairwise order for one block
-        if t.shape[-1] >= 8:
-            r = [t[..., k] for k in range(8)]
-            b = 8
-            while b + 8 <= t.shape[-1]:
-                r = [r[k] + t[..., b + k] for k in range(8)]
-                b += 8
-            fb = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
-        else:
-            b = 1
-        for k in range(b, t.shape[-1]):
-            fb = fb + t[..., k]
+        fb = frame_sum_float64(f * Phi64)                          # A_: np.sum(f * Phi, axis=3)
         y1 = y1 + (y.double() - fb)
         r = (y1 - fb) / Phi_sum.double()
         f = f + step_size * (r[..., None] * Phi64)

@@ -2,7 +2,8 @@
 """Generate tests/golden/gaptv.npz by IMPORTING the reference's GAP_TV_rec (utils/cg_utils.py, through ref_shims.py) and running its
 own code on CPU.  Like make_golden.py it runs only where the reference is mounted, and it stores data only.
 
-    python tests/golden/make_gaptv_golden.py
+    python tests/golden/make_gaptv_golden.py              -> gaptv.npz
+    python tests/golden/make_gaptv_golden.py --shapes     -> gaptv_shapes.npz
 
 The reference calls skimage.restoration.denoise_tv_chambolle (scikit-image 0.17.2), which is not installed here.  This script replaces
 cg_utils.denoise_tv_chambolle with `denoise_tv_chambolle` below: a float64 restatement, line by line, of skimage 0.17.2's
@@ -32,6 +33,15 @@ only source of randomness is numpy's RandomState, a stream numpy keeps fixed, an
   deq_rec_crop, deq_rec_frames, deq_psnr   the reference's DEQFixedPoint (SimpleCNN, cnn.ckpt, Anderson m=5 beta=1 lam=1e-2, 10 iterations, tol 1e-5)
                             on drop8:0 started from its GAP-TV point (40 iterations, step 1, TV weight 0.3): its reconstruction in
                             CROP, per-frame sum and sum of squares of the full one, and its PSNR
+
+gaptv_shapes.npz (--shapes): the seeded cases of SHAPES (ragged sizes, B from 1 to 128, binary, non-binary and zero-sum-pixel masks,
+a step and a TV weight other than the defaults).  Inputs are rebuilt by `shape_case` (restated in tests/test_gaptv_edges.py) and
+checked by hash; per case <name>:
+  <name>_params             (H, W, B, maxiter, step_size, tv_weight, seed) float64
+  <name>_sha                sha256 prefix of the float32 bytes of y, Phi
+  <name>_rec64              the float64 result of the last TV call (1,H,W,B)
+  <name>_stop, <name>_margin, <name>_tie   the per-call records (1, maxiter, B), as above
+Every seed was picked so that no stop test comes within 1e-9 eps E_init of a tie (min tie >= 1e-9).
 """
 import hashlib
 import os
@@ -157,13 +167,13 @@ def harness_psnr(rec, gt):
     return 10.0 * np.log10(1.0 / np.mean(d * d, dtype=np.float64))
 
 
-def run(y, Phi, gt, maxiter):
+def run(y, Phi, gt, maxiter, step=STEP, tv_weight=TV_WEIGHT):
     """The reference's GAP_TV_rec on one measurement (batch 1) -> (float32 result, PSNR printed, (maxiter, B) records)."""
     Ps = torch.sum(Phi, axis=3)
     Ps[Ps == 0] = 1
     del RECORD[:]
     ref_shims.PSNR_LOG.clear()
-    rec = cg_utils.GAP_TV_rec(y, Phi, Ps, gt, cg_utils.A_, cg_utils.At_, maxiter=maxiter, step_size=STEP, tv_weight=TV_WEIGHT)
+    rec = cg_utils.GAP_TV_rec(y, Phi, Ps, gt, cg_utils.A_, cg_utils.At_, maxiter=maxiter, step_size=step, tv_weight=tv_weight)
     f64 = cg_utils.psnr(rec.numpy().astype(np.float64), gt)                # (the print used the float64 f)
     B = Phi.shape[-1]
     rs = np.array(RECORD, dtype=object).reshape(maxiter, B, 3)
@@ -221,5 +231,48 @@ def main():
     print("wrote", os.path.join(HERE, "gaptv.npz"), os.path.getsize(os.path.join(HERE, "gaptv.npz")), "bytes")
 
 
+# name, H, W, B, maxiter, step_size, tv_weight, mask, seed: B = 1, 5 (< 8: left to right), 13 (the 8-sum loop and a tail of 5), 16 (two
+# rounds, no tail), 128 (sixteen rounds, MAX_FRAMES); 17 x 130 is three 64-column tiles, the last ragged, and two 16-row tiles
+SHAPES = (("b1", 19, 23, 1, 6, 1.0, 0.3, "float", 1),
+          ("b5", 17, 130, 5, 4, 1.0, 0.3, "binary", 2),
+          ("b13", 11, 23, 13, 4, 1.0, 0.3, "zeros", 3),
+          ("b16", 9, 21, 16, 4, 1.5, 0.3, "float", 4),
+          ("b128", 5, 7, 128, 3, 1.0, 0.1, "binary", 5))
+
+
+def shape_case(H, W, B, mask, seed):
+    """A seeded case (numpy float64 arithmetic, rounded to float32 once; restated in tests/test_gaptv_edges.py) -> y (1,H,W),
+    Phi (1,H,W,B) float32.  mask: "float" uniform in [0,1), "binary" 0/1, "zeros" uniform with column 0 and the centre pixel zero
+    in every frame (Phi_sum 0 there, replaced by 1)."""
+    rs = np.random.RandomState(seed)
+    x = rs.random_sample((1, H, W, B))
+    x = (x + np.roll(x, 1, axis=1) + np.roll(x, 1, axis=2)) / 3.0
+    u = rs.random_sample((1, H, W, B))
+    Phi = (u < 0.5).astype(np.float32) if mask == "binary" else u.astype(np.float32)
+    if mask == "zeros":
+        Phi[0, :, 0, :] = 0
+        Phi[0, H // 2, W // 2, :] = 0
+    y = np.sum(x * Phi, axis=3).astype(np.float32)
+    return y, Phi
+
+
+def shapes():
+    out = {}
+    for name, H, W, B, it, step, weight, mask, seed in SHAPES:
+        t0 = time.time()
+        y, Phi = shape_case(H, W, B, mask, seed)
+        _, _, rs = run(torch.from_numpy(y), torch.from_numpy(Phi), np.zeros((1, H, W, B), np.float32), it, step, weight)
+        tie = rs[..., 2].astype(np.float64)
+        assert tie.min() >= 1e-9, (name, tie.min())
+        out.update({f"{name}_params": np.array([H, W, B, it, step, weight, seed], np.float64), f"{name}_sha": np.array(sha(y, Phi)),
+                    f"{name}_rec64": LAST[0].astype(np.float64), f"{name}_stop": rs[None, ..., 0].astype(np.int32),
+                    f"{name}_margin": rs[None, ..., 1].astype(np.float64), f"{name}_tie": tie[None]})
+        print(f"{name}: {H}x{W}x{B}, {it} iterations, stops {sorted(set(rs[..., 0].ravel().tolist()))}, min tie {tie.min():.2e}, "
+              f"{time.time() - t0:.1f} s", flush=True)
+    path = os.path.join(HERE, "gaptv_shapes.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    shapes() if sys.argv[1:] == ["--shapes"] else main()

@@ -82,6 +82,7 @@ def image(shape, seed):
 def tv_planes_float64(x, weight, eps, n_iter_max, tau):
     """The restatement batched over planes x (n,H,W) (each plane on its own, frozen at its stop) -> (out, stop, tie) where tie is the
     smallest |margin| / (eps E_init) over the plane's stop tests."""
+    from deqsci_amd.gaptv import sqrt_float64
     img = x.double()
     n, H, W = img.shape
     ph, pw = torch.zeros_like(img), torch.zeros_like(img)
@@ -104,7 +105,7 @@ def tv_planes_float64(x, weight, eps, n_iter_max, tau):
         gh, gw = torch.zeros_like(img), torch.zeros_like(img)
         gh[:, :-1, :] = out[:, 1:, :] - out[:, :-1, :]
         gw[:, :, :-1] = out[:, :, 1:] - out[:, :, :-1]
-        norm = torch.sqrt(gh ** 2 + gw ** 2)
+        norm = sqrt_float64(gh ** 2 + gw ** 2)
         E = (E + weight * norm.sum(dim=(1, 2))) / float(H * W)
         den = norm * (tau / weight) + 1.
         ph, pw = (ph - tau * gh) / den, (pw - tau * gw) / den
@@ -112,7 +113,9 @@ def tv_planes_float64(x, weight, eps, n_iter_max, tau):
             E_init, E_prev = E.clone(), E.clone()
             continue
         margin = (E_prev - E).abs() - eps * E_init
-        tie = torch.where(active, torch.minimum(tie, margin.abs() / (eps * E_init)), tie)
+        # E_init = 0 only for a constant plane: E stays exactly 0 and the test 0 < 0 can never fire, so it is no tie
+        ratio = torch.where(E_init > 0, margin.abs() / (eps * E_init), torch.full_like(E_init, float("inf")))
+        tie = torch.where(active, torch.minimum(tie, ratio), tie)
         fire = active & ((E_prev - E).abs() < eps * E_init)
         stop[fire] = i
         active = active & ~fire
@@ -120,6 +123,29 @@ def tv_planes_float64(x, weight, eps, n_iter_max, tau):
         if not active.any():
             break
     return res, stop, tie
+
+
+def gaptv_planes_float64(y, Phi, Phi_sum, maxiter, step, weight, n_iter_max=30):
+    """deqsci_amd.gaptv.gaptv_float64 batched over measurements, each with its own mask: y (bsz,H,W), Phi (bsz,H,W,B), Phi_sum
+    (bsz,H,W) float32 -> (f (bsz,H,W,B) float64, stop (bsz, maxiter, B) int32, tie (bsz,): the smallest tie of tv_planes_float64 over
+    every TV call of the measurement)."""
+    from deqsci_amd.gaptv import frame_sum_float64
+    bsz, H, W, B = Phi.shape
+    Phi64 = Phi.double()
+    f = (y[..., None] * Phi).double()
+    y1 = torch.zeros(y.shape, dtype=torch.float64)
+    stop = torch.zeros((bsz, maxiter, B), dtype=torch.int32)
+    tie = torch.full((bsz,), float("inf"), dtype=torch.float64)
+    for it in range(maxiter):
+        fb = frame_sum_float64(f * Phi64)
+        y1 = y1 + (y.double() - fb)
+        r = (y1 - fb) / Phi_sum.double()
+        f = f + step * (r[..., None] * Phi64)
+        out, s, t = tv_planes_float64(f.permute(0, 3, 1, 2).reshape(bsz * B, H, W), weight, EPS, n_iter_max, 1. / 6.)
+        f = out.reshape(bsz, B, H, W).permute(0, 2, 3, 1).contiguous()
+        stop[:, it] = s.reshape(bsz, B)
+        tie = torch.minimum(tie, t.reshape(bsz, B).min(dim=1).values)
+    return f, stop, tie
 
 
 # ----------------------------------------------------------------------------- CPU
@@ -275,6 +301,7 @@ def test_tv_kernel_vs_float64_restatement(shape, weight, n_iter_max):
     assert keep.any()
     assert torch.equal(stop.cpu()[keep], wstop[keep]), (stop.cpu(), wstop)
     assert rel_l2(got.cpu()[keep].numpy(), want[keep].numpy()) < 1e-7
+    assert torch.equal(got.cpu()[keep], want[keep].float())                             # every operation is the restatement's
     if n_iter_max == 1:
         assert torch.equal(got.cpu(), x) and (stop.cpu() == 1).all()
 
@@ -335,7 +362,8 @@ def test_batch_is_bit_identical_to_single_calls_and_repeatable():
         ys.append(y)
         Phis.append(Phi.expand(len(ms), -1, -1, -1))
     y = torch.cat(ys).to(DEV)
-    Phi = torch.cat(Phis).contiguous().to(DEV)                                           # (8,H,W,B): every measurement its own mask
+    # (8,H,W,B), one mask per measurement; the shipped clips' masks are equal, test_gaptv_edges.py checks distinct ones
+    Phi = torch.cat(Phis).contiguous().to(DEV)
     Ps = phi_sum(Phi)
     out8, stop8 = _hip.gaptv(y, Phi, Ps, return_stop=True)
     again, stop_again = _hip.gaptv(y, Phi, Ps, return_stop=True)
@@ -357,6 +385,8 @@ def test_zero_phi_sum_pixel_gives_finite_output():
     assert float(Ps[0, 10, 20]) == 1.0
     out = _hip.gaptv(torch.from_numpy(y).to(DEV), dPhi, Ps, maxiter=5)
     assert torch.isfinite(out).all()
+    want, _, tie = gaptv_planes_float64(torch.from_numpy(y), torch.from_numpy(Phi), Ps.cpu(), 5, 1, 0.3)
+    assert float(tie[0]) >= TIE and torch.equal(out.cpu(), want.float())
 
 
 @pytest.mark.gpu
