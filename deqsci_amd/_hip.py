@@ -801,33 +801,54 @@ def ffdnet_head_split16(x, weights, sigma, out=None, in_rng=None, in_exp=SP16_DE
     """x (n,1,2H,2W) planar, sigma (n,) or (1,) -> relu(conv3x3(cat(sigma map, pixel_unshuffle(x,2)), w)) as an Sp16, on the f16 matrix
     cores with the split-fp16 arithmetic (`weights` = HeadSplit16Weights(w)).  in_rng: range slot holding max |x| of the image (the
     kernel adds sigma itself); (out_rng, out_exp): the range of the output; track: a slot that receives max |output|."""
+    return _ffdnet_head("ffdnet_head_split16", Sp16, x, weights, sigma, out, in_rng, in_exp, out_rng, out_exp, track)
+
+
+def _ffdnet_head(what, act, x, weights, sigma, out, in_rng, in_exp, out_rng, out_exp, track=None):
+    """ffdnet_head_split16 (act = Sp16) and ffdnet_head_p32 (act = P32): one kernel each, the same arguments but for `track`, which only
+    the sp16 form has."""
     n, c, H2, W2 = x.shape
     if c != 1 or H2 % 2 or W2 % 2 or not isinstance(weights, HeadSplit16Weights):
-        raise DeqsciHipError(f"ffdnet_head_split16: (n,1,even,even) image and HeadSplit16Weights required, got {tuple(x.shape)}")
+        raise DeqsciHipError(f"{what}: (n,1,even,even) image and HeadSplit16Weights required, got {tuple(x.shape)}")
     if sigma.numel() not in (1, n) or sigma.dtype != torch.float32 or not sigma.is_cuda:
-        raise DeqsciHipError("ffdnet_head_split16: sigma must be a fp32 GPU tensor with 1 or n elements")
+        raise DeqsciHipError(f"{what}: sigma must be a fp32 GPU tensor with 1 or n elements")
     H, W = H2 // 2, W2 // 2
-    o = out if out is not None else Sp16.empty(n, H, W, x.device)
+    o = out if out is not None else act.empty(n, H, W, x.device)
+    if not isinstance(o, act) or (o.n, o.H, o.W) != (n, H, W):
+        raise DeqsciHipError(f"{what}: out must be a {act.__name__} of the output's shape")
     o.rng, o.exp = out_rng, int(out_exp)
     wp = weights.packed if weights.packed.device == x.device else weights.packed.to(x.device)
+    args = (_p(x, "x"), wp.data_ptr(), sigma.data_ptr(), 0 if sigma.numel() == 1 else sigma.stride(0), o.t.data_ptr(), n, H, W, weights.sw,
+            _rng(in_rng, n), int(in_exp), _rng(out_rng, n), o.exp)
     with _dev(x):
-        _check(load().deqsci_ffdnet_head_split16(_p(x, "x"), wp.data_ptr(), sigma.data_ptr(), 0 if sigma.numel() == 1 else sigma.stride(0),
-                                                 o.t.data_ptr(), n, H, W, weights.sw, _rng(in_rng, n), int(in_exp), _rng(out_rng, n), o.exp,
-                                                 _rng(track, n), _stream()), "ffdnet_head_split16")
+        if act is Sp16:
+            _check(load().deqsci_ffdnet_head_split16(*args, _rng(track, n), _stream()), what)
+        else:
+            _check(load().deqsci_ffdnet_head_p32(*args, _stream()), what)
     return o
 
 
 def tail_split16(h, weights, out=None):
     """h Sp16 -> the denoiser's last layer on the f16 matrix cores: COUT = 4: planar noise (n,1,2H,2W) = pixel_shuffle(conv3x3(h, w, pad=1), 2)
     (FFDNet); COUT = 1: (n,1,H,W) = conv3x3(h, w, pad=1) (SimpleCNN).  `weights` = TailSplit16Weights(w)."""
-    if not isinstance(h, Sp16) or not isinstance(weights, TailSplit16Weights):
+    if not isinstance(h, Sp16):
         raise DeqsciHipError("tail_split16: an Sp16 activation and TailSplit16Weights are required")
+    return _tail("tail_split16", h, weights, out)
+
+
+def _tail(what, h, weights, out):
+    """tail_split16 (h Sp16) and ffdnet_tail_p32 (h P32): the kernel is picked by h's layout and the weights' COUT."""
+    if not isinstance(weights, TailSplit16Weights):
+        raise DeqsciHipError(f"{what}: TailSplit16Weights of a (4,64,3,3) or (1,64,3,3) weight are required")
     f = 2 if weights.cout == 4 else 1
     o = out if out is not None else torch.empty((h.n, 1, f * h.H, f * h.W), device=h.t.device, dtype=torch.float32)
     wp = weights.packed if weights.packed.device == h.t.device else weights.packed.to(h.t.device)
-    fn = load().deqsci_ffdnet_tail_split16 if weights.cout == 4 else load().deqsci_conv3x3_c64_to_1_split16
+    if isinstance(h, Sp16):
+        fn = load().deqsci_ffdnet_tail_split16 if weights.cout == 4 else load().deqsci_conv3x3_c64_to_1_split16
+    else:
+        fn = load().deqsci_ffdnet_tail_p32 if weights.cout == 4 else load().deqsci_conv3x3_c64_to_1_p32
     with _dev(h.t):
-        _check(fn(h.t.data_ptr(), wp.data_ptr(), _p(o, "out"), h.n, h.H, h.W, weights.sw, _rng(h.rng, h.n), h.exp, _stream()), "tail_split16")
+        _check(fn(h.t.data_ptr(), wp.data_ptr(), _p(o, "out"), h.n, h.H, h.W, weights.sw, _rng(h.rng, h.n), h.exp, _stream()), what)
     return o
 
 
@@ -866,51 +887,47 @@ def conv3x3_c64_split16(x, weights, bias=None, relu=True, out=None, out_f32=Fals
     return o
 
 
-class Split16Stack:
-    """A RUN of 64->64 layers for deqsci_conv3x3_c64_split16_stack: the device table of (weights, bias, w_exp, relu) per layer - three
-    8-byte words each - the tensors it points to (kept alive here), and per launch shape the progress words of the tiles (zeroed once:
-    they count on from launch to launch) and the two ping-pong buffers (kept: a captured hipGraph carries their addresses)."""
-    __slots__ = ("table", "n_layers", "keep", "_state", "act")
-    TILE = (16, 32)                                                   # block tile of the kernel: rows x columns of output pixels
+class _Stack:
+    """A RUN of 64->64 layers for one stack launch: the device table of (weights, bias, w_exp, relu) per layer - three 8-byte words each -
+    the tensors it points to (kept alive here), and per launch shape the progress words of the tiles (zeroed once: they count on from
+    launch to launch) and the two ping-pong buffers (kept: a captured hipGraph carries their addresses).  Split16Stack and Wino16Stack
+    name their kernel's activation class ACT, weights class WEIGHTS, block TILE (rows x columns of output pixels), measurement hook kind
+    HOOK and C entry point ENTRY, and the head, launch and tail functions of that layout (the engine's slice-by-slice f-call)."""
+    __slots__ = ("table", "n_layers", "keep", "_state")
 
     def __init__(self, layers, device):
-        """layers: [(Split16Weights, bias tensor or None, relu), ...]"""
+        """layers: [(WEIGHTS, bias tensor or None, relu), ...]"""
         rows, keep = [], []
-        self.act = Sp16
         for w16, bias, relu in layers:
-            if not isinstance(w16, self._weights_class()):
-                raise DeqsciHipError(f"{type(self).__name__}: every layer needs {self._weights_class().__name__}")
+            if not isinstance(w16, self.WEIGHTS):
+                raise DeqsciHipError(f"{type(self).__name__}: every layer needs {self.WEIGHTS.__name__}")
             wp = w16.packed if w16.packed.device == torch.device(device) else w16.packed.to(device)
             b = None if bias is None else f32c(bias.detach().to(device))
             if b is not None and b.numel() < 64:
-                raise DeqsciHipError("Split16Stack: bias must have 64 elements")
+                raise DeqsciHipError(f"{type(self).__name__}: bias must have 64 elements")
             keep += [wp, b]
             rows += [wp.data_ptr(), 0 if b is None else b.data_ptr(), (int(w16.sw) & 0xffffffff) | ((1 if relu else 0) << 32)]
         self.table = torch.tensor(rows, dtype=torch.int64).to(device)
         self.n_layers, self.keep, self._state = len(layers), keep, {}
 
-    @staticmethod
-    def _weights_class():
-        return Split16Weights
-
     def state(self, n, H, W):
-        """(Sp16, Sp16) ping-pong outputs of a batch of n images (kept: a captured hipGraph carries their addresses)."""
+        """(ACT, ACT) ping-pong outputs of a batch of n images (kept: a captured hipGraph carries their addresses)."""
         st = self._state.get(("out", n, H, W))
         if st is None:
             dev = self.table.device
             for key in [k for k in self._state if k[0] == "out"]:      # one live batch shape at a time (2 x 256 bytes per pixel and image)
                 del self._state[key]
-            st = self._state[("out", n, H, W)] = (self.act.empty(n, H, W, dev), self.act.empty(n, H, W, dev))
+            st = self._state[("out", n, H, W)] = (self.ACT.empty(n, H, W, dev), self.ACT.empty(n, H, W, dev))
         return st
 
     def head_buffer(self, n, H, W):
-        """An Sp16 for the run's INPUT of a slice of n images (the engine runs first layer -> run -> last layer slice by slice, so that each
+        """An ACT for the run's INPUT of a slice of n images (the engine runs first layer -> run -> last layer slice by slice, so that each
         hands its output to the next through the Infinity Cache); kept like the output buffers."""
         hb = self._state.get(("head", n, H, W))
         if hb is None:
             for key in [k for k in self._state if k[0] == "head"]:
                 del self._state[key]
-            hb = self._state[("head", n, H, W)] = self.act.empty(n, H, W, self.table.device)
+            hb = self._state[("head", n, H, W)] = self.ACT.empty(n, H, W, self.table.device)
         return hb
 
     def flags(self, n, H, W):
@@ -962,34 +979,39 @@ def conv3x3_c64_split16_stack(x, stack, ranges=None, events=None, per_launch=Non
     least x.n images to write into instead of the stack's own."""
     if not isinstance(x, Sp16) or not isinstance(stack, Split16Stack) or not x.t.is_contiguous() or x.t.dtype != torch.float16 or not x.t.is_cuda:
         raise DeqsciHipError("conv3x3_c64_split16_stack: a contiguous Sp16 GPU activation and a Split16Stack are required")
+    return _stack_launch("conv3x3_c64_split16_stack", x, stack, ranges, events, per_launch, rng_offset, out_bufs, check)
+
+
+def _stack_launch(what, x, stack, ranges, events, per_launch, rng_offset, out_bufs, check):
+    """conv3x3_c64_split16_stack and conv3x3_c64_wino16_stack once x and the stack's type are checked: the kernel, layout and tile are the
+    stack's."""
     n, H, W = x.n, x.H, x.W
     if x.t.device != stack.table.device:
-        raise DeqsciHipError("conv3x3_c64_split16_stack: the stack was built for another device")
+        raise DeqsciHipError(f"{what}: the stack was built for another device")
     n_total = n if ranges is None or not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 else ranges.shape[1]
     if ranges is not None and (not isinstance(ranges, torch.Tensor) or ranges.dtype != torch.float32 or ranges.dim() != 2
                                or ranges.shape[0] != stack.n_layers + 1 or rng_offset < 0 or rng_offset + n > n_total
                                or not ranges.is_contiguous() or ranges.device != x.t.device):
-        raise DeqsciHipError(f"conv3x3_c64_split16_stack: ranges must be a contiguous fp32 ({stack.n_layers + 1}, >= {rng_offset + n}) tensor on the input's device")
+        raise DeqsciHipError(f"{what}: ranges must be a contiguous fp32 ({stack.n_layers + 1}, >= {rng_offset + n}) tensor on the input's device")
     if (ranges is None) != (x.rng is None):
-        raise DeqsciHipError("conv3x3_c64_split16_stack: the input's range and the run's ranges go together (both measured or both fixed)")
-    per = (split16_stack_per_launch(n, H, W, cus=torch.cuda.get_device_properties(x.t.device).multi_processor_count) if per_launch is None
-           else int(per_launch))
+        raise DeqsciHipError(f"{what}: the input's range and the run's ranges go together (both measured or both fixed)")
+    per = split16_stack_per_launch(n, H, W, cus=_cus(x.t.device), tile=stack.TILE) if per_launch is None else int(per_launch)
     if per <= 0:
-        raise DeqsciHipError("conv3x3_c64_split16_stack: per_launch must be positive")
+        raise DeqsciHipError(f"{what}: per_launch must be positive")
     bufs = stack.state(n, H, W) if out_bufs is None else out_bufs
-    if len(bufs) != 2 or any(not isinstance(b, Sp16) or b.n < n or (b.H, b.W) != (H, W) or not b.t.is_contiguous() or b.t.device != x.t.device for b in bufs):
-        raise DeqsciHipError("conv3x3_c64_split16_stack: out_bufs must be two contiguous Sp16 of the input's H x W with at least its images")
+    if len(bufs) != 2 or any(type(b) is not stack.ACT or b.n < n or (b.H, b.W) != (H, W) or not b.t.is_contiguous() or b.t.device != x.t.device for b in bufs):
+        raise DeqsciHipError(f"{what}: out_bufs must be two contiguous {stack.ACT.__name__} of the input's H x W with at least its images")
+    fn = getattr(load(), stack.ENTRY)
     with _dev(x.t):
         for a in range(0, n, per):
             m = min(per, n - a)
-            ev = _hook_events("s16stack", m, H, W, events, layers=stack.n_layers) or (None, None)
-            _check(load().deqsci_conv3x3_c64_split16_stack(x.t[a:a + m].data_ptr(), bufs[0].t[a:a + m].data_ptr(), bufs[1].t[a:a + m].data_ptr(),
-                                                           stack.table.data_ptr(), stack.n_layers, m, H, W,
-                                                           None if ranges is None else ranges.data_ptr() + 4 * (rng_offset + a), n_total, x.exp, SP16_DEFAULT_EXP,
-                                                           stack.flags(m, H, W).data_ptr(), _stream(), ev[0], ev[1]), "conv3x3_c64_split16_stack")
+            ev = _hook_events(stack.HOOK, m, H, W, events, layers=stack.n_layers) or (None, None)
+            _check(fn(x.t[a:a + m].data_ptr(), bufs[0].t[a:a + m].data_ptr(), bufs[1].t[a:a + m].data_ptr(), stack.table.data_ptr(), stack.n_layers,
+                      m, H, W, None if ranges is None else ranges.data_ptr() + 4 * (rng_offset + a), n_total, x.exp, SP16_DEFAULT_EXP,
+                      stack.flags(m, H, W).data_ptr(), _stream(), ev[0], ev[1]), what)
     out = bufs[(stack.n_layers - 1) % 2]
     if out.n != n:
-        out = Sp16(out.t[:n], n, H, W)
+        out = stack.ACT(out.t[:n], n, H, W)
     out.rng, out.exp = (None if ranges is None else ranges[stack.n_layers][rng_offset:rng_offset + n]), SP16_DEFAULT_EXP
     if check is None:
         check = not torch.cuda.is_current_stream_capturing()
@@ -997,6 +1019,13 @@ def conv3x3_c64_split16_stack(x, stack, ranges=None, events=None, per_launch=Non
         raise DeqsciHipError("a wait inside the stack launch timed out - its workgroups were not all resident (the device's CUs are shared with "
                              "other work): the output of this call is invalid; use one launch per layer")
     return out
+
+
+class Split16Stack(_Stack):
+    """A run of layers of Split16Weights for deqsci_conv3x3_c64_split16_stack (the direct kernel): Sp16 activations."""
+    __slots__ = ()
+    ACT, WEIGHTS, TILE, HOOK, ENTRY = Sp16, Split16Weights, (16, 32), "s16stack", "deqsci_conv3x3_c64_split16_stack"
+    head, launch, tail = staticmethod(ffdnet_head_split16), staticmethod(conv3x3_c64_split16_stack), staticmethod(tail_split16)
 
 
 # ----------------------------------------------------------------------------- split-fp16 Winograd F(2,3) x direct (csrc/conv_w16.hip)
@@ -1098,52 +1127,14 @@ def conv3x3_c64_wino16(x, weights, bias=None, relu=True, out=None, events=None, 
 
 def ffdnet_head_p32(x, weights, sigma, out=None, in_rng=None, in_exp=SP16_DEFAULT_EXP, out_rng=None, out_exp=SP16_DEFAULT_EXP):
     """ffdnet_head_split16 writing a P32 (the input of a run of conv3x3_c64_wino16 layers): same weights, same arithmetic, 2^e y unsplit."""
-    n, c, H2, W2 = x.shape
-    if c != 1 or H2 % 2 or W2 % 2 or not isinstance(weights, HeadSplit16Weights):
-        raise DeqsciHipError(f"ffdnet_head_p32: (n,1,even,even) image and HeadSplit16Weights required, got {tuple(x.shape)}")
-    if sigma.numel() not in (1, n) or sigma.dtype != torch.float32 or not sigma.is_cuda:
-        raise DeqsciHipError("ffdnet_head_p32: sigma must be a fp32 GPU tensor with 1 or n elements")
-    H, W = H2 // 2, W2 // 2
-    o = out if out is not None else P32.empty(n, H, W, x.device)
-    if not isinstance(o, P32) or (o.n, o.H, o.W) != (n, H, W):
-        raise DeqsciHipError("ffdnet_head_p32: out must be a P32 of the output's shape")
-    o.rng, o.exp = out_rng, int(out_exp)
-    wp = weights.packed if weights.packed.device == x.device else weights.packed.to(x.device)
-    with _dev(x):
-        _check(load().deqsci_ffdnet_head_p32(_p(x, "x"), wp.data_ptr(), sigma.data_ptr(), 0 if sigma.numel() == 1 else sigma.stride(0),
-                                             o.t.data_ptr(), n, H, W, weights.sw, _rng(in_rng, n), int(in_exp), _rng(out_rng, n), o.exp,
-                                             _stream()), "ffdnet_head_p32")
-    return o
+    return _ffdnet_head("ffdnet_head_p32", P32, x, weights, sigma, out, in_rng, in_exp, out_rng, out_exp)
 
 
 def ffdnet_tail_p32(h, weights, out=None):
     """tail_split16 reading a P32: COUT = 4 (FFDNet's last layer + pixel shuffle) or 1 (a plain 64 -> 1 layer: SimpleCNN's last);
     `weights` = TailSplit16Weights(w)."""
     _act_check(h, "ffdnet_tail_p32")
-    if not isinstance(weights, TailSplit16Weights) or weights.cout not in (1, 4):
-        raise DeqsciHipError("ffdnet_tail_p32: TailSplit16Weights of a (4,64,3,3) or (1,64,3,3) weight are required")
-    shape = (h.n, 1, 2 * h.H, 2 * h.W) if weights.cout == 4 else (h.n, 1, h.H, h.W)
-    o = out if out is not None else torch.empty(shape, device=h.t.device, dtype=torch.float32)
-    wp = weights.packed if weights.packed.device == h.t.device else weights.packed.to(h.t.device)
-    fn = load().deqsci_ffdnet_tail_p32 if weights.cout == 4 else load().deqsci_conv3x3_c64_to_1_p32
-    with _dev(h.t):
-        _check(fn(h.t.data_ptr(), wp.data_ptr(), _p(o, "out"), h.n, h.H, h.W, weights.sw, _rng(h.rng, h.n), h.exp, _stream()), "tail_p32")
-    return o
-
-
-class Wino16Stack(Split16Stack):
-    """A RUN of 64->64 layers for deqsci_conv3x3_c64_wino16_stack: Split16Stack with Wino16Weights, block tiles of 8 x 64 pixels and P32
-    activations."""
-    __slots__ = ()
-    TILE = (8, 64)
-
-    def __init__(self, layers, device):
-        super().__init__(layers, device)
-        self.act = P32
-
-    @staticmethod
-    def _weights_class():
-        return Wino16Weights
+    return _tail("ffdnet_tail_p32", h, weights, out)
 
 
 def conv3x3_c64_wino16_stack(x, stack, ranges=None, events=None, per_launch=None, rng_offset=0, out_bufs=None, check=None):
@@ -1152,41 +1143,15 @@ def conv3x3_c64_wino16_stack(x, stack, ranges=None, events=None, per_launch=None
     _act_check(x, "conv3x3_c64_wino16_stack")
     if not isinstance(stack, Wino16Stack):
         raise DeqsciHipError("conv3x3_c64_wino16_stack: a Wino16Stack is required")
-    n, H, W = x.n, x.H, x.W
-    if x.t.device != stack.table.device:
-        raise DeqsciHipError("conv3x3_c64_wino16_stack: the stack was built for another device")
-    n_total = n if ranges is None or not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 else ranges.shape[1]
-    if ranges is not None and (not isinstance(ranges, torch.Tensor) or ranges.dtype != torch.float32 or ranges.dim() != 2
-                               or ranges.shape[0] != stack.n_layers + 1 or rng_offset < 0 or rng_offset + n > n_total
-                               or not ranges.is_contiguous() or ranges.device != x.t.device):
-        raise DeqsciHipError(f"conv3x3_c64_wino16_stack: ranges must be a contiguous fp32 ({stack.n_layers + 1}, >= {rng_offset + n}) tensor on the input's device")
-    if (ranges is None) != (x.rng is None):
-        raise DeqsciHipError("conv3x3_c64_wino16_stack: the input's range and the run's ranges go together (both measured or both fixed)")
-    per = (split16_stack_per_launch(n, H, W, cus=torch.cuda.get_device_properties(x.t.device).multi_processor_count, tile=stack.TILE)
-           if per_launch is None else int(per_launch))
-    if per <= 0:
-        raise DeqsciHipError("conv3x3_c64_wino16_stack: per_launch must be positive")
-    bufs = stack.state(n, H, W) if out_bufs is None else out_bufs
-    if len(bufs) != 2 or any(type(b) is not stack.act or b.n < n or (b.H, b.W) != (H, W) or not b.t.is_contiguous() or b.t.device != x.t.device for b in bufs):
-        raise DeqsciHipError("conv3x3_c64_wino16_stack: out_bufs must be two contiguous activations of the input's format and H x W with at least its images")
-    with _dev(x.t):
-        for a in range(0, n, per):
-            m = min(per, n - a)
-            ev = _hook_events("w16stack", m, H, W, events, layers=stack.n_layers) or (None, None)
-            _check(load().deqsci_conv3x3_c64_wino16_stack(x.t[a:a + m].data_ptr(), bufs[0].t[a:a + m].data_ptr(), bufs[1].t[a:a + m].data_ptr(),
-                                                          stack.table.data_ptr(), stack.n_layers, m, H, W,
-                                                          None if ranges is None else ranges.data_ptr() + 4 * (rng_offset + a), n_total, x.exp, SP16_DEFAULT_EXP,
-                                                          stack.flags(m, H, W).data_ptr(), _stream(), ev[0], ev[1]), "conv3x3_c64_wino16_stack")
-    out = bufs[(stack.n_layers - 1) % 2]
-    if out.n != n:
-        out = stack.act(out.t[:n], n, H, W)
-    out.rng, out.exp = (None if ranges is None else ranges[stack.n_layers][rng_offset:rng_offset + n]), SP16_DEFAULT_EXP
-    if check is None:
-        check = not torch.cuda.is_current_stream_capturing()
-    if check and stack.timed_out():                             # (one host sync; DEQSCIEngine passes check=False and looks once per reconstruction)
-        raise DeqsciHipError("a wait inside the stack launch timed out - its workgroups were not all resident (the device's CUs are shared with "
-                             "other work): the output of this call is invalid; use one launch per layer")
-    return out
+    return _stack_launch("conv3x3_c64_wino16_stack", x, stack, ranges, events, per_launch, rng_offset, out_bufs, check)
+
+
+class Wino16Stack(_Stack):
+    """A run of layers of Wino16Weights for deqsci_conv3x3_c64_wino16_stack (the Winograd kernel): P32 activations, block tiles of 8 x 64
+    pixels."""
+    __slots__ = ()
+    ACT, WEIGHTS, TILE, HOOK, ENTRY = P32, Wino16Weights, (8, 64), "w16stack", "deqsci_conv3x3_c64_wino16_stack"
+    head, launch, tail = staticmethod(ffdnet_head_p32), staticmethod(conv3x3_c64_wino16_stack), staticmethod(ffdnet_tail_p32)
 
 
 class Conv64Weights:

@@ -142,8 +142,8 @@ class _Denoiser:
         self._wkey = key
         self.fast = None
         self.wino = None
-        self.tail_w = self.head_w = None
-        self.plain_head_w = self.plain_tail_w = None
+        self.tail_w = self.head_w = self.tail_w16 = self.head_w16 = None
+        self.plain_head_w = self.plain_tail_w = self.plain_tail_w16 = None
         from .networks import DnCNN
         from .networks.simplecnn import RealSNConv2d
         seq = None
@@ -181,10 +181,6 @@ class _Denoiser:
             self.ranges = None
             self._stacks = {}
             self._wstacks = {}
-
-            self.tail_w = self.head_w = None
-            self.plain_head_w = self.plain_tail_w = None
-            self.tail_w16 = self.plain_tail_w16 = self.head_w16 = None
             if (not isinstance(net, FFDNet) and self.fused_edges and self.channels_last and layers[0][0].is_cuda):
                 # SimpleCNN-style stacks: 1 -> 64 (+ReLU) and 64 -> 1 edge layers as HIP stencils (csrc/ffdnet_edges.hip)
                 if tuple(layers[0][0].shape) == (64, 1, 3, 3) and layers[0][1] is None:
@@ -232,18 +228,14 @@ class _Denoiser:
     # overlap from memory instead of the L2, and there is no kernel boundary worth saving between two 100 us launches)
     STACK_MIN_LAYERS = 3
 
-    def _stack_for(self, idx, device):
-        """The Split16Stack of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a hipGraph capture)."""
-        st = self._stacks.get(idx[0])
+    def _stack_for(self, idx, device, w16=False):
+        """The Split16Stack (w16: Wino16Stack) of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a
+        hipGraph capture)."""
+        stacks = self._wstacks if w16 else self._stacks
+        st = stacks.get(idx[0])
         if st is None or st.n_layers != len(idx) or st.table.device != torch.device(device):
-            st = self._stacks[idx[0]] = _hip.Split16Stack([(self.wino[i].s16, self.fast[i][1], self.fast[i][2]) for i in idx], device)
-        return st
-
-    def _wstack_for(self, idx, device):
-        """The Wino16Stack of the run of layers idx (built by prepare(), never inside a hipGraph capture)."""
-        st = self._wstacks.get(idx[0])
-        if st is None or st.n_layers != len(idx) or st.table.device != torch.device(device):
-            st = self._wstacks[idx[0]] = _hip.Wino16Stack([(self.wino[i].w16, self.fast[i][1], self.fast[i][2]) for i in idx], device)
+            st = stacks[idx[0]] = (_hip.Wino16Stack if w16 else _hip.Split16Stack)(
+                [(self.wino[i].w16 if w16 else self.wino[i].s16, self.fast[i][1], self.fast[i][2]) for i in idx], device)
         return st
 
     def _middle_run(self):
@@ -253,20 +245,54 @@ class _Denoiser:
         idx = list(range(1, len(self.fast) - 1))
         return idx if all(self.wino[i] is not None for i in idx) else None
 
+    def _has_stack(self, stacks, idx):
+        """Whether `stacks` (_stacks or _wstacks) holds a stack built for exactly the run of layers idx."""
+        return idx is not None and idx[0] in stacks and stacks[idx[0]].n_layers == len(idx)
+
+    def _route(self, n, H, W, device, policy, cal):
+        """The path (_run_gen) of an f-call on n images of H x W under the conv64 `policy`, calibrating (cal) or not, from the attributes as
+        they are NOW: tests and tools set them between calls, and the engine turns `stack` off and `per_layer_w16` on behind a time-out."""
+        if self.fast is None or self.tag not in ("ffdnet", "denoiser"):
+            return "module"
+        cuda = torch.device(device).type == "cuda"
+        packed = all(u is not None for u in self.wino[1:-1])
+        if self.tag == "ffdnet":
+            # a run of 64->64 layers on the split-fp16 kernel: the head writes its sp16 layout, the tail reads it - no conversion pass
+            sp = (cuda and self.head_w is not None and self.tail_w is not None and packed
+                  and _hip.conv64_kernel_for(n, H // 2, W // 2, device, policy) == "s16")
+            run = self._middle_run()
+            if (sp and not cal and self.stack and self.slice_edges and run is not None and len(run) >= self.STACK_MIN_LAYERS
+                    and self._has_stack(self._stacks, run)):
+                return "w16 stack launch" if self.stack_kernel == "w16" and self._has_stack(self._wstacks, run) else "s16 stack launch"
+            if (sp and not cal and not self.stack and self.per_layer_w16 and self.stack_kernel == "w16" and self.ranges is not None
+                    and self._has_stack(self._wstacks, run)):
+                return "w16 per layer"
+            return "sp16 per layer" if sp else "per layer"
+        if not (cuda and (self.plain_head_w is not None or self.plain_tail_w is not None)):
+            return "layers"
+        sp = (self.plain_head_w is not None and self.plain_tail_w is not None and packed
+              and _hip.conv64_kernel_for(n, H, W, device, policy) == "s16")
+        if sp and not cal and self.stack_kernel == "w16" and self.conv64 != "s16" and self.ranges is not None:
+            # the 64->64 layers on the split-fp16 Winograd kernel (csrc/conv_w16.hip: a third fewer matrix-core products), one launch per
+            # layer (two layers: no run worth a stack launch), p32 activations from the first layer to the last; the ranges are the ones
+            # the first f-call measured on the direct kernels.  conv64="s16" means the direct kernel (ADVICE r5).  (A long DnCNN-style run
+            # - a user plugin; test_plugin_stack_dncnn17_follows_the_data_scale - takes this path too: per-layer Winograd launches, a third
+            # fewer matrix-core products than its one direct stack launch.)
+            return "w16 per layer"
+        return "sp16 per layer" if sp else "per layer"
+
+    def _slicing(self, path, run, n, H, W, device):
+        """(stack, images per stack launch) of an f-call on a "... stack launch" path, n images of H x W at the 64->64 layers."""
+        st = (self._wstacks if path == "w16 stack launch" else self._stacks)[run[0]]
+        return st, self.stack_per_launch or _hip.split16_stack_per_launch(n, H, W, cus=_hip._cus(device), tile=st.TILE)
+
     def stack_slice(self, bsz, B, H, W, device):
-        """Images per stack launch when an f-call of this shape goes slice by slice - first layer -> the run of 64->64 layers as ONE stack
-        launch -> last layer (the branch of _run below; a calibrating call aside) - else None.  prepare() must have run."""
-        if self.tag != "ffdnet" or self.fast is None or self.head_w is None or self.tail_w is None or torch.device(device).type != "cuda":
+        """Images per stack launch when an f-call of this shape takes a stack launch path under the engine's policy (a calibrating call
+        and the first conv64_f22_calls f-calls aside) - else None.  prepare() must have run."""
+        path = self._route(bsz * B, H, W, device, self.conv64, False)
+        if path not in ("w16 stack launch", "s16 stack launch"):
             return None
-        run = self._middle_run()
-        if (not self.stack or not self.slice_edges or run is None or len(run) < self.STACK_MIN_LAYERS or run[0] not in self._stacks
-                or self._stacks[run[0]].n_layers != len(run) or not all(u is not None for u in self.wino[1:-1])
-                or _hip.conv64_kernel_for(bsz * B, H // 2, W // 2, device, self.conv64) != "s16"):
-            return None
-        w16 = self.stack_kernel == "w16" and run[0] in self._wstacks and self._wstacks[run[0]].n_layers == len(run)
-        st = self._wstacks[run[0]] if w16 else self._stacks[run[0]]
-        return self.stack_per_launch or _hip.split16_stack_per_launch(bsz * B, H // 2, W // 2,
-                                                                      cus=torch.cuda.get_device_properties(device).multi_processor_count, tile=st.TILE)
+        return self._slicing(path, self._middle_run(), bsz * B, H // 2, W // 2, device)[1]
 
     def stack_timed_out(self):
         """(host sync) whether a wait inside a stack launch gave up since the last call: its results are invalid."""
@@ -274,7 +300,7 @@ class _Denoiser:
 
     def _run_layers(self, h, idx, fused):
         if (self.stack and isinstance(h, _hip.Sp16) and len(idx) >= self.STACK_MIN_LAYERS and self._native_out and not self._calibrating
-                and idx[0] in self._stacks and self._stacks[idx[0]].n_layers == len(idx) and (h.rng is None) == (self.ranges is None)):
+                and self._has_stack(self._stacks, idx) and (h.rng is None) == (self.ranges is None)):
             # the whole run in one launch (per slice of the batch): sp16 in, sp16 out, ranges of the run = slots idx[0] .. idx[-1] + 1
             self.stack_launches += 1
             return _hip.conv3x3_c64_split16_stack(h, self._stack_for(idx, h.t.device), None if self.ranges is None else self.ranges[idx[0]:idx[-1] + 2],
@@ -333,7 +359,7 @@ class _Denoiser:
         if run is not None and len(run) >= self.STACK_MIN_LAYERS and self.wino[run[0]].s16.packed.is_cuda:
             self._stack_for(run, device)
             if self.stack_kernel == "w16" and self.tag == "ffdnet" and self.head_w16 is not None and self.tail_w16 is not None:
-                self._wstack_for(run, device)
+                self._stack_for(run, device, w16=True)
         if self.tag == "ffdnet":
             t = self.sigma_table
             if t is None or t.numel() < n_calls or t.device != torch.device(device):
@@ -367,125 +393,107 @@ class _Denoiser:
             self._calibrating = False
 
     def _run_gen(self, z1, x, call, cal):
-        """(generator) the f-call's denoiser; yields "stack" behind every stack launch - where a grouped reconstruction switches to its other
-        half (DEQSCIEngine._reconstruct_grouped) - and returns (output, is_noise)."""
+        """(generator) the f-call's denoiser on the path _route picks; yields "stack" behind every stack launch when a gate is set - where
+        a grouped reconstruction switches to its other half (DEQSCIEngine._reconstruct_grouped) - and returns (output, is_noise)."""
         bsz, B, H, W = z1.shape
+        path = self._route(bsz * B, H, W, x.device, self._policy, cal)
         if self.tag == "ffdnet":
-            sig = self.sigma_table[call:call + 1].expand(bsz * B)
-            if self.fast is not None:
-                # a run of 64->64 layers on the split-fp16 kernel: the head writes its sp16 layout, the tail reads it - no conversion pass
-                sp = (x.is_cuda and self.head_w is not None and self.tail_w is not None and all(u is not None for u in self.wino[1:-1])
-                      and _hip.conv64_kernel_for(bsz * B, H // 2, W // 2, x.device, self._policy) == "s16")
-                run = self._middle_run()
-                if (sp and not cal and self.stack and self.slice_edges and run is not None and len(run) >= self.STACK_MIN_LAYERS
-                        and run[0] in self._stacks and self._stacks[run[0]].n_layers == len(run)):
-                    # slice by slice: first layer -> the run of 64->64 layers as one stack launch -> last layer, each handing its output to the
-                    # next through the Infinity Cache (a slice's activation is at most 128 MiB: _hip.split16_stack_per_launch)
-                    n, sg = bsz * B, self.sigma_table[call:call + 1]
-                    w16 = self.stack_kernel == "w16" and run[0] in self._wstacks and self._wstacks[run[0]].n_layers == len(run)
-                    st = self._wstacks[run[0]] if w16 else self._stacks[run[0]]
-                    per = self.stack_per_launch or _hip.split16_stack_per_launch(n, H // 2, W // 2,
-                                                                                  cus=torch.cuda.get_device_properties(x.device).multi_processor_count,
-                                                                                  tile=st.TILE)
-                    bufs, hbuf = st.state(min(per, n), H // 2, W // 2), st.head_buffer(min(per, n), H // 2, W // 2)
-                    rows = None if self.ranges is None else self.ranges[run[0]:run[-1] + 2]
-                    out = torch.empty((n, 1, H, W), dtype=torch.float32, device=x.device)
-                    for a in range(0, n, per):
-                        m = min(per, n - a)
-                        hin = hbuf if m == hbuf.n else st.act(hbuf.t[:m], m, hbuf.H, hbuf.W)
-                        in_rng = None if self.ranges is None else self._slot(0)[a:a + m]
-                        out_rng = None if self.ranges is None else self._slot(1)[a:a + m]
-                        if w16:
-                            hs = _hip.ffdnet_head_p32(x[a:a + m], self.head_w16, sg, out=hin, in_rng=in_rng, out_rng=out_rng)
-                            if self.gate is not None:
-                                self.gate.acquire()
-                            ys = _hip.conv3x3_c64_wino16_stack(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
-                            if self.gate is not None:
-                                self.gate.release()
-                                yield "stack"
-                            _hip.ffdnet_tail_p32(ys, self.tail_w16, out=out[a:a + m])
-                        else:
-                            hs = _hip.ffdnet_head_split16(x[a:a + m], self.head_w16, sg, out=hin, in_rng=in_rng, out_rng=out_rng)
-                            if self.gate is not None:
-                                self.gate.acquire()
-                            ys = _hip.conv3x3_c64_split16_stack(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
-                            if self.gate is not None:
-                                self.gate.release()
-                                yield "stack"
-                            _hip.tail_split16(ys, self.tail_w16, out=out[a:a + m])
-                    self.stack_launches += 1
-                    self.last_path = ("w16" if w16 else "s16") + " stack launch"
-                    return out.reshape(bsz, B, H, W), True
-                if (sp and not cal and not self.stack and self.per_layer_w16 and self.stack_kernel == "w16" and self.ranges is not None
-                        and run is not None and self.head_w16 is not None and self.tail_w16 is not None and run[0] in self._wstacks):
-                    # behind a stack time-out: the same kernel, the same ranges, one launch per layer - the stack launch's bits
-                    sg = self.sigma_table[call:call + 1]
-                    h = _hip.ffdnet_head_p32(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1))
-                    for i in run:
-                        h = _hip.conv3x3_c64_wino16(h, self.wino[i].w16, self.fast[i][1], self.fast[i][2], out_rng=self._slot(i + 1))
-                    self.last_path = "w16 per layer (behind a stack time-out)"
-                    return _hip.ffdnet_tail_p32(h, self.tail_w16).reshape(bsz, B, H, W), True
-                self.last_path = "per layer"
-                if self.head_w is not None and x.is_cuda:
-                    sg = self.sigma_table[call:call + 1]
-                    if sp:
-                        if cal:                                # max |image| (the head adds sigma itself), then max |its own output|
-                            self._measured = True
-                            _hip.absmax(x, self._slot(0))
-                            _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_exp=0, track=self._slot(1))
-                        h = _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1))
-                    else:
-                        h = _hip.ffdnet_head(x, self.head_w, sg)
-                    first_done = True
-                else:
-                    h = torch.cat((sig.view(-1, 1, 1, 1).expand(bsz * B, 1, H // 2, W // 2), F.pixel_unshuffle(x, 2)), 1)
-                    first_done = False
-                if self.tail_w is not None and h.is_cuda:
-                    defer = self.fused_epilogue and self.fast[-2][1] is not None and self.fast[-2][2]
-                    if defer:
-                        raw, b = self._run_stack(h, skip_last=True, skip_first=first_done, defer_last_epilogue=True, native_out=sp)
-                    else:
-                        raw, b = self._run_stack(h, skip_last=True, skip_first=first_done, native_out=sp), None
-                    out = _hip.tail_split16(raw, self.tail_w16) if isinstance(raw, _hip.Sp16) else _hip.ffdnet_tail(raw, self.tail_w, in_bias=b)
-                else:
-                    out = F.pixel_shuffle(self._run_stack(h, skip_first=first_done), 2)
+            sg = self.sigma_table[call:call + 1]
+            if path == "module":
+                out = self.net(x, sg.expand(bsz * B))
+            elif path in ("w16 stack launch", "s16 stack launch"):
+                out = yield from self._ffdnet_slices(x, sg, path)
+                self.last_path = path
+            elif path == "w16 per layer":
+                # behind a stack time-out: the same kernel, the same ranges, one launch per layer - the stack launch's bits
+                out = self._w16_per_layer(_hip.ffdnet_head_p32(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1)), self.tail_w16)
+                self.last_path = "w16 per layer (behind a stack time-out)"
             else:
-                out = self.net(x, sig)
+                self.last_path = "per layer"
+                out = self._ffdnet_per_layer(x, sg, cal, path == "sp16 per layer")
             return out.reshape(bsz, B, H, W), True
         if self.tag == "denoiser":
-            if self.fast is not None:
-                if x.is_cuda and (self.plain_head_w is not None or self.plain_tail_w is not None):
-                    first = self.plain_head_w is not None
-                    sp = (first and self.plain_tail_w is not None and all(u is not None for u in self.wino[1:-1])
-                          and _hip.conv64_kernel_for(bsz * B, H, W, x.device, self._policy) == "s16")
-                    if first and sp and cal:
-                        self._measured = True
-                        _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=True, out_exp=0, track=self._slot(1))
-                    if (first and sp and not cal and self.stack_kernel == "w16" and self.plain_tail_w16 is not None and self.conv64 != "s16"
-                            and all(u is not None for u in self.wino[1:-1]) and self.ranges is not None):
-                        # the 64->64 layers on the split-fp16 Winograd kernel (csrc/conv_w16.hip: a third fewer matrix-core products), one
-                        # launch per layer (two layers: no run worth a stack launch), p32 activations from the first layer to the last; the
-                        # ranges are the ones the first f-call measured on the direct kernels below.  conv64="s16" means the direct kernel
-                        # (ADVICE r5).  (A long DnCNN-style run - a user plugin; test_plugin_stack_dncnn17_follows_the_data_scale - takes this
-                        # branch too: per-layer Winograd launches, a third fewer matrix-core products than its one direct stack launch.)
-                        h = _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], p32=True, out_rng=self._slot(1))
-                        for i in range(1, len(self.fast) - 1):
-                            h = _hip.conv3x3_c64_wino16(h, self.wino[i].w16, self.fast[i][1], self.fast[i][2], out_rng=self._slot(i + 1))
-                        return _hip.ffdnet_tail_p32(h, self.plain_tail_w16).reshape(bsz, B, H, W), True
-                    h = _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=sp, out_rng=self._slot(1) if sp else None) if first else x
-                    if self.plain_tail_w is not None:
-                        h = self._run_stack(h, skip_first=first, skip_last=True, native_out=sp)
-                        out = (_hip.tail_split16(h, self.plain_tail_w16) if isinstance(h, _hip.Sp16) else
-                               _hip.conv3x3_c64_to_1(h.contiguous(memory_format=torch.channels_last), self.plain_tail_w))
-                    else:
-                        out = self._run_stack(h, skip_first=first)
-                    return out.reshape(bsz, B, H, W), True
-                return self._run_stack(x).reshape(bsz, B, H, W), True
-            return self.net(x).reshape(bsz, B, H, W), True
+            if path == "module":
+                out = self.net(x)
+            elif path == "layers":
+                out = self._run_stack(x)
+            elif path == "w16 per layer":
+                out = self._w16_per_layer(_hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], p32=True, out_rng=self._slot(1)),
+                                          self.plain_tail_w16)
+            else:
+                out = self._plain_per_layer(x, cal, path == "sp16 per layer")
+            return out.reshape(bsz, B, H, W), True
         if self.tag == "conv2d":
             return self.net(x).reshape(bsz, B, H, W), False
         x5 = z1.view(bsz, 1, B, H, W)
         return self.net(x5).reshape(bsz, B, H, W), self.tag == "3d_denoiser"
+
+    def _ffdnet_slices(self, x, sg, path):
+        """(generator) FFDNet slice by slice on the kernels of the path's stack: first layer -> the run of 64->64 layers as one stack launch
+        -> last layer, each handing its output to the next through the Infinity Cache (a slice's activation is at most 128 MiB)."""
+        n, H, W = x.shape[0], x.shape[2] // 2, x.shape[3] // 2
+        run = self._middle_run()
+        st, per = self._slicing(path, run, n, H, W, x.device)
+        bufs, hbuf = st.state(min(per, n), H, W), st.head_buffer(min(per, n), H, W)
+        rows = None if self.ranges is None else self.ranges[run[0]:run[-1] + 2]
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        for a in range(0, n, per):
+            m = min(per, n - a)
+            hin = hbuf if m == hbuf.n else st.ACT(hbuf.t[:m], m, H, W)
+            in_rng = None if self.ranges is None else self._slot(0)[a:a + m]
+            out_rng = None if self.ranges is None else self._slot(1)[a:a + m]
+            hs = st.head(x[a:a + m], self.head_w16, sg, out=hin, in_rng=in_rng, out_rng=out_rng)
+            if self.gate is not None:
+                self.gate.acquire()
+            ys = st.launch(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
+            if self.gate is not None:
+                self.gate.release()
+                yield "stack"
+            st.tail(ys, self.tail_w16, out=out[a:a + m])
+        self.stack_launches += 1
+        return out
+
+    def _w16_per_layer(self, h, tail_w16):
+        """From the first layer's P32 output h: the 64->64 layers as one launch per layer of the Winograd split-fp16 kernel, the last layer."""
+        for i in range(1, len(self.fast) - 1):
+            h = _hip.conv3x3_c64_wino16(h, self.wino[i].w16, self.fast[i][1], self.fast[i][2], out_rng=self._slot(i + 1))
+        return _hip.ffdnet_tail_p32(h, tail_w16)
+
+    def _ffdnet_per_layer(self, x, sg, cal, sp):
+        """FFDNet layer by layer.  sp: the first layer writes sp16 and the last reads it (a calibrating call measures their ranges first)."""
+        n, _, H, W = x.shape
+        if self.head_w is not None and x.is_cuda:
+            if sp:
+                if cal:                                # max |image| (the head adds sigma itself), then max |its own output|
+                    self._measured = True
+                    _hip.absmax(x, self._slot(0))
+                    _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_exp=0, track=self._slot(1))
+                h = _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1))
+            else:
+                h = _hip.ffdnet_head(x, self.head_w, sg)
+            first_done = True
+        else:
+            h = torch.cat((sg.expand(n).view(-1, 1, 1, 1).expand(n, 1, H // 2, W // 2), F.pixel_unshuffle(x, 2)), 1)
+            first_done = False
+        if self.tail_w is not None and h.is_cuda:
+            defer = self.fused_epilogue and self.fast[-2][1] is not None and self.fast[-2][2]
+            raw = self._run_stack(h, skip_last=True, skip_first=first_done, defer_last_epilogue=defer, native_out=sp)
+            raw, b = raw if defer else (raw, None)
+            return _hip.tail_split16(raw, self.tail_w16) if isinstance(raw, _hip.Sp16) else _hip.ffdnet_tail(raw, self.tail_w, in_bias=b)
+        return F.pixel_shuffle(self._run_stack(h, skip_first=first_done), 2)
+
+    def _plain_per_layer(self, x, cal, sp):
+        """SimpleCNN / DnCNN with HIP edge layers, layer by layer.  sp: as for _ffdnet_per_layer."""
+        first = self.plain_head_w is not None
+        if sp and cal:
+            self._measured = True
+            _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=True, out_exp=0, track=self._slot(1))
+        h = _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=sp, out_rng=self._slot(1) if sp else None) if first else x
+        if self.plain_tail_w is not None:
+            h = self._run_stack(h, skip_first=first, skip_last=True, native_out=sp)
+            return (_hip.tail_split16(h, self.plain_tail_w16) if isinstance(h, _hip.Sp16) else
+                    _hip.conv3x3_c64_to_1(h.contiguous(memory_format=torch.channels_last), self.plain_tail_w))
+        return self._run_stack(h, skip_first=first)
 
 
 class _StackTimeout(Exception):
@@ -605,15 +613,15 @@ class DEQSCIEngine:
         return ws
 
     # ------------------------------------------------------------------ one f-call = GAP -> denoise -> store -> solve
-    def _store_solve(self, ws, x_in, call, slot, n_filled, n_solve, x_next, eps, res_row):
-        return _exhaust(self._store_solve_steps(ws, x_in, call, slot, n_filled, n_solve, x_next, eps, res_row))
+    def _denoise_steps(self, z1, call, calibrate=False):
+        """(generator) den.run_steps where a gate is set (a half of a grouped reconstruction: it yields behind every stack launch), else
+        den.run - which tests and tools wrap to see every f-call."""
+        if self.den.gate is not None:
+            return (yield from self.den.run_steps(z1, call, calibrate=calibrate))
+        return self.den.run(z1, call, calibrate=calibrate)
 
     def _store_solve_steps(self, ws, x_in, call, slot, n_filled, n_solve, x_next, eps, res_row):
-        # (the first f-call measures the activations' ranges; only a half of a grouped reconstruction - a gate is set - needs the generator form)
-        if self.den.gate is not None:
-            out, is_noise = yield from self.den.run_steps(ws.z1, call, calibrate=(call == 0))
-        else:
-            out, is_noise = self.den.run(ws.z1, call, calibrate=(call == 0))
+        out, is_noise = yield from self._denoise_steps(ws.z1, call, calibrate=(call == 0))     # (the first f-call measures the activations' ranges)
         if call == 1 and self._eager and self._early_check and self.den.stack and self.den.stack_launches and self.den.stack_timed_out():
             # the FIRST stack launch of the reconstruction: a wait that gave up (its workgroups were not all resident: somebody else holds CUs)
             # is seen here, one f-call in - not after 180 f-calls on invalid data.  One host sync per reconstruction (~0.1 ms of queue refill).
@@ -868,12 +876,7 @@ class DEQSCIEngine:
     def _enqueue(self, ws, y, Phi4, Phi_sum, initial_point, poll):
         """Every launch of one reconstruction on the current stream.  poll: True = lagged residual read-back with early stop,
         False = one read-back at the end, None = no host traffic at all (what a hipGraph capture records)."""
-        steps = self._enqueue_steps(ws, y, Phi4, Phi_sum, initial_point, poll)
-        while True:
-            try:
-                next(steps)
-            except StopIteration as done:
-                return done.value
+        return _exhaust(self._enqueue_steps(ws, y, Phi4, Phi_sum, initial_point, poll))
 
     def _enqueue_steps(self, ws, y, Phi4, Phi_sum, initial_point, poll):
         """_enqueue as a generator that yields behind every f-call (a grouped reconstruction issues the f-calls of its halves alternately);
@@ -892,10 +895,7 @@ class DEQSCIEngine:
         res_row = last
         # z = f(z*)  (new_equilibrium_utils_yaping.py:268)
         _hip.gap_update(x_last, phi, y, ps, LAYOUT_BHW, out=ws.z1)
-        if self.den.gate is not None:
-            out, is_noise = yield from self.den.run_steps(ws.z1, call)
-        else:
-            out, is_noise = self.den.run(ws.z1, call)
+        out, is_noise = yield from self._denoise_steps(ws.z1, call)
         out = _hip.f32c(out)
         rec = _hip.residual_out(ws.z1, out, LAYOUT_HWB) if is_noise else _hip.transpose(out, LAYOUT_HWB)
         call += 1
@@ -903,10 +903,7 @@ class DEQSCIEngine:
             yield "fcall"
             zt = _hip.transpose(rec, LAYOUT_BHW)
             _hip.gap_update(zt, phi, y, ps, LAYOUT_BHW, out=ws.z1)
-            if self.den.gate is not None:
-                yield from self.den.run_steps(ws.z1, call)
-            else:
-                self.den.run(ws.z1, call)
+            yield from self._denoise_steps(ws.z1, call)
             call += 1
         return rec, call, last, res_row
 

@@ -354,6 +354,55 @@ def test_conv64_policy_resolution():
         _hip._CUS.pop(0, None)
 
 
+def test_denoiser_route_table(monkeypatch):
+    """_Denoiser._route, the one decision of an f-call's path, pinned as a table: kind = the kernel the conv64 policy picks at the 64->64
+    layers' resolution (half the image's for FFDNet), then the tag, which edge weights and stacks exist, whether the call calibrates, and
+    the knobs.  stack_slice asks the same question under the engine's policy, not the call's."""
+    from types import SimpleNamespace
+    from deqsci_amd.engine import _Denoiser
+    asked = []
+
+    def route(tag="ffdnet", kind="s16", cal=False, device="cuda", edges=("head", "tail"), stacks=("s16", "w16"), packed=True, **knobs):
+        n_layers = 15 if tag == "ffdnet" else 4                     # FFDNet: a 13-layer run; SimpleCNN: 2
+        den = object.__new__(_Denoiser)
+        den.tag, den.fast = tag, [None] * n_layers
+        den.wino = [None] + [object() if packed else None] * (n_layers - 2) + [None]
+        den.head_w = den.plain_head_w = object() if "head" in edges else None
+        den.tail_w = den.plain_tail_w = object() if "tail" in edges else None
+        den._stacks = {1: SimpleNamespace(n_layers=n_layers - 2)} if "s16" in stacks else {}
+        den._wstacks = {1: SimpleNamespace(n_layers=n_layers - 2)} if "w16" in stacks else {}
+        den.ranges = object()
+        den.conv64, den.stack, den.slice_edges, den.stack_kernel, den.per_layer_w16 = "fast", True, True, "w16", False
+        for k, v in knobs.items():
+            setattr(den, k, v)
+        monkeypatch.setattr(_hip, "conv64_kernel_for", lambda n, H, W, device, policy: asked.append((n, H, W, policy)) or kind)
+        return den, den._route(16, 256, 256, device, "fast", cal)
+
+    ffdnet = lambda **kw: route(**kw)[1]                            # noqa: E731
+    assert ffdnet() == "w16 stack launch" and asked[-1] == (16, 128, 128, "fast")
+    assert ffdnet(stack_kernel="s16") == ffdnet(stacks=("s16",)) == "s16 stack launch"
+    assert ffdnet(stacks=("w16",)) == ffdnet(slice_edges=False) == ffdnet(cal=True) == ffdnet(STACK_MIN_LAYERS=14) == "sp16 per layer"
+    assert ffdnet(stack=False) == ffdnet(stack=False, per_layer_w16=True, cal=True) == "sp16 per layer"
+    assert ffdnet(stack=False, per_layer_w16=True) == "w16 per layer"
+    assert ffdnet(stack=False, per_layer_w16=True, stack_kernel="s16") == ffdnet(stack=False, per_layer_w16=True, ranges=None) == "sp16 per layer"
+    assert ffdnet(stack=False, per_layer_w16=True, stacks=("s16",)) == "sp16 per layer"
+    assert ffdnet(conv64="fast32") == "sp16 per layer"                # (no run for the stack launch under an fp32 policy)
+    assert ffdnet(kind="f22") == ffdnet(kind="f44") == ffdnet(edges=("head",)) == ffdnet(device="cpu") == ffdnet(packed=False) == "per layer"
+    assert ffdnet(fast=None) == "module"
+    plain = lambda **kw: route(tag="denoiser", stacks=(), **kw)[1]  # noqa: E731
+    assert plain() == "w16 per layer" and asked[-1] == (16, 256, 256, "fast")
+    assert plain(conv64="s16") == plain(stack_kernel="s16") == plain(cal=True) == plain(ranges=None) == "sp16 per layer"
+    assert plain(kind="f22") == plain(edges=("head",)) == plain(edges=("tail",)) == plain(packed=False) == "per layer"
+    assert plain(edges=()) == plain(device="cpu") == "layers"
+    assert plain(fast=None) == "module"
+    for tag in ("conv2d", "conv3d", "3d_denoiser"):
+        assert route(tag=tag, fast=None)[1] == "module"
+    den, _ = route(stack_per_launch=8, _policy="f22")
+    assert den.stack_slice(2, 8, 256, 256, "cuda") == 8 and asked[-1] == (16, 128, 128, "fast")
+    assert route(slice_edges=False)[0].stack_slice(2, 8, 256, 256, "cuda") is None
+    assert route(kind="f22")[0].stack_slice(2, 8, 256, 256, "cuda") is None
+
+
 def test_split16_weight_pack_layout():
     """Split16Weights: hi + lo == 2^sw w to 2^-22, max |2^sw w| in [2^13, 2^14), and the LDS order of csrc/conv_s16.hip
     [chunk][tap][piece][cout group][lane][j] with cout = 32 g + lane % 32, cin = 16 c + 8 (lane // 32) + j."""
