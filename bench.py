@@ -3,14 +3,18 @@
 180 DEQ (Anderson) iterations, FFDNet denoiser, plus the MFMA roofline of the dominant kernel (the
 denoiser's 64->64 layers: split-fp16 arithmetic on the f16 matrix cores under Winograd F(2,3) along x nested in the direct sum along y - as
 the STACK launch, one launch of deqsci::w16::conv_w16_kernel<1> per 13 layers and slice of 32 images, csrc/conv_w16.hip; --stack-kernel s16:
-round 4's direct form, deqsci::s16::conv_s16_kernel<0, 0, 1>; --no-stack: one launch per layer), the HBM roofline of the fused
-Phi/Phi^T + GAP-update kernel, a parity spot check of the very configuration that is timed against the CPU oracle, the other
-configurations a reader asks about (one measurement per call, the shipped clips of BASELINE config 2 with their PSNR, the fp32-only policy,
-the exact-Gram arithmetic, one stream instead of two: `summary`, the LAST key of the line), and the reference algorithm timed on the host CPU.
+round 4's direct form, deqsci::s16::conv_s16_kernel<0, 0, 1>; --no-stack: one launch per layer) and the HBM roofline of the fused
+Phi/Phi^T + GAP-update kernel, both from HIP events on the launches of the timed steps themselves.
+
+With --full (N = 1 only), after the headline: the same kernels alone on a working set beyond the Infinity Cache, a parity spot check of
+the very configuration that is timed against the CPU oracle, the other configurations a reader asks about (one measurement per call, the
+shipped clips of BASELINE config 2 with their PSNR, the fp32-only policy, the exact-Gram arithmetic, one stream instead of two: `summary`,
+the LAST key of the line), and the reference algorithm timed on the host CPU.  A plain run does only what the headline needs.
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts N rank processes itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                 # also writes the last timed step's reconstruction to DIR/*.npy
+    python bench.py --gpus 1 --full                        # the headline, then everything else the line can carry
 
 One "step" = one full reconstruction pass (x0 = Phi^T y, max_iter+1 f-calls, final all-gather) over
 one synthetic batch of `--batch-per-gpu` measurements per GPU (SURVEY 8(d) C3 recipe: Bernoulli(0.5)
@@ -231,16 +235,21 @@ def parse_args(argv=None):
                     help="kernel of the 64->64 layers (DEQSCIEngine): auto = fast = split-fp16 direct convolution on the f16 matrix cores "
                          "where it is faster, Winograd F(2x2,3x3) below; fast32 = fp32 MFMA arithmetic only (F(4x4,3x3) / F(2x2,3x3))")
     ap.add_argument("--conv64-f22-calls", type=int, default=None, help="run the first K f-calls on F(2x2,3x3) whatever the policy")
-    ap.add_argument("--no-other-kernel", action="store_true", help="skip the extra steps under the other conv64 policies")
-    ap.add_argument("--other-steps", type=int, default=5, help="timed steps per other conv64 policy (behind one warm-up step)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also run what it does not need - the other conv64 policies, the other configurations, the "
+                         "streaming kernels alone (hbm_stream_roofline), the oracle spot check and the CPU baseline (each can be skipped by its "
+                         "--no-* option)")
+    ap.add_argument("--no-other-kernel", action="store_true", help="--full: skip the extra steps under the other conv64 policies")
+    ap.add_argument("--other-steps", type=int, default=5, help="--full: timed steps per other conv64 policy (behind one warm-up step)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short runs of the other BASELINE configurations and variants (reference f-call count, the other stack kernel, the "
-                         "reference's Anderson arithmetic, SimpleCNN, 512x512x16)")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle spot check of the timed configuration (2 measurements, 10 iterations)")
+                    help="--full: skip the short runs of the other BASELINE configurations and variants (reference f-call count, the other stack "
+                         "kernel, the reference's Anderson arithmetic, SimpleCNN, 512x512x16)")
+    ap.add_argument("--no-parity-check", action="store_true",
+                    help="--full: skip the oracle spot check of the timed configuration (2 measurements, 10 iterations)")
     ap.add_argument("--iters", type=int, default=180)
     ap.add_argument("--denoiser", default="ffdnet", choices=["ffdnet", "SimpleCNN"])
     ap.add_argument("--size", default="256x256x8")
-    ap.add_argument("--cpu-iters", type=int, default=28)
+    ap.add_argument("--cpu-iters", type=int, default=28, help="--full: Anderson iterations of the CPU baseline's sample")
     ap.add_argument("--no-channels-last", action="store_true")
     ap.add_argument("--no-fused-epilogue", action="store_true")
     ap.add_argument("--no-fused-edges", action="store_true")
@@ -259,9 +268,9 @@ def parse_args(argv=None):
                     help="2: a batch of at least two stack slices runs as two half batches on two streams, issued alternately up to every stack launch "
                          "(DEQSCIEngine groups; bit-identical results; measured -4 % ... +1.3 %: an A/B, not the default); 1: one stream")
     ap.add_argument("--no-stack", action="store_true", help="one launch per 64->64 layer even where a run of layers fits one launch (A/B at small batches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-hbm-stream", action="store_true")
+    ap.add_argument("--no-hbm-stream", action="store_true", help="--full: skip the streaming kernels alone (hbm_stream_roofline)")
     ap.add_argument("--ranks-share-gpu0", action="store_true",
                     help="test rig for a one-GPU box: all ranks on cuda:0, gloo collective (real engine, real sharding; not a measurement)")
     ap.add_argument("--plumbing-selftest", action="store_true",
@@ -596,7 +605,7 @@ def run_rank(args):
             for ct in conv_timers.values():
                 ct.close()
         if world == 1 and not selftest:
-            if not args.no_other_kernel and not args.no_winograd:
+            if args.full and not args.no_other_kernel and not args.no_winograd:
                 # the same step under the OTHER conv64 policies, `--other-steps` timed steps each behind a warm-up step, outside the timed region:
                 # what the all-fp32-MFMA paths deliver on this very box, sustained (the reader who does not accept split-fp16 operands as fp32
                 # arithmetic takes "fast32")
@@ -616,7 +625,7 @@ def run_rank(args):
                     out["other_conv64_policies"][name] = {"value": M * B / dt2, "unit": "frames/s", "ms_per_step": 1e3 * dt2, "steps": args.other_steps,
                                                           "warmup": 1}
                     del eng2, step2
-            if not args.no_other_configs and args.denoiser == "ffdnet" and args.size == "256x256x8":
+            if args.full and not args.no_other_configs and args.denoiser == "ffdnet" and args.size == "256x256x8":
                 # short runs OUTSIDE the timed region, same box, each behind a warm-up step: (a) the reference's f-call count measured, not
                 # scaled (extra_call = the dead f(z) of new_equilibrium_utils_yaping.py:271-272: 182 calls); (b) the other stack kernel; (c) the
                 # reference's Anderson arithmetic (fp32 Gram: anderson_arith="reference"); (d) BASELINE config 5 (SimpleCNN) and (e) config 4
@@ -666,12 +675,12 @@ def run_rank(args):
                 del e_, st1
                 oc["config2_shipped_clips"] = config2_shipped_clips(args, dev)
                 out["other_configs"] = oc
-            if not args.no_hbm_stream:
+            if args.full and not args.no_hbm_stream:
                 del y, Phi
                 out["hbm_stream_roofline"] = hbm_stream_roofline(H, W, B, eng.m, dev)
-            if not args.no_parity_check:
+            if args.full and not args.no_parity_check:
                 out["parity_spot_check"] = parity_spot_check(args, dev, H, W, B)
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_iters, f_calls, H, W, B, args.denoiser)
             # the numbers a reader asks for next to the headline, as scalars: in `config` (which record keepers parse whole) and once more as
             # the LAST key of the line (which survives a tail cut).  frames/s unless named otherwise; all on this box, outside the timed region

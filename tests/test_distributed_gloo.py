@@ -187,6 +187,22 @@ def test_bench_dump_outputs_two_ranks(tmp_path):
     assert out.returncode != 0 and "--steps" in out.stderr
 
 
+def test_bench_full_is_opt_in():
+    """What the headline does not need runs only under `--full` (off by default); the option is accepted wherever bench.py runs."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--plumbing-selftest", "--full", "--size", "16x12x8", "--steps", "1",
+                          "--warmup", "0"], capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0])["data"] == "selftest"
+
+
 def test_bench_dump_outputs_keeps_to_64_mb(tmp_path):
     """An output above the budget is cut to a fixed, seeded sample of whole measurements, named by <name>_sample_index.npy."""
     import numpy as np

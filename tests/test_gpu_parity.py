@@ -2142,6 +2142,36 @@ def test_bench_two_ranks_on_one_gpu_real_engine():
     assert rec["allgather_bytes_per_step"] == 2 * 2 * 256 * 256 * 8 * 4 and rec["value"] > 0 and 0 < rec["final_res"] < 1
 
 
+def test_bench_plain_run_and_full():
+    """A plain `bench.py --gpus 1` line carries the headline and the in-loop rooflines of its timed steps, and nothing that takes runs of its
+    own; `--full` adds the other policies, the other configurations, the streaming kernels alone, the oracle spot check and the CPU
+    baseline (at 12 iterations here: what is checked is that each leg runs and lands on the line, not its figure)."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--iters", "12", "--steps", "1", "--warmup", "1"]
+    moved = ("other_conv64_policies", "other_configs", "hbm_stream_roofline", "parity_spot_check", "cpu_baseline")
+    recs = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-iters", "2", "--other-steps", "1"])):
+        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=900, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        recs[name] = json.loads(lines[0])
+    for rec in recs.values():
+        assert rec["metric"] == "reconstructed frames/sec at 256x256x8, 180 DEQ iters" and rec["unit"] == "frames/s" and rec["higher_is_better"] is True
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["config"]["f_calls_per_step"] == 13
+        assert rec["roofline"]["bound"] == "mfma" and rec["hbm_roofline"]["bound"] == "hbm"
+        assert list(rec)[-1] == "summary" and rec["summary"]["headline_frames_per_s"] == round(rec["value"], 2)
+    assert not any(k in recs["plain"] for k in moved), [k for k in moved if k in recs["plain"]]
+    full = recs["full"]
+    assert all(k in full for k in moved), [k for k in moved if k not in full]
+    assert full["parity_spot_check"]["ok"] and full["cpu_baseline"]["value"] > 0
+    assert "fast32" in full["other_conv64_policies"] and "config2_shipped_clips" in full["other_configs"]
+    assert {"config4_512x512x16", "one_measurement_per_call", "parity_spot_check_rel_l2"} <= set(full["summary"])
+
+
 def test_engine_512x512x16_ffdnet_vs_oracle():
     """BASELINE config 4 with its own denoiser: FFDNet at 512x512x16 (half-resolution planes of 256x256 through the head / tail
     stencils and the Winograd layers, the B = 16 kernel instantiations, batch 2 with per-sample masks), and_maxiters=5, against

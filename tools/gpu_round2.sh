@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r02
 cd $R
-timeout 900 python bench.py --steps 2 --warmup 1 2>&1 | grep "^{" > $O/r02_bench_n1.json
+timeout 900 python bench.py --full --steps 2 --warmup 1 2>&1 | grep "^{" > $O/r02_bench_n1.json
 timeout 900 python bench.py --steps 1 --warmup 1 --denoiser SimpleCNN --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{" > $O/r02_bench_n1_simplecnn.json
 ( timeout 900 python bench.py --steps 1 --warmup 1 --size 512x512x16 --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 3 --warmup 2 --batch-per-gpu 1 --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{";

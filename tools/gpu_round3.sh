@@ -6,8 +6,8 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03p
 cd $R
 skip() { [[ " $R3_SKIP " == *" $1 "* ]]; }
-timeout 900 python bench.py --steps 3 --warmup 1 2>&1 | grep "^{" > $O/r03_bench_n1.json
-timeout 900 python bench.py --steps 2 --warmup 1 --denoiser SimpleCNN --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{" > $O/r03_bench_n1_simplecnn.json
+timeout 900 python bench.py --full --steps 3 --warmup 1 2>&1 | grep "^{" > $O/r03_bench_n1.json
+timeout 900 python bench.py --full --steps 2 --warmup 1 --denoiser SimpleCNN --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{" > $O/r03_bench_n1_simplecnn.json
 ( timeout 900 python bench.py --steps 1 --warmup 1 --size 512x512x16 --no-cpu-baseline --no-hbm-stream --no-other-kernel 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 3 --warmup 2 --batch-per-gpu 1 --no-cpu-baseline --no-hbm-stream --no-other-kernel 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 3 --warmup 2 --batch-per-gpu 1 --no-graph --no-cpu-baseline --no-hbm-stream --no-other-kernel 2>&1 | grep "^{";

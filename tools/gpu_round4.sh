@@ -9,8 +9,8 @@ O=$R/gpurun_out/r04p
 cd $R
 skip() { [[ " $R4_SKIP " == *" $1 "* ]]; }
 ( timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 ) > $O/r04_gputest_summary.txt
-timeout 900 python bench.py --steps 5 --warmup 1 2>&1 | grep "^{" > $O/r04_bench_n1.json
-timeout 900 python bench.py --steps 3 --warmup 1 --denoiser SimpleCNN --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{" > $O/r04_bench_n1_simplecnn.json
+timeout 900 python bench.py --full --steps 5 --warmup 1 2>&1 | grep "^{" > $O/r04_bench_n1.json
+timeout 900 python bench.py --full --steps 3 --warmup 1 --denoiser SimpleCNN --no-cpu-baseline --no-hbm-stream 2>&1 | grep "^{" > $O/r04_bench_n1_simplecnn.json
 ( timeout 900 python bench.py --steps 1 --warmup 1 --size 512x512x16 --no-cpu-baseline --no-hbm-stream --no-other-kernel --no-parity-check 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 6 --warmup 2 --batch-per-gpu 1 --no-cpu-baseline --no-hbm-stream --no-other-kernel --no-parity-check 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 6 --warmup 2 --batch-per-gpu 1 --no-graph --no-cpu-baseline --no-hbm-stream --no-other-kernel --no-parity-check 2>&1 | grep "^{";

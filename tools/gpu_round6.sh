@@ -8,7 +8,7 @@ O=$R/gpurun_out/r06p
 cd $R
 skip() { [[ " $R6_SKIP " == *" $1 "* ]]; }
 if ! skip tests; then ( timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -3 ) > $O/r06_gputest_summary.txt; fi
-timeout 900 python bench.py --steps 5 --warmup 1 2>&1 | grep "^{" > $O/r06_bench_n1.json
+timeout 900 python bench.py --full --steps 5 --warmup 1 2>&1 | grep "^{" > $O/r06_bench_n1.json
 if ! skip shapes; then
 ( timeout 900 python bench.py --steps 6 --warmup 2 --batch-per-gpu 1 --no-cpu-baseline --no-hbm-stream --no-other-kernel --no-other-configs --no-parity-check 2>&1 | grep "^{";
   timeout 900 python bench.py --steps 6 --warmup 2 --batch-per-gpu 1 --no-graph --no-cpu-baseline --no-hbm-stream --no-other-kernel --no-other-configs --no-parity-check 2>&1 | grep "^{";

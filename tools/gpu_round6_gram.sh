@@ -8,7 +8,7 @@ timeout 1500 python -m pytest tests/test_gpu_parity.py -q -x -k "reference_gram 
 tail -4 $O/tests.log
 Q="--no-other-kernel --no-other-configs --no-cpu-baseline --no-hbm-stream"
 for g in auto 1; do
-  python bench.py --steps 3 --warmup 1 --groups $g $Q 2>&1 | tail -1 > $O/bench_g$g.json
+  python bench.py --full --steps 3 --warmup 1 --groups $g $Q 2>&1 | tail -1 > $O/bench_g$g.json
   python - <<PY
 import json
 d=json.load(open("$O/bench_g$g.json")); r=d.get("roofline",{})

@@ -11,7 +11,7 @@ for v in "$@"; do
     DEQSCI_HIP_LIB=$PWD/build/w16v/lib_$v.so STACK_IMAGES=64 timeout 300 python tools/stack_bench.py 2>&1 | grep -v amdgpu.ids | tail -1 >> $O/stack.txt
   done
   DEQSCI_HIP_LIB=$PWD/build/w16v/lib_$v.so STACK_IMAGES=8 timeout 300 python tools/stack_bench.py 2>&1 | grep -v amdgpu.ids | tail -1 >> $O/stack.txt
-  DEQSCI_HIP_LIB=$PWD/build/w16v/lib_$v.so timeout 600 python bench.py --steps 3 --warmup 1 --no-other-kernel --no-other-configs --no-cpu-baseline --no-hbm-stream 2>&1 | tail -1 | python -c "
+  DEQSCI_HIP_LIB=$PWD/build/w16v/lib_$v.so timeout 600 python bench.py --full --steps 3 --warmup 1 --no-other-kernel --no-other-configs --no-cpu-baseline --no-hbm-stream 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 r = d.get('roofline', {})
