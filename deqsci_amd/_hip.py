@@ -70,6 +70,9 @@ SIGNATURES = {
     "deqsci_ssim_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _ptr, _ptr],
     "deqsci_gaptv_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _f64, _f64, _f64, _int, _ptr, _ptr, _ptr],
     "deqsci_tv_chambolle_f32": [_ptr, _ptr, _i64, _i64, _i64, _f64, _f64, _int, _f64, _ptr, _ptr, _ptr],
+    "deqsci_relu_mask_pack_f32": [_ptr, _ptr, _i64, _ptr],
+    "deqsci_conv3x3_c64_winograd_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
+    "deqsci_conv3x3_c1_to_64_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -471,6 +474,39 @@ def conv3x3_c1_to_64(x, w_packed, relu=True, out=None, sp16=False, out_rng=None,
     return o
 
 
+def relu_mask_pack(a, out=None):
+    """fp32 channels_last (n,64,H,W) activation -> (n,H,W) int64 words, bit c = (a[:, c] > 0) (csrc/vjp.hip: the implicit backward's
+    ReLU masks; +-0.0 and NaN give 0)."""
+    n, c, H, W = a.shape
+    if c != 64 or not a.is_contiguous(memory_format=torch.channels_last) or a.dtype != torch.float32 or not a.is_cuda:
+        raise DeqsciHipError("relu_mask_pack: fp32 channels_last GPU activation with 64 channels required")
+    o = out if out is not None else torch.empty((n, H, W), device=a.device, dtype=torch.int64)
+    if tuple(o.shape) != (n, H, W) or o.dtype != torch.int64 or not o.is_contiguous() or o.device != a.device:
+        raise DeqsciHipError("relu_mask_pack: out must be a contiguous int64 (n,H,W) tensor on the activation's device")
+    with _dev(a):
+        _check(load().deqsci_relu_mask_pack_f32(a.data_ptr(), o.data_ptr(), n * H * W, _stream()), "relu_mask_pack")
+    return o
+
+
+def _mask_ptr(mask, n, H, W, what):
+    if (not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (n, H, W) or mask.dtype != torch.int64 or not mask.is_cuda
+            or not mask.is_contiguous()):
+        raise DeqsciHipError(f"{what}: mask must be the contiguous int64 (n,H,W) = {(n, H, W)} GPU tensor of relu_mask_pack")
+    return mask.data_ptr()
+
+
+def conv3x3_c1_to_64_masked(x, w_packed, mask, out=None):
+    """x (n,1,H,W) planar -> conv3x3(x, w, pad=1) * mask as a channels_last (n,64,H,W) activation (mask: relu_mask_pack's words)."""
+    n, c, H, W = x.shape
+    if c != 1:
+        raise DeqsciHipError(f"conv3x3_c1_to_64_masked: (n,1,H,W) image required, got {tuple(x.shape)}")
+    o = out if out is not None else torch.empty((n, 64, H, W), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    with _dev(x):
+        _check(load().deqsci_conv3x3_c1_to_64_masked_f32(_p(x, "x"), _p(w_packed, "w_packed"), _mask_ptr(mask, n, H, W, "conv3x3_c1_to_64_masked"),
+                                                         o.data_ptr(), n, H, W, _stream()), "conv3x3_c1_to_64_masked")
+    return o
+
+
 def pack_head_weights(w):
     """(64,5,3,3) conv weight -> [ch*9+tap (45)][cout//4 (16)][cout%4 (4)] for deqsci_ffdnet_head_f32."""
     if tuple(w.shape) != (64, 5, 3, 3):
@@ -530,6 +566,21 @@ def conv3x3_c64_winograd(x, u_packed, bias=None, relu=True, out=None, events=Non
         else:
             _check(load().deqsci_conv3x3_c64_winograd_timed_f32(x.data_ptr(), _p(u_packed, "u_packed"), _p(bias, "bias", True), o.data_ptr(),
                                                                 n, H, W, 1 if relu else 0, _stream(), ev[0], ev[1]), "conv3x3_c64_winograd_timed")
+    return o
+
+
+def conv3x3_c64_winograd_masked(x, u_packed, mask, out=None):
+    """x (n,64,H,W) channels_last -> conv3x3(x, w, pad=1) * mask (no bias, no ReLU; mask: relu_mask_pack's words) as a new channels_last
+    tensor: the Winograd F(2x2,3x3) kernel with the implicit backward's epilogue."""
+    n, c, H, W = x.shape
+    if c != 64 or not x.is_contiguous(memory_format=torch.channels_last) or x.dtype != torch.float32 or not x.is_cuda:
+        raise DeqsciHipError("conv3x3_c64_winograd_masked: fp32 channels_last GPU activation with 64 channels required")
+    _check_packed(u_packed, 16, "pack_winograd_weights")
+    o = out if out is not None else torch.empty_like(x, memory_format=torch.channels_last)
+    with _dev(x):
+        _check(load().deqsci_conv3x3_c64_winograd_masked_f32(x.data_ptr(), _p(u_packed, "u_packed"),
+                                                             _mask_ptr(mask, n, H, W, "conv3x3_c64_winograd_masked"), o.data_ptr(),
+                                                             n, H, W, _stream()), "conv3x3_c64_winograd_masked")
     return o
 
 

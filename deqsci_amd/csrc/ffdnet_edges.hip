@@ -139,11 +139,13 @@ __global__ __launch_bounds__(TB) void edge_tail_kernel(const float* __restrict__
 constexpr int H1_T = 32, H1_P = H1_T + 2, H1_PS = H1_P + 1;
 // OUT_SP16: the output as an sp16 activation (1) or a p32 activation (2: the 16-byte pixels of csrc/conv_w16.hip, 2^e y unsplit, even / odd
 // columns of a 64-column block apart) holding 2^e y, e from the range (out_amax, out_exp) (common.hpp); `track` (may be NULL):
-// max |y| of the launch folded into *track - the range measurement of the first f-call
+// max |y| of the launch folded into *track - the range measurement of the first f-call.  OUT_SP16 = 3: fp32 channels_last out, no ReLU,
+// y = conv * mask with `mask` one 64-bit word per pixel (bit c = channel c) - with the tail's weights transposed and flipped, the tail's
+// transpose in the implicit backward (csrc/vjp.hip)
 template <int OUT_SP16>
 __global__ __launch_bounds__(TB) void conv_c1_to_64_kernel(const float* __restrict__ x, const float* __restrict__ wq,
                                                            float* __restrict__ h, int H, int W, int relu, const float* __restrict__ out_amax,
-                                                           int out_exp, float* __restrict__ track) {
+                                                           int out_exp, float* __restrict__ track, const uint32_t* __restrict__ mask) {
     __shared__ float patch[H1_P * H1_PS];
     __shared__ uint32_t trk_s[TB / WAVE];
     float tmax = 0.0f;
@@ -172,7 +174,12 @@ __global__ __launch_bounds__(TB) void conv_c1_to_64_kernel(const float* __restri
         for (int tap = 0; tap < 9; ++tap) acc = fma4(patch[(lr + tap / 3) * H1_PS + lc + tap % 3], wr[tap], acc);
         if (r < H && c < W) {
             if (relu) { acc.x = fmaxf(acc.x, 0.0f); acc.y = fmaxf(acc.y, 0.0f); acc.z = fmaxf(acc.z, 0.0f); acc.w = fmaxf(acc.w, 0.0f); }
-            if (OUT_SP16) {
+            if (OUT_SP16 == 3) {                                // couts 4 cq .. 4 cq + 3: half cq >> 3 of the pixel's word
+                const uint32_t m = mask[2 * ((int64_t)n * H * W + (int64_t)r * W + c) + (cq >> 3)] >> (4 * (cq & 7));
+                acc.x = (m & 1u) ? acc.x : 0.0f; acc.y = (m & 2u) ? acc.y : 0.0f;
+                acc.z = (m & 4u) ? acc.z : 0.0f; acc.w = (m & 8u) ? acc.w : 0.0f;
+                st4(hn + ((int64_t)r * W + c) * 64 + 4 * cq, acc);
+            } else if (OUT_SP16) {
                 if (track) tmax = fmaxf(fmaxf(tmax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));   // (uniform branch)
                 if (OUT_SP16 == 2) {                            // plane cq = couts 4 cq .. 4 cq + 3
                     const int64_t nbc = (W + 63) >> 6;
@@ -402,22 +409,31 @@ extern "C" int deqsci_conv3x3_c64_to_1_f32(const float* h, const float* w_packed
 }
 
 static int c1_to_64_impl(const float* x, const float* w_packed, float* h, int64_t n, int64_t H, int64_t W, int relu, int sp16, const float* out_amax,
-                         int out_exp, float* track_amax, deqsci_stream_t stream) {
+                         int out_exp, float* track_amax, deqsci_stream_t stream, const uint64_t* mask = nullptr) {
     if (!x || !w_packed || !h) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
     if (n > 65535 || H > (1 << 20) || W > (1 << 20) || out_exp < -SP16_EXP_LIMIT || out_exp > SP16_EXP_LIMIT) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(w_packed) || !aligned16(h)) return DEQSCI_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)ceil_div(W, H1_T), (unsigned)ceil_div(H, H1_T), (unsigned)n);
-    if (sp16 == 2) hipLaunchKernelGGL(conv_c1_to_64_kernel<2>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax);
-    else if (sp16) hipLaunchKernelGGL(conv_c1_to_64_kernel<1>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax);
-    else hipLaunchKernelGGL(conv_c1_to_64_kernel<0>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax);
+    const uint32_t* m32 = reinterpret_cast<const uint32_t*>(mask);
+    if (mask) hipLaunchKernelGGL(conv_c1_to_64_kernel<3>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, 0, nullptr, 0, nullptr, m32);
+    else if (sp16 == 2) hipLaunchKernelGGL(conv_c1_to_64_kernel<2>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax, m32);
+    else if (sp16) hipLaunchKernelGGL(conv_c1_to_64_kernel<1>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax, m32);
+    else hipLaunchKernelGGL(conv_c1_to_64_kernel<0>, grid, dim3(TB), 0, st, x, w_packed, h, (int)H, (int)W, relu, out_amax, out_exp, track_amax, m32);
     return launch_status();
 }
 
 extern "C" int deqsci_conv3x3_c1_to_64_f32(const float* x, const float* w_packed, float* h, int64_t n, int64_t H, int64_t W,
                                            int relu, deqsci_stream_t stream) {
     return c1_to_64_impl(x, w_packed, h, n, H, W, relu, 0, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int deqsci_conv3x3_c1_to_64_masked_f32(const float* x, const float* w_packed, const uint64_t* mask, float* h, int64_t n,
+                                                  int64_t H, int64_t W, deqsci_stream_t stream) {
+    if (!mask) return DEQSCI_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(mask) & 7) != 0) return DEQSCI_ERR_ALIGN;
+    return c1_to_64_impl(x, w_packed, h, n, H, W, 0, 0, nullptr, 0, nullptr, stream, mask);
 }
 
 extern "C" int deqsci_conv3x3_c1_to_64_sp16(const float* x, const float* w_packed, void* h_sp16, int64_t n, int64_t H, int64_t W,

@@ -93,10 +93,14 @@ __device__ __forceinline__ int wg_div(int t, uint32_t mg, uint32_t sh) { return 
 
 // tiles_x / tiles_y: block tiles per image row / column; n_tiles = images * tiles_x * tiles_y;
 // (mg_img, sh_img) / (mg_tx, sh_tx): division magic for tiles_x * tiles_y and tiles_x
-__global__ __launch_bounds__(WG_TB, 2) void winograd_conv64_kernel(const float* __restrict__ x, const float* __restrict__ Ug,
-                                                                   const float* __restrict__ bias, float* __restrict__ y,
-                                                                   int H, int W, int relu, int tiles_x, int tiles_y, int n_tiles,
-                                                                   uint32_t mg_img, uint32_t sh_img, uint32_t mg_tx, uint32_t sh_tx) {
+// MASK = 1: the implicit backward's layer (csrc/vjp.hip): no bias, no ReLU, output = conv * mask with mask one 64-bit word per pixel
+// (bit c = channel c), read as two 32-bit halves (cout half wn) in the epilogue only.
+template <int MASK>
+__device__ __forceinline__ void winograd_conv64_body(const float* __restrict__ x, const float* __restrict__ Ug,
+                                                     const float* __restrict__ bias, float* __restrict__ y,
+                                                     int H, int W, int relu, int tiles_x, int tiles_y, int n_tiles,
+                                                     uint32_t mg_img, uint32_t sh_img, uint32_t mg_tx, uint32_t sh_tx,
+                                                     const uint32_t* __restrict__ mask) {
     __shared__ __attribute__((aligned(16))) float Us[2 * WG_U_CHUNK];             // 2 x U[xi][cout half][MFMA lane][j][2]   64 KB
     __shared__ __attribute__((aligned(16))) float Raw[2 * WG_RAW_BUF];            // 2 x raw chunk tile                    27.4 KB
     __shared__ __attribute__((aligned(16))) float bias_s[64];
@@ -295,6 +299,22 @@ __global__ __launch_bounds__(WG_TB, 2) void winograd_conv64_kernel(const float* 
                     }
                 }
             }
+            if (MASK && in0) {                                // 4 couts 32 wn + 16 j + 4 (lane >> 4) + e of the four pixels
+                const int64_t p = (int64_t)n * H * W + (int64_t)oy * W + ox;
+                const int sh = 16 * j + 4 * (lane >> 4);
+                const uint32_t m00 = mask[2 * p + wn] >> sh;
+                const uint32_t m01 = inx ? mask[2 * (p + 1) + wn] >> sh : 0u;
+                const uint32_t m10 = iny ? mask[2 * (p + W) + wn] >> sh : 0u;
+                const uint32_t m11 = inx && iny ? mask[2 * (p + W + 1) + wn] >> sh : 0u;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int b = 2 * h + e;
+                        o00[h][e] = (m00 >> b) & 1u ? o00[h][e] : 0.0f; o01[h][e] = (m01 >> b) & 1u ? o01[h][e] : 0.0f;
+                        o10[h][e] = (m10 >> b) & 1u ? o10[h][e] : 0.0f; o11[h][e] = (m11 >> b) & 1u ? o11[h][e] : 0.0f;
+                    }
+            }
             if (in0) {
                 float* oj = o + 16 * j;
                 st4s(oj, make_float4(o00[0][0], o00[0][1], o00[1][0], o00[1][1]));
@@ -431,6 +451,20 @@ __global__ __launch_bounds__(WG_TB, 2) void winograd_conv64_kernel(const float* 
 #endif
 }
 
+__global__ __launch_bounds__(WG_TB, 2) void winograd_conv64_kernel(const float* __restrict__ x, const float* __restrict__ Ug,
+                                                                   const float* __restrict__ bias, float* __restrict__ y,
+                                                                   int H, int W, int relu, int tiles_x, int tiles_y, int n_tiles,
+                                                                   uint32_t mg_img, uint32_t sh_img, uint32_t mg_tx, uint32_t sh_tx) {
+    winograd_conv64_body<0>(x, Ug, bias, y, H, W, relu, tiles_x, tiles_y, n_tiles, mg_img, sh_img, mg_tx, sh_tx, nullptr);
+}
+
+__global__ __launch_bounds__(WG_TB, 2) void winograd_masked_conv64_kernel(const float* __restrict__ x, const float* __restrict__ Ug,
+                                                                          const uint32_t* __restrict__ mask, float* __restrict__ y,
+                                                                          int H, int W, int tiles_x, int tiles_y, int n_tiles,
+                                                                          uint32_t mg_img, uint32_t sh_img, uint32_t mg_tx, uint32_t sh_tx) {
+    winograd_conv64_body<1>(x, Ug, nullptr, y, H, W, 0, tiles_x, tiles_y, n_tiles, mg_img, sh_img, mg_tx, sh_tx, mask);
+}
+
 }  // namespace deqsci
 
 #ifndef WG_NO_CABI
@@ -445,7 +479,7 @@ static void wg_magic(uint32_t d, uint32_t* mg, uint32_t* sh) {
 }
 
 static int winograd_impl(const float* x, const float* u_packed, const float* bias, float* y, int64_t n, int64_t H, int64_t W,
-                         int relu, deqsci_stream_t stream, hipEvent_t ev0, hipEvent_t ev1) {
+                         int relu, deqsci_stream_t stream, hipEvent_t ev0, hipEvent_t ev1, const uint64_t* mask = nullptr) {
     if (!x || !u_packed || !y) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
     if (H > (1 << 20) || W > (1 << 20) || x == y) return DEQSCI_ERR_UNSUPPORTED;
@@ -462,7 +496,10 @@ static int winograd_impl(const float* x, const float* u_packed, const float* bia
     wg_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
     // (the timed entry point stamps ev0/ev1 with the dispatch's own begin/end; the plain one is an ordinary launch, which
     // is what a stream capture - DEQSCIEngine's hipGraph - records)
-    if (ev0 || ev1)
+    if (mask)
+        hipLaunchKernelGGL(winograd_masked_conv64_kernel, grid, dim3(WG_TB), 0, st, x, u_packed, reinterpret_cast<const uint32_t*>(mask), y,
+                           (int)H, (int)W, (int)tiles_x, (int)tiles_y, (int)n_tiles, mg_img, sh_img, mg_tx, sh_tx);
+    else if (ev0 || ev1)
         hipExtLaunchKernelGGL(winograd_conv64_kernel, grid, dim3(WG_TB), 0, st, ev0, ev1, 0, x, u_packed, bias, y, (int)H, (int)W, relu,
                               (int)tiles_x, (int)tiles_y, (int)n_tiles, mg_img, sh_img, mg_tx, sh_tx);
     else
@@ -474,6 +511,13 @@ static int winograd_impl(const float* x, const float* u_packed, const float* bia
 extern "C" int deqsci_conv3x3_c64_winograd_f32(const float* x, const float* u_packed, const float* bias, float* y, int64_t n,
                                                int64_t H, int64_t W, int relu, deqsci_stream_t stream) {
     return winograd_impl(x, u_packed, bias, y, n, H, W, relu, stream, nullptr, nullptr);
+}
+
+extern "C" int deqsci_conv3x3_c64_winograd_masked_f32(const float* x, const float* u_packed, const uint64_t* mask, float* y, int64_t n,
+                                                      int64_t H, int64_t W, deqsci_stream_t stream) {
+    if (!mask) return DEQSCI_ERR_NULL;
+    if ((reinterpret_cast<uintptr_t>(mask) & 7) != 0) return DEQSCI_ERR_ALIGN;
+    return winograd_impl(x, u_packed, nullptr, y, n, H, W, 0, stream, nullptr, nullptr, mask);
 }
 
 extern "C" int deqsci_conv3x3_c64_winograd_timed_f32(const float* x, const float* u_packed, const float* bias, float* y, int64_t n,

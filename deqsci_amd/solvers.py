@@ -17,7 +17,7 @@ whole loop to deqsci_amd.engine.DEQSCIEngine (planar state, fused kernels, no pe
 import torch
 import torch.nn as nn
 
-from . import _hip, autograd as _ag
+from . import _hip, autograd as _ag, vjp as _vjp
 from ._hip import LAYOUT_BHW, LAYOUT_HWB
 from .engine import SIGMA0, SIGMA_DECAY, DEQSCIEngine
 from .operators import A_torch_, At_torch_
@@ -35,6 +35,7 @@ class EquilibriumProxGradSCI(nn.Module):
         self.noise_sigma = None
         self._y_ref = None          # the measurement tensor of the previous call (held, so its storage cannot be recycled)
         self._y_ver = -1
+        self._taped = None          # (z1 planar (bsz*B,1,H,W), sigma or None) of the last taped call: the point device_vjp linearises at
 
     def _sigma(self, y, n):
         """sigma bookkeeping of :408-413: restart at 60/255 when y.mean() changes, else *0.971.
@@ -65,12 +66,15 @@ class EquilibriumProxGradSCI(nn.Module):
         else:
             z1 = z + self.At((y - self.A(z, Phi)) / Phi_sum, Phi)
         zp = z1.permute(0, 3, 1, 2).contiguous()
+        self._taped = (zp.detach().view(bsz * c, 1, w, h), None)
         if tag == 'conv2d':
             return op(zp.view(bsz * c, 1, w, h)).view(bsz, c, w, h).permute(0, 2, 3, 1)
         if tag == 'conv3d':
             return op(zp.view(bsz, 1, c, w, h)).view(bsz, c, w, h).permute(0, 2, 3, 1)
         if tag == 'ffdnet':
-            noise = op(zp.view(bsz * c, 1, w, h), self._sigma(y, bsz * c))
+            sigma = self._sigma(y, bsz * c)
+            self._taped = (self._taped[0], sigma)
+            noise = op(zp.view(bsz * c, 1, w, h), sigma)
         elif tag == 'denoiser':
             noise = op(zp.view(bsz * c, 1, w, h))
         elif tag == '3d_denoiser':
@@ -79,6 +83,36 @@ class EquilibriumProxGradSCI(nn.Module):
             print('unknown nonlinear_op tag!')
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
+
+    def device_vjp_eligibility(self):
+        """(ok, reason): whether device_vjp can serve this map (HIP GAP operators and a denoiser deqsci_amd.vjp.eligibility accepts)."""
+        if not (self.A is A_torch_ and self.At is At_torch_):
+            return False, "custom A / At: the device map uses the HIP GAP projection"
+        return _vjp.eligibility(self.nonlinear_op)
+
+    def device_vjp(self, Phi, Phi_sum):
+        """The map v -> J_f(z0)^T v = P (v - J_D(z1)^T v) of the LAST taped call f(z0) (its z1 and sigma: no further call of f, the
+        sigma state stays where that call left it), on the HIP kernels: v and the result (bsz,H,W,B) fp32 on the GPU, no host sync."""
+        if self._taped is None:
+            raise RuntimeError("device_vjp: no taped call of this map to linearise at")
+        ok, why = self.device_vjp_eligibility()
+        if not ok:
+            raise ValueError(f"device_vjp: {why}")
+        z1p, sigma = self._taped
+        jd = _vjp.DenoiserVJP(self.nonlinear_op, z1p, sigma)
+        Phi, Phi_sum = _hip.f32c(Phi), _hip.f32c(Phi_sum)
+        zero_y = None
+
+        def jmap(v):
+            nonlocal zero_y
+            v = _hip.f32c(v)
+            if zero_y is None:
+                zero_y = torch.zeros(v.shape[:3], device=v.device, dtype=torch.float32)
+            if not jd.zero:
+                vp = _hip.transpose(v, LAYOUT_BHW)                                    # (bsz,B,H,W) = the denoiser's (bsz*B,1,H,W)
+                v = _hip.residual_out(vp, jd(vp.view(jd.shape)).view(vp.shape), LAYOUT_HWB)   # v - J_D^T v, back in (bsz,H,W,B)
+            return _hip.gap_update(v, Phi, zero_y, Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
+        return jmap
 
     def forward(self, z, y, Phi, Phi_sum):
         bsz, w, h, c = z.shape
@@ -176,6 +210,12 @@ class DEQFixedPoint(nn.Module):
         self.use_engine = True
         self.engine_options = {}          # extra DEQSCIEngine arguments of this build, e.g. {"conv64": "fast32"} (fp32-MFMA kernels only)
         self._engine = None
+        # how the backward hook of a taped forward forms J_f(z0)^T v: "autograd" (torch.autograd.grad through f0's graph, the reference's
+        # way) or "device" (EquilibriumProxGradSCI.device_vjp: the HIP kernels, falling back to autograd where the denoiser has no device
+        # VJP - deqsci_amd.vjp.eligibility).  last_backward_path: the path the last hook ran; backward_fallback_reason: why not "device".
+        self.implicit_backward = "autograd"
+        self.last_backward_path = None
+        self.backward_fallback_reason = None
 
     def _engine_for(self):
         f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
@@ -199,6 +239,26 @@ class DEQFixedPoint(nn.Module):
             self._engine = (key, DEQSCIEngine(f.nonlinear_op, **{**cfg, **self.engine_options}))
         return self._engine[1]
 
+    def _device_map(self, Phi, Phi_sum):
+        """implicit_backward = "device": the device map of the taped call just made, or None (autograd) with the reason recorded."""
+        if self.implicit_backward not in ("autograd", "device"):
+            raise ValueError(f"implicit_backward={self.implicit_backward!r}: expected 'autograd' or 'device'")
+        self.backward_fallback_reason = None
+        if self.implicit_backward == "autograd":
+            return None
+        if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
+            self.backward_fallback_reason = "DataParallel over several devices (the taped call ran on replicas)"
+            return None
+        f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
+        if not isinstance(f, EquilibriumProxGradSCI):
+            self.backward_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
+            return None
+        ok, why = f.device_vjp_eligibility()
+        if not ok:
+            self.backward_fallback_reason = why
+            return None
+        return f.device_vjp(Phi, Phi_sum)
+
     def forward(self, x, Phi, Phi_sum, initial_point=None, train_flag=True):
         """x is the measurement y.  Without a tape (torch.no_grad(), or no parameter of f requiring a gradient) this is the
         inference path; with one it is the reference's training forward (:249-281): solve without tape, one taped f call,
@@ -212,11 +272,19 @@ class DEQFixedPoint(nn.Module):
             z = self.f(z, x, Phi, Phi_sum)                                     # re-engage the tape (:268)
             z0 = z.clone().detach().requires_grad_()
             f0 = self.f(z0, x, Phi, Phi_sum)                                   # Jacobian-vector products come from this graph
+            jmap = self._device_map(Phi, Phi_sum)
 
-            def backward_hook(grad):
-                g, self.backward_res = self.solver(
-                    lambda v: torch.autograd.grad(f0, z0, v, retain_graph=True)[0] + grad, grad, **self.kwargs)
-                return g
+            if jmap is not None:
+                def backward_hook(grad):
+                    self.last_backward_path = "device"
+                    g, self.backward_res = self.solver(lambda v: jmap(v) + grad, grad, **self.kwargs)
+                    return g
+            else:
+                def backward_hook(grad):
+                    self.last_backward_path = "autograd"
+                    g, self.backward_res = self.solver(
+                        lambda v: torch.autograd.grad(f0, z0, v, retain_graph=True)[0] + grad, grad, **self.kwargs)
+                    return g
             z.register_hook(backward_hook)
             return z
         eng = self._engine_for()

@@ -1,0 +1,170 @@
+"""The DEQ's implicit backward on the device: vector-Jacobian products J_D(x)^T v of a denoiser plugin on the HIP kernels.
+
+The training forward's hook (solvers/new_equilibrium_utils_yaping.py:273-276) solves  g = J_f(z0)^T g + grad, and with
+f(z) = z1 - D(z1), z1 = P z + c and P = I - Phi^T diag(1/Phi_sum) Phi symmetric,
+
+    J_f(z0)^T v = P (v - J_D(z1)^T v)          (P u = the GAP kernel with y = 0, as in deqsci_amd/autograd.py)
+
+For a conv [+BN-eval] + ReLU stack (SimpleCNN, RealSN_SimpleCNN in eval mode, DnCNN-17-style plugins) J_D^T v runs the layers
+backwards: each conv with its BN-folded weight (w * s) transposed and flipped and no bias, each ReLU replaced by its unit's mask
+from ONE forward pass at x (ReLU'(0) = 0, as in PyTorch).  The masks are fixed for all of the hook's iterations, so every
+product is linear in v:
+
+    v (n,1,H,W) -> conv3x3(1 -> 64) * mask[k-2] -> [conv3x3(64 -> 64) * mask[i-1]] for i = k-2 .. 1 -> conv3x3(64 -> 1)
+
+= csrc/ffdnet_edges.hip's 1 -> 64 stencil with the masked epilogue (the tail's transpose), csrc/winograd.hip's F(2x2,3x3) kernel with
+the masked epilogue, and the existing 64 -> 1 stencil (the head's transpose); the masks are packed one 64-bit word per pixel by
+csrc/vjp.hip.  FFDNet detaches its input (networks/ffdnet/models.py in the reference, deqsci_amd/networks/ffdnet.py), so for it
+J_D^T = 0 and the hook's product is P v alone.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _hip
+
+_FFDNET_OK = "FFDNet detaches its input: J_D^T = 0"
+
+
+def _modules():
+    from .networks import DnCNN, FFDNet
+    from .networks.simplecnn import RealSNConv2d
+    return DnCNN, FFDNet, RealSNConv2d
+
+
+def _conv_ok(conv):
+    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1) and tuple(conv.stride) == (1, 1)
+            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
+def host_plan(net):
+    """(layers, reason): the denoiser as [(weight, bias or None, relu)] with eval-mode BatchNorm folded into the conv the way
+    engine._fold_bn does it (weight * s, bias = beta - mean * s), or (None, why not) when the net is not a conv [+BN-eval] + ReLU
+    stack of 3x3, pad-1 convolutions without bias.  Usable on the CPU."""
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    if not isinstance(net, DnCNN):
+        return None, f"not a conv [+BN] + ReLU stack: {type(net).__name__}"
+    mods = list(net.dncnn)
+    layers, i = [], 0
+    while i < len(mods):
+        conv = mods[i]
+        if isinstance(conv, RealSNConv2d):
+            if conv.training:
+                return None, "RealSNConv2d in train mode (its weight is renormalised by the power iteration)"
+            w = conv.weight.detach()
+        elif isinstance(conv, torch.nn.Conv2d):
+            if not _conv_ok(conv):
+                return None, "Conv2d other than 3x3, stride 1, padding 1"
+            if conv.bias is not None:
+                return None, "Conv2d with a bias"
+            w = conv.weight.detach()
+        else:
+            return None, f"unknown module {type(conv).__name__} where a convolution was expected"
+        b = None
+        i += 1
+        if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
+            bn = mods[i]
+            if bn.training or not bn.track_running_stats:
+                return None, "BatchNorm2d in train mode (batch statistics: its Jacobian is not a fixed scale)"
+            from .engine import _fold_bn
+            w, b = _fold_bn(w, bn)
+            w, b = w.detach(), b.detach()
+            i += 1
+        relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
+        if relu:
+            i += 1
+        elif i < len(mods) and not isinstance(mods[i], (torch.nn.Conv2d, RealSNConv2d)):
+            return None, f"unknown module {type(mods[i]).__name__}"
+        layers.append((w, b, relu))
+    return layers, None
+
+
+def eligibility(net):
+    """(ok, reason): whether DenoiserVJP (and DEQFixedPoint.implicit_backward = "device") can differentiate through `net`.  CPU-safe."""
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    if isinstance(net, FFDNet):
+        if net.num_input_channels != 1:
+            return False, "FFDNet with 3 channels (the HIP kernels cover the grayscale network only)"
+        if any(isinstance(m, torch.nn.BatchNorm2d) and m.training for m in net.modules()):
+            return False, "FFDNet with BatchNorm2d in train mode"
+        return True, _FFDNET_OK
+    if getattr(net, "tag", None) != "denoiser":
+        return False, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' and 'ffdnet' plugins have a device VJP"
+    layers, why = host_plan(net)
+    if layers is None:
+        return False, why
+    shapes = [tuple(w.shape) for w, _, _ in layers]
+    if len(layers) < 2 or shapes[0] != (64, 1, 3, 3) or shapes[-1] != (1, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
+        return False, f"layer shapes {shapes}: the kernels cover 1 -> 64 -> ... -> 64 -> 1"
+    if layers[0][1] is not None or layers[-1][1] is not None:
+        return False, "bias on the first or the last layer"
+    if not all(r for _, _, r in layers[:-1]) or layers[-1][2]:
+        return False, "ReLU pattern other than after every layer but the last"
+    return True, "conv [+BN-eval] + ReLU stack"
+
+
+def _transposed(w):
+    """conv_transpose2d(g, w, padding=1) == conv2d(g, _transposed(w), padding=1) for a 3x3 kernel."""
+    return w.transpose(0, 1).flip(2, 3).contiguous()
+
+
+def plan_vjp(layers, x, v):
+    """J_D(x)^T v of the stack `layers` (host_plan) evaluated in x's dtype with F.conv2d and explicit masks - the host statement of what
+    DenoiserVJP runs (tests: float64 against torch.autograd.grad).  Returns (vjp, masks)."""
+    h, masks = x, []
+    for w, b, relu in layers[:-1]:
+        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
+        if relu:
+            masks.append(h > 0)
+            h = torch.relu(h)
+        else:
+            masks.append(None)
+    g = v
+    for i in range(len(layers) - 1, 0, -1):
+        g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
+        if masks[i - 1] is not None:
+            g = g * masks[i - 1]
+    return F.conv2d(g, _transposed(layers[0][0].to(v)), padding=1), masks
+
+
+class DenoiserVJP:
+    """v -> J_D(x)^T v for a (n,1,H,W) fp32 GPU image x and v of its shape, on the HIP kernels.  One forward pass at x (the existing fp32
+    kernels: 1 -> 64 stencil, Winograd F(2x2,3x3)) builds the ReLU masks; every call is then k-1 masked transposed layers and the 64 -> 1
+    stencil, enqueued on the current stream with no host synchronisation (safe to capture).  sigma: FFDNet's noise level (unused: its
+    input is detached, the product is zero).  Raises ValueError with eligibility()'s reason for a net it cannot differentiate."""
+
+    def __init__(self, net, x, sigma=None):
+        ok, why = eligibility(net)
+        if not ok:
+            raise ValueError(f"DenoiserVJP: {why}")
+        if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
+            raise _hip.DeqsciHipError(f"DenoiserVJP: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
+        self.shape = tuple(x.shape)
+        self.zero = why == _FFDNET_OK
+        self.masks = []
+        if self.zero:
+            return
+        layers, _ = host_plan(net)
+        x = _hip.f32c(x.detach())
+        dev = x.device
+        with torch.no_grad():
+            w0 = layers[0][0].to(dev, torch.float32)
+            h = _hip.conv3x3_c1_to_64(x, _hip.pack_c1_to_64_weights(w0), relu=True)
+            self.masks.append(_hip.relu_mask_pack(h))
+            for w, b, _ in layers[1:-1]:
+                h = _hip.conv3x3_c64_winograd(h, _hip.pack_winograd_weights(w.to(dev, torch.float32)),
+                                              None if b is None else b.to(dev, torch.float32).contiguous(), True)
+                self.masks.append(_hip.relu_mask_pack(h))
+            del h
+            self.tail_t = _hip.pack_c1_to_64_weights(_transposed(layers[-1][0].to(dev, torch.float32)))
+            self.mid_t = [_hip.pack_winograd_weights(_transposed(w.to(dev, torch.float32))) for w, _, _ in layers[1:-1]]
+            self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
+
+    def __call__(self, v):
+        if tuple(v.shape) != self.shape:
+            raise _hip.DeqsciHipError(f"DenoiserVJP: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
+        if self.zero:
+            return torch.zeros_like(v)
+        g = _hip.conv3x3_c1_to_64_masked(_hip.f32c(v), self.tail_t, self.masks[-1])
+        for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
+            g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
+        return _hip.conv3x3_c64_to_1(g, self.head_t)

@@ -382,6 +382,27 @@ int64_t deqsci_tv_chambolle_workspace_bytes(int64_t n, int64_t H, int64_t W);
 int deqsci_tv_chambolle_f32(const float* image, float* out, int64_t n, int64_t H, int64_t W, double weight, double eps,
                             int n_iter_max, double tau, int* stop, void* workspace, deqsci_stream_t stream);
 
+/* ---- the DEQ's implicit backward on the device (not on the reconstruction path) ----
+ * The hook of the training forward (solvers/new_equilibrium_utils_yaping.py:273-276) solves g = J_f(z0)^T g + grad, and every
+ * J_f^T v = P (v - J_D(z1)^T v) (P = the GAP projection with y = 0, deqsci_gap_update_f32).  J_D^T v of a conv [+BN] + ReLU stack
+ * runs the layers backwards with the weights transposed and flipped (BN folded into the scale, no bias), each ReLU replaced by
+ * the unit's mask from ONE forward pass at z1: v -> conv3x3(1 -> 64) * mask -> [conv3x3(64 -> 64) * mask] ... ->
+ * conv3x3(64 -> 1) (deqsci_conv3x3_c64_to_1_f32 with in_bias NULL).  The masks do not change between the hook's iterations.
+ * Same conventions as above: device pointers, caller-owned buffers, no allocation, no host synchronisation, graph-capturable.
+ *
+ * V0  mask (n_pixels) uint64, 8-byte aligned: bit c of mask[p] = (a[p*64 + c] > 0) for the fp32 channels_last activation a
+ *     (n_pixels, 64), 4-byte aligned - ReLU'(0) = 0 as in PyTorch: +-0.0 and NaN give 0.  n_pixels = 0: nothing is launched.
+ * V1  the 64 -> 64 layer of deqsci_conv3x3_c64_winograd_f32 (Winograd F(2x2,3x3): same x, u_packed, y, sizes and limits;
+ *     channels_last in and out) with output = conv3x3(x) * mask instead of relu(conv3x3(x) + bias): no bias, no ReLU, the mask
+ *     (n*H*W words, pixel order of y) as written by V0; 8-byte aligned.  Scale-free fp32 arithmetic: the VJP's inputs change scale
+ *     from one iteration to the next.  (F(4x4,3x3) has no masked form: at its 256-register limit the mask reads spill.)
+ * V2  the same epilogue on deqsci_conv3x3_c1_to_64_f32: h = conv3x3(x) * mask, x planar (n,1,H,W), h channels_last (n,H,W,64). */
+int deqsci_relu_mask_pack_f32(const float* a, uint64_t* mask, int64_t n_pixels, deqsci_stream_t stream);
+int deqsci_conv3x3_c64_winograd_masked_f32(const float* x, const float* u_packed, const uint64_t* mask, float* y,
+                                           int64_t n, int64_t H, int64_t W, deqsci_stream_t stream);
+int deqsci_conv3x3_c1_to_64_masked_f32(const float* x, const float* w_packed, const uint64_t* mask, float* h,
+                                       int64_t n, int64_t H, int64_t W, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
