@@ -68,6 +68,7 @@ SIGNATURES = {
     "deqsci_ffdnet_tail_p32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr],
     "deqsci_conv3x3_c1_to_64_sp16": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _int, _ptr, _ptr],
     "deqsci_ssim_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _int, _ptr, _ptr],
+    "deqsci_sqerr_rows_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _int, _ptr, _ptr],
     "deqsci_gaptv_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _f64, _f64, _f64, _int, _ptr, _ptr, _ptr],
     "deqsci_tv_chambolle_f32": [_ptr, _ptr, _i64, _i64, _i64, _f64, _f64, _int, _f64, _ptr, _ptr, _ptr],
     "deqsci_relu_mask_pack_f32": [_ptr, _ptr, _i64, _ptr],
@@ -79,7 +80,7 @@ SIGNATURES = {
 }
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
-                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes")
+                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -117,6 +118,8 @@ def load():
     lib.deqsci_gram_ref_bytes.argtypes = [_i64, _i64]
     lib.deqsci_ssim_workspace_bytes.restype = _i64
     lib.deqsci_ssim_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _int]
+    lib.deqsci_sqerr_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_sqerr_workspace_bytes.argtypes = [_i64, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -1326,6 +1329,41 @@ def ssim_frames(x, y, layout=LAYOUT_HWB, window=11, mode="same", clamp_x=False):
     with _dev(x):
         _check(load().deqsci_ssim_f32(_p(x, "x"), _p(y, "y"), out.data_ptr(), M, H, W, B, layout, window, SSIM_MODES[mode],
                                       1 if clamp_x else 0, ws.data_ptr(), _stream()), "ssim")
+    return out
+
+
+# ----------------------------------------------------------------------------- per-f-call squared error (csrc/trace.hip)
+def sqerr_workspace(bsz, N, device):
+    """The caller-owned workspace of sqerr_rows for (bsz, N) rows (float64 words; no initialisation needed)."""
+    return torch.empty((max(int(load().deqsci_sqerr_workspace_bytes(bsz, N)) // 8, 1),), device=device, dtype=torch.float64)
+
+
+def sqerr_rows(x, gt, out=None, clamp_x=True, workspace=None):
+    """out[s] = sum_i (clamp(x[s, i]) - gt[s, i])^2: difference and square in fp32, the sum in float64 (harness.psnr's arithmetic before
+    its mean) -> (bsz,) float64 on the device.  x: (bsz, N) fp32 whose rows are dense but may lie x.stride(0) >= N elements apart (a slot of
+    the Anderson history, ws.F[:, slot]); gt: (bsz, N) fp32 contiguous.  clamp_x: x clamped to [0,1] on load.  out / workspace
+    (sqerr_workspace): given by a caller that must not allocate (the engine, inside a hipGraph capture); else from torch's allocator."""
+    if x.dim() != 2 or tuple(x.shape) != tuple(gt.shape):
+        raise DeqsciHipError(f"sqerr_rows: x {tuple(x.shape)} and gt {tuple(gt.shape)} must be the same 2-d shape")
+    for name, t in (("x", x), ("gt", gt)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise DeqsciHipError(f"sqerr_rows: {name} must be a float32 tensor on a HIP device; deqsci_amd has no CPU path")
+    bsz, N = x.shape
+    if not gt.is_contiguous() or (N > 1 and x.stride(1) != 1) or (bsz > 1 and x.stride(0) < N):
+        raise DeqsciHipError("sqerr_rows: gt must be contiguous and the rows of x dense")
+    if out is None:
+        out = torch.empty((bsz,), device=x.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or out.numel() != bsz or not out.is_contiguous() or out.device != x.device:
+        raise DeqsciHipError(f"sqerr_rows: out must be {bsz} contiguous float64 values on x's device")
+    if bsz == 0 or N == 0:
+        return out.zero_()
+    if workspace is None:
+        workspace = sqerr_workspace(bsz, N, x.device)
+    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < load().deqsci_sqerr_workspace_bytes(bsz, N) or workspace.device != x.device:
+        raise DeqsciHipError("sqerr_rows: workspace too small (sqerr_workspace(bsz, N, device))")
+    with _dev(x):
+        _check(load().deqsci_sqerr_rows_f32(x.data_ptr(), gt.data_ptr(), out.data_ptr(), bsz, N, x.stride(0) if bsz > 1 else max(x.stride(0), N),
+                                            1 if clamp_x else 0, workspace.data_ptr(), _stream()), "sqerr_rows")
     return out
 
 

@@ -11,6 +11,9 @@ measurements sharded over them (deqsci_amd.distributed), rank 0 prints and write
 `--ssim` (also this build's) adds the per-clip SSIM and a 'Total Average SSIM' line (window 11, `--ssim_mode same|valid`).
 `--init_point gaptv` starts the DEQ from GAP-TV (the reference's commented-out initial point) instead of At(y, Phi); `--baseline gaptv`
 reconstructs by GAP-TV alone, with no DEQ (both this build's; deqsci_amd.gaptv).
+`--snapshots 10,30,100` (this build's) also scores the clips at those iteration horizons out of the SAME run (one extra f-call each) and
+prints one '[and_maxiters K] Total Average PSNR' line per horizon after the usual lines; `--trace FILE.json` writes the PSNR and the
+residual of every f-call, per clip and measurement.
 """
 import argparse
 import os
@@ -20,7 +23,7 @@ import time
 import torch
 
 from . import checkpoint, distributed
-from .harness import SCITestDataset, evaluate, png_payloads, write_png
+from .harness import SCITestDataset, evaluate, png_payloads, print_horizons, trace_document, write_png
 from .networks import DnCNN, FFDNet
 from .operators import A_torch_, At_torch_
 from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp
@@ -47,6 +50,25 @@ def build_pipeline(denoiser, loadpath=None, and_maxiters=100, and_m=5, and_beta=
     solver = solver.to(device)
     deq = DEQFixedPoint(solver, andersonexp, m=and_m, beta=and_beta, lam=1e-2, max_iter=and_maxiters, tol=1e-5)
     return solver, deq
+
+
+def parse_snapshots(text):
+    """'10,30,100' -> (10, 30, 100) (argparse type of --snapshots; the engine checks the values against --and_maxiters)."""
+    try:
+        out = tuple(int(v) for v in str(text).split(',') if v.strip() != '')
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--snapshots wants comma-separated iteration counts, got {text!r}")
+    if not out:
+        raise argparse.ArgumentTypeError("--snapshots wants at least one iteration count")
+    return out
+
+
+def write_trace(path, results):
+    """--trace FILE.json: {clip: {measurement: {"psnr": [...], "res": [...]}}}, one value per issued f-call of the iteration."""
+    import json
+    with open(path, "w") as fh:
+        json.dump(trace_document(results), fh)
+        fh.write("\n")
 
 
 def parser():
@@ -84,6 +106,11 @@ def parser():
     p.add_argument('--baseline', default=None, choices=['gaptv'],
                    help="(this build) reconstruct by the classical baseline alone, no DEQ: gaptv = GAP-TV (40 iterations, step 1, TV weight "
                         "0.3).  The same clip lines, totals, PNGs and --ssim handling")
+    p.add_argument('--snapshots', default=None, type=parse_snapshots, metavar='K1,K2,..',
+                   help="(this build) also score the clips at these iteration horizons (each smaller than --and_maxiters), out of the same run: "
+                        "one '[and_maxiters K] Total Average PSNR' line per horizon after the usual lines (with SSIM under --ssim)")
+    p.add_argument('--trace', default=None, metavar='FILE.json',
+                   help="(this build) write the PSNR and the residual of every f-call, per clip and measurement, to FILE.json")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
     ignored.add_argument('--n_epochs', default=80)
     ignored.add_argument('--batch_size', type=int, default=1)
@@ -112,6 +139,8 @@ def run(args):
             opts["anderson_arith"] = args.anderson_arith
         if opts:
             deq.engine_options = opts
+    if args.baseline is not None and (args.snapshots is not None or args.trace):
+        sys.exit("--snapshots / --trace are the DEQ iteration's: not available with --baseline")
     if rank == 0:
         if deq is not None:
             print('loaded dict!')
@@ -130,12 +159,17 @@ def run(args):
     avg, results = evaluate(deq, SCITestDataset(args.testpath), device=dev, on_clip=on_clip,
                             batch="all" if args.batch_measurements == "all" else bool(args.batch_measurements or world > 1),
                             ssim=ssim, ssim_mode=args.ssim_mode or "same", init=args.init_point,
-                            method="deq" if args.baseline is None else args.baseline)
+                            method="deq" if args.baseline is None else args.baseline,
+                            **({"snapshots": args.snapshots, "trace": bool(args.trace)} if (args.snapshots is not None or args.trace) else {}))
     dt = time.time() - t0
     if rank == 0:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
         if ssim:
             print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
+        if args.snapshots is not None:
+            print_horizons(results)
+        if args.trace:
+            write_trace(args.trace, results)
         for path, img in images.items():
             write_png(path, img)
         n = sum(r.frames for r in results)
@@ -152,6 +186,12 @@ def main(argv=None):
         sys.exit("deqsci_amd is the inference hot path only: --inference False (training) is out of scope")
     if args.denoiser not in SHIPPED:
         raise NotImplementedError('unknown denoiser!')
+    if args.snapshots is not None:
+        from .engine import check_snapshots
+        try:
+            check_snapshots(args.snapshots, args.and_maxiters, "anderson")
+        except ValueError as e:
+            sys.exit(f"--snapshots: {e}")
     ids = [int(v) for v in str(args.gpu_ids).split(',') if v != '']
     if distributed.relaunch_needed(len(ids)):
         # the launcher parent never calls into HIP (not even to count devices): visibility variables / KFD topology only

@@ -62,6 +62,32 @@ def _exhaust(gen):
             return done.value
 
 
+def check_snapshots(snapshots, max_iter, iterator="anderson"):
+    """The `snapshots=` request of DEQSCIEngine.reconstruct as a tuple of ints (None: no snapshot), or ValueError: every entry an
+    integer iteration count, strictly increasing, smaller than max_iter, and one the iterator can stop at (Anderson: at least 3 - a
+    run with max_iter <= 2 raises in the reference; Picard: at least 1)."""
+    if snapshots is None:
+        return None
+    if isinstance(snapshots, (str, bytes)) or not hasattr(snapshots, "__iter__"):
+        raise ValueError(f"snapshots={snapshots!r}: expected a sequence of iteration counts")
+    out = []
+    for k in snapshots:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError(f"snapshots={snapshots!r}: {k!r} is not an integer iteration count")
+        out.append(int(k))
+    if not out:
+        return None
+    lo = 3 if iterator == "anderson" else 1
+    for a, b in zip(out, out[1:]):
+        if b <= a:
+            raise ValueError(f"snapshots={tuple(out)}: must be strictly increasing")
+    if out[0] < lo:
+        raise ValueError(f"snapshots={tuple(out)}: the smallest horizon of the {iterator} iteration is {lo}")
+    if out[-1] >= max_iter:
+        raise ValueError(f"snapshots={tuple(out)}: every horizon must be smaller than max_iter={max_iter} (the run's own result is the last one)")
+    return tuple(out)
+
+
 def _fold_bn(conv_w, bn):
     scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
     return (conv_w * scale.view(-1, 1, 1, 1)).contiguous(), (bn.bias - bn.running_mean * scale).contiguous()
@@ -596,11 +622,12 @@ class DEQSCIEngine:
         self._stack_wanted, self._stack_off_for, self.stack_timeouts_total = bool(stack), 0, 0
         self._ws = {}
         self._graph = None
+        self._snaps, self._trace, self._gt = None, False, None      # the options of the reconstruct() call in progress
         self.last_info = None
 
     # ------------------------------------------------------------------ buffers
     def _workspace(self, bsz, H, W, B, device):
-        key = (bsz, H, W, B, str(device), self.iterator, self.m, self.max_iter)
+        key = (bsz, H, W, B, str(device), self.iterator, self.m, self.max_iter, self._snaps, self._trace and self._gt is not None)
         ws = self._ws.get(key)
         if ws is None:
             m = self.m if self.iterator == "anderson" else 1
@@ -609,6 +636,14 @@ class DEQSCIEngine:
             ws.xbuf = [torch.empty((bsz, B, H, W), device=device, dtype=torch.float32) for _ in range(2)]
             ws.z1 = torch.empty((bsz, B, H, W), device=device, dtype=torch.float32)
             ws.host_res = torch.full((rows, 1 + bsz), float('inf'), dtype=torch.float32).pin_memory()   # unfinished copy != converged
+            # snapshots: one output buffer per horizon (a replayed hipGraph writes them in place; they are cloned out as rec is)
+            ws.snap = {K: torch.empty((bsz, H, W, B), device=device, dtype=torch.float32) for K in (self._snaps or ())}
+            ws.sq = ws.sq_ws = ws.gt = None
+            if self._trace and self._gt is not None:
+                # trace with a ground truth: sum of squared errors of every f-call's output, row = the f-call's residual row
+                ws.sq = torch.zeros((rows, bsz), device=device, dtype=torch.float64)
+                ws.sq_ws = _hip.sqerr_workspace(bsz, H * W * B, device)
+                ws.gt = torch.empty((bsz, B, H, W), device=device, dtype=torch.float32)
             self._ws = {key: ws}          # one live shape at a time: history is bsz*m*N*8 bytes
         return ws
 
@@ -633,6 +668,24 @@ class DEQSCIEngine:
         else:
             _hip.residual_store(ws, out, None, x_in, slot, n_filled, x_next, ref=ref)
         _hip.anderson_solve(ws, slot, n_filled, n_solve, self.lam, eps, res_row, ref=ref)    # (+ lam I and the fp32 LU of :178-180 in K6)
+        if ws.sq is not None:
+            # trace: |clamp(F_k) - gt|^2 per measurement from the history slot K4 just wrote (csrc/trace.hip), into row k of the table
+            _hip.sqerr_rows(ws.F[:, slot], ws.gt.view(ws.bsz, ws.N), out=ws.sq[res_row], clamp_x=True, workspace=ws.sq_ws)
+
+    def _snapshot_steps(self, ws, x_last, call, phi, y, ps, K):
+        """(generator) the result of the run with max_iter=K, formed as _enqueue_steps forms the final z = f(z*): f(x_last) as f-call
+        number `call`, into ws.snap[K].  Advances nothing the main run reads later: sigma is indexed by `call`, the activation ranges
+        are those of f-call 0, ws.z1 is rewritten by the next iteration, the history is untouched."""
+        stale = self.den._stale
+        _hip.gap_update(x_last, phi, y, ps, LAYOUT_BHW, out=ws.z1)
+        out, is_noise = yield from self._denoise_steps(ws.z1, call)
+        out = _hip.f32c(out)
+        if is_noise:
+            _hip.residual_out(ws.z1, out, LAYOUT_HWB, out=ws.snap[K])
+        else:
+            _hip.transpose(out, LAYOUT_HWB, out=ws.snap[K])
+        if stale:                                             # (conv64_f22_calls: the ranges are measured by the main run's own first split-fp16 call)
+            self.den._stale = True
 
     def _poll(self, ws, row):
         ws.host_res[row].copy_(ws.res[row], non_blocking=True)
@@ -642,11 +695,36 @@ class DEQSCIEngine:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def reconstruct(self, y, Phi, Phi_sum=None, initial_point=None):
+    def reconstruct(self, y, Phi, Phi_sum=None, initial_point=None, *, snapshots=None, trace=False, gt=None):
         """y (bsz,H,W), Phi (bsz|1,H,W,B) or (H,W,B) fp32 on the GPU -> reconstruction (bsz,H,W,B).
-        `self.last_info` holds res (whole batch), per-sample res, iterations and f-call count."""
+        `self.last_info` holds res (whole batch), per-sample res, iterations and f-call count.
+
+        snapshots=(K1, K2, ...): also the reconstruction at those iteration horizons (strictly increasing, each smaller than max_iter)
+        from this ONE run, one extra f-call each: last_info["snapshots"][K] = {"rec" (bsz,H,W,B), "res", "res_per_sample"} is what an
+        engine with max_iter=K returns and reports, bit for bit (if the tolerance test stops the run before K, the run's own result).
+        trace=True: last_info["trace"] = {"res" (n_calls,), "res_per_sample" (n_calls,bsz), "psnr" (n_calls,bsz) or None}, float64 numpy:
+        the residual rows of the f-calls of the iteration (f-call k = row k; the closing z = f(z*) and the snapshots' f-calls have no
+        row), copied back once at the end; with gt= (the ground truth, (bsz,H,W,B) on the device) also the PSNR of every f-call's output
+        against it, per measurement, by harness.psnr's definition (csrc/trace.hip, no host sync).  Both are None when not asked for, and
+        neither changes the result.  A call with snapshots or a trace runs ungrouped (groups=2 is ignored for it).  An invalid request
+        raises ValueError before anything is launched."""
+        snaps = check_snapshots(snapshots, self.max_iter, self.iterator)
+        if gt is not None and not trace:
+            raise ValueError("gt= is the ground truth of the trace's PSNR: pass trace=True with it")
+        if gt is not None and not (isinstance(gt, torch.Tensor) and gt.dim() == 4 and isinstance(y, torch.Tensor) and gt.shape[0] == y.shape[0]
+                                   and tuple(gt.shape[1:3]) == tuple(y.shape[1:3]) and gt.shape[3] == Phi.shape[-1]):
+            raise ValueError(f"gt must be a (bsz,H,W,B) tensor matching y {tuple(getattr(y, 'shape', ()))} and Phi {tuple(getattr(Phi, 'shape', ()))}")
         if not (isinstance(y, torch.Tensor) and y.is_cuda):
             raise _hip.DeqsciHipError("DEQSCIEngine.reconstruct needs GPU tensors; there is no CPU path")
+        if gt is not None and gt.device != y.device:
+            raise ValueError(f"gt is on {gt.device}, y on {y.device}")
+        self._snaps, self._trace, self._gt = snaps, bool(trace), (None if gt is None else _hip.f32c(gt))
+        try:
+            return self._reconstruct_checked(y, Phi, Phi_sum, initial_point)
+        finally:
+            self._snaps, self._trace, self._gt = None, False, None
+
+    def _reconstruct_checked(self, y, Phi, Phi_sum, initial_point):
         with torch.cuda.device(y.device):          # events, stream sync and launches all on y's device
             if self._stack_off_for > 0:            # (a stack launch timed out a while ago: per-layer launches for STACK_RETRY_CALLS calls, then try again)
                 self._stack_off_for -= 1
@@ -683,6 +761,7 @@ class DEQSCIEngine:
                 # about) is redone on the fp32 MFMA kernels - THIS call only (eagerly; a captured hipGraph and the policy of later,
                 # unrelated inputs are left alone; every rank of a sharded job decides for its own call) - and last_info says so.  A run
                 # that diverges by itself comes back non-finite again and is returned as it is.
+                first = self.last_info.get("snapshots")
                 saved = (self.conv64_policy, self.den.conv64, self.use_graph)
                 self.conv64_policy = self.den.conv64 = self.den._policy = "fast32"
                 self.use_graph = False
@@ -692,6 +771,13 @@ class DEQSCIEngine:
                     self.conv64_policy, self.den.conv64, self.use_graph = saved
                     self.den._policy = saved[1]
                 fallback = "fast32"
+                if first:
+                    # a run with max_iter=K is redone on fp32 only if ITS residual is not finite: a horizon whose residual was still finite
+                    # in the first pass keeps that pass's snapshot (what the separate run returns), the others come from the redo
+                    snaps = self.last_info["snapshots"]
+                    for K, v in first.items():
+                        if math.isfinite(v["res"]):
+                            snaps[K] = v
             self.last_info["conv64_fallback"] = fallback
             # what the first f-call measured: max |activation| in front of every layer of the denoiser's stack, here the maximum over the
             # batch's images (the kernels use one range per image: den.ranges; 0 where no split-fp16 layer ran)
@@ -726,7 +812,8 @@ class DEQSCIEngine:
             initial_point = _hip.f32c(initial_point)
         graph = self.use_graph if self.use_graph != "auto" else bsz * H * W <= self.GRAPH_AUTO_PIXELS
         self._grouped = False
-        plan = None if graph else self._group_plan(bsz, H, W, B, y.device)
+        extras = self._snaps is not None or self._trace
+        plan = None if (graph or extras) else self._group_plan(bsz, H, W, B, y.device)
         if plan is not None:
             rec = self._reconstruct_grouped(plan, y, Phi4, Phi_sum, initial_point)
             if rec is not None:
@@ -737,13 +824,41 @@ class DEQSCIEngine:
             rec = self._replay(ws, y, Phi4, Phi_sum, initial_point)
             if rec is not None:
                 return rec
-        rec, call, last, res_row = self._enqueue(ws, y, Phi4, Phi_sum, initial_point, self.poll_residual)
+        rec, call, last, res_row = self._enqueue(ws, y, Phi4, Phi_sum, initial_point, self.poll_residual, self._gt)
+        if extras:
+            ws.host_res.copy_(ws.res, non_blocking=True)      # the whole residual table, once
         torch.cuda.current_stream().synchronize()
         r = ws.host_res[res_row]
         self.last_info = {"res": float(r[0]), "res_per_sample": r[1:].tolist(), "iterations": last,
                           "f_calls": call, "iterator": self.iterator, "graph": False}
+        self._add_extras(ws, rec, last, res_row)
         self._warn_if_not_finite()
         return rec
+
+    def _add_extras(self, ws, rec, last, res_row):
+        """last_info["snapshots"] / ["trace"] of the call in progress from the workspace (the stream is synchronised and ws.host_res holds
+        the whole table when either was asked for).  The f-calls behind the snapshots count in "f_calls"."""
+        info = self.last_info
+        info["snapshots"] = info["trace"] = None
+        if self._snaps is not None:
+            snaps = {}
+            for K in self._snaps:
+                k_last = K - 1                                # `last` of the run with max_iter=K (both iterators)
+                if last < k_last:                             # the tolerance test stopped the run first: that run stops there too
+                    snaps[K] = {"rec": rec, "res": info["res"], "res_per_sample": list(info["res_per_sample"])}
+                    continue
+                r = ws.host_res[k_last if self.iterator == "anderson" else K]
+                snaps[K] = {"rec": ws.snap[K].clone(), "res": float(r[0]), "res_per_sample": r[1:].tolist()}
+                info["f_calls"] += 1
+            info["snapshots"] = snaps
+        if self._trace:
+            n = res_row + 1
+            table = ws.host_res[:n].numpy().astype(np.float64)
+            psnr = None
+            if ws.sq is not None:
+                with np.errstate(divide="ignore"):
+                    psnr = 10.0 * np.log10(1.0 / (ws.sq[:n].cpu().numpy() / float(ws.N)))
+            info["trace"] = {"res": table[:, 0].copy(), "res_per_sample": table[:, 1:].copy(), "psnr": psnr}
 
     # ------------------------------------------------------------------ two half batches on two streams
     def _group_plan(self, bsz, H, W, B, device):
@@ -858,6 +973,7 @@ class DEQSCIEngine:
         self.den.stack_launches += max(k.den.stack_launches for k in kids)
         self.last_info = {"res": res, "res_per_sample": [v for ws in wss for v in ws.host_res[res_row, 1:].tolist()], "iterations": last,
                           "f_calls": call, "iterator": self.iterator, "graph": False, "groups": [list(p) for p in plan]}
+        self._add_extras(None, rec, last, res_row)            # (never asked for on this path: both keys None)
         self._warn_if_not_finite()
         return rec
 
@@ -873,15 +989,17 @@ class DEQSCIEngine:
             warnings.warn("DEQSCIEngine: the reconstruction's residual is not finite.  If the iteration itself is not diverging, an activation of "
                           f"the denoiser has left fp16's range inside the split-fp16 64->64 layers ({how}): " + what + ".", RuntimeWarning, stacklevel=4)
 
-    def _enqueue(self, ws, y, Phi4, Phi_sum, initial_point, poll):
+    def _enqueue(self, ws, y, Phi4, Phi_sum, initial_point, poll, gt=None):
         """Every launch of one reconstruction on the current stream.  poll: True = lagged residual read-back with early stop,
         False = one read-back at the end, None = no host traffic at all (what a hipGraph capture records)."""
-        return _exhaust(self._enqueue_steps(ws, y, Phi4, Phi_sum, initial_point, poll))
+        return _exhaust(self._enqueue_steps(ws, y, Phi4, Phi_sum, initial_point, poll, gt))
 
-    def _enqueue_steps(self, ws, y, Phi4, Phi_sum, initial_point, poll):
+    def _enqueue_steps(self, ws, y, Phi4, Phi_sum, initial_point, poll, gt=None):
         """_enqueue as a generator that yields behind every f-call (a grouped reconstruction issues the f-calls of its halves alternately);
-        returns what _enqueue returns."""
+        returns what _enqueue returns.  gt: the trace's ground truth (bsz,H,W,B), transposed once to the loop's planar order."""
         self._eager = poll is not None
+        if ws.gt is not None:
+            _hip.transpose(gt, LAYOUT_BHW, out=ws.gt)
         phi = _hip.transpose(Phi4, LAYOUT_BHW)
         ps = Phi_sum if Phi_sum is not None else _hip.phi_sum(phi, LAYOUT_BHW)
         if initial_point is None:
@@ -912,7 +1030,7 @@ class DEQSCIEngine:
         """-> reconstruction, or None when this call has to take the eager path (first call of a shape: it warms every
         kernel up; or the tolerance test fired inside the replayed run)."""
         key = (tuple(y.shape), tuple(Phi4.shape), Phi_sum is not None, initial_point is not None, self.den._wkey, self.extra_call,
-               None if self.den.sigma_table is None else self.den.sigma_table.data_ptr())
+               None if self.den.sigma_table is None else self.den.sigma_table.data_ptr(), self._snaps, self._trace and self._gt is not None)
         g = self._graph
         if g is None or g["key"] != key or g["ws"] is not ws:
             # (the graph holds the workspace it was captured on: its nodes carry that workspace's raw pointers)
@@ -922,11 +1040,12 @@ class DEQSCIEngine:
             g["y"], g["Phi4"] = y.clone(), Phi4.clone()
             g["ps"] = None if Phi_sum is None else Phi_sum.clone()
             g["x0"] = None if initial_point is None else initial_point.clone()
+            g["gt"] = None if ws.gt is None else self._gt.clone()
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             c0 = self.den.stack_launches
             with torch.cuda.graph(graph):
-                g["rec"], g["call"], g["last"], g["res_row"] = self._enqueue(ws, g["y"], g["Phi4"], g["ps"], g["x0"], None)
+                g["rec"], g["call"], g["last"], g["res_row"] = self._enqueue(ws, g["y"], g["Phi4"], g["ps"], g["x0"], None, g["gt"])
             g["graph"], g["stack_n"] = graph, self.den.stack_launches - c0
         else:
             self.den.stack_launches += g["stack_n"]
@@ -936,6 +1055,8 @@ class DEQSCIEngine:
                 g["ps"].copy_(Phi_sum)
             if initial_point is not None:
                 g["x0"].copy_(initial_point)
+            if g["gt"] is not None:
+                g["gt"].copy_(self._gt)
         g["graph"].replay()
         rec = g["rec"].clone()
         ws.host_res.copy_(ws.res, non_blocking=True)          # the whole residual table, once
@@ -947,6 +1068,7 @@ class DEQSCIEngine:
         r = ws.host_res[g["res_row"]]
         self.last_info = {"res": float(r[0]), "res_per_sample": r[1:].tolist(), "iterations": g["last"],
                           "f_calls": g["call"], "iterator": self.iterator, "graph": True}
+        self._add_extras(ws, rec, g["last"], g["res_row"])
         self._warn_if_not_finite()
         return rec
 
@@ -974,6 +1096,9 @@ class DEQSCIEngine:
             yield from self._store_solve_steps(ws, x, k, k % m, nf, nf, None, 1e-5, k)
             last = k
             yield "fcall"
+            if k + 1 in ws.snap:                              # X_k is overwritten two iterations on: the horizon k + 1 result now, as f-call k + 1
+                yield from self._snapshot_steps(ws, x, k + 1, phi, y, ps, k + 1)
+                yield "fcall"
             if poll:
                 ev = self._poll(ws, k)
                 if prev_ev is not None:
@@ -1003,6 +1128,9 @@ class DEQSCIEngine:
             yield from self._store_solve_steps(ws, x, k + 1, 0, 1, 0, nxt, 1e-7, k + 1)
             last = k
             yield "fcall"
+            if k + 1 in ws.snap:                              # the run with max_iter = k + 1 returns f(nxt) as f-call k + 2
+                yield from self._snapshot_steps(ws, nxt, k + 2, phi, y, ps, k + 1)
+                yield "fcall"
             if poll:
                 ev = self._poll(ws, k + 1)
                 if prev_ev is not None:

@@ -131,6 +131,9 @@ class ClipResult:
     seconds: float = 0.0
     info: dict = field(default_factory=dict)
     ssim: list | None = None          # per measurement, the mean SSIM over its B frames (only when asked for)
+    # (only when asked for) {K: {"psnr": [...], "res": [...], "ssim": [...] or None, "rec": (M,H,W,B)}}: the run with and_maxiters=K, scored as above
+    snapshots: dict | None = None
+    trace: dict | None = None         # (only when asked for) {"psnr": (M, n_calls), "res": (M, n_calls)}: every f-call of the iteration
 
     @property
     def mean_psnr(self):
@@ -169,6 +172,80 @@ def _residuals(deep_eq_module, n):
     return [r] * n, (info or {})
 
 
+def _gt_batch(gt, ids, B, device):
+    """The ground truth of the measurements ids as an (M,H,W,B) fp32 tensor on the device (what clip_psnr scores against)."""
+    return torch.stack([torch.as_tensor(gt[..., B * m:B * (m + 1)]) for m in ids]).to(device, torch.float32).contiguous()
+
+
+def _rows(rows):
+    """Per-measurement rows -> an (M, n_calls) float64 array (a list of arrays if early stops left them of different lengths)."""
+    rows = [np.asarray(r, dtype=np.float64) for r in rows]
+    return np.stack(rows) if rows and all(r.shape == rows[0].shape for r in rows) else rows
+
+
+class _Horizons:
+    """The snapshots= / trace= options around the forward calls of one harness batch: sets them on the DEQ module for each call
+    (DEQFixedPoint.snapshots / .trace / .trace_gt), collects what the calls leave (last_snapshots / last_trace), and gathers the
+    per-measurement results over the process group as the reconstructions and the PSNR scalars are gathered."""
+
+    def __init__(self, module, snapshots, trace, method):
+        self.module, self.snapshots, self.trace = module, (None if snapshots is None else tuple(snapshots)), bool(trace)
+        self.on = self.snapshots is not None or self.trace
+        if self.on and method != "deq":
+            raise ValueError("snapshots / trace are the DEQ iteration's: not available with method='gaptv'")
+        if self.on and not hasattr(module, "last_snapshots"):
+            raise NotImplementedError(f"snapshots / trace need this package's DEQFixedPoint, not {type(module).__name__}")
+        self.recs = {K: [] for K in (self.snapshots or ())}
+        self.res = {K: [] for K in (self.snapshots or ())}
+        self.t_psnr, self.t_res = [], []
+
+    def forward(self, call, gt_part):
+        """call() = the module's forward for one batch whose ground truth is gt_part (M_part,H,W,B) on the device."""
+        if not self.on:
+            return call()
+        mod = self.module
+        old = (mod.snapshots, mod.trace, mod.trace_gt)
+        mod.snapshots, mod.trace, mod.trace_gt = self.snapshots, self.trace, (gt_part if self.trace else None)
+        try:
+            rec = call()
+        finally:
+            mod.snapshots, mod.trace, mod.trace_gt = old
+        for K, v in (mod.last_snapshots or {}).items():
+            self.recs[K].append(v["rec"].detach())
+            self.res[K].extend(v["res_per_sample"])
+        if self.trace:
+            tr = mod.last_trace
+            self.t_psnr.extend(tr["psnr"][:, j] for j in range(tr["psnr"].shape[1]))
+            self.t_res.extend(tr["res_per_sample"][:, j] for j in range(tr["res_per_sample"].shape[1]))
+        return rec
+
+    def finish(self, y, Phi, group):
+        """-> ({K: {"rec" (M,H,W,B), "res" [M]}} or None, {"psnr" (M,n_calls), "res" (M,n_calls)} or None) over ALL measurements."""
+        snaps = trace = None
+        if self.snapshots is not None:
+            snaps = {}
+            for K in self.snapshots:
+                local = torch.cat(self.recs[K]) if self.recs[K] else None
+                rec = distributed.sharded_reconstruct(lambda a, b: local, y, Phi, group=group) if distributed._active(group) else local
+                snaps[K] = {"rec": rec, "res": distributed.gather_scalars(self.res[K], group=group)}
+        if self.trace:
+            trace = {"psnr": _rows(distributed.gather_scalars(self.t_psnr, group=group)),
+                     "res": _rows(distributed.gather_scalars(self.t_res, group=group))}
+        return snaps, trace
+
+
+def _scored(snaps, trace, lo, hi, gt, ids, ssim, ssim_mode):
+    """ClipResult.snapshots / .trace of the measurements [lo, hi) of a batch: every snapshot scored exactly as the final result is."""
+    out = None
+    if snaps is not None:
+        out = {}
+        for K, v in snaps.items():
+            r = v["rec"][lo:hi]
+            out[K] = {"psnr": clip_psnr(r, gt, ids), "res": list(v["res"][lo:hi]),
+                      "ssim": clip_ssim(r, gt, ids, ssim_mode) if ssim else None, "rec": r}
+    return out, (None if trace is None else {k: v[lo:hi] for k, v in trace.items()})
+
+
 def _start(init, y, Phi, Phi_sum):
     """The DEQ's starting point: "At" = initial_point (the reference's), "gaptv" = initial_point_gaptv (its commented-out one)."""
     with torch.no_grad():
@@ -179,6 +256,13 @@ def _start(init, y, Phi, Phi_sum):
     raise ValueError(f"init must be 'At' or 'gaptv', got {init!r}")
 
 
+def _shard_start(M, group):
+    """Index of the first of M measurements that this rank reconstructs (distributed.sharded_reconstruct); 0 without a process group."""
+    if not distributed._active(group):
+        return 0
+    return distributed.shard_bounds(M, torch.distributed.get_world_size(group), torch.distributed.get_rank(group))[0]
+
+
 def _check_method(method, init):
     if method not in ("deq", "gaptv"):
         raise ValueError(f"method must be 'deq' or 'gaptv', got {method!r}")
@@ -186,12 +270,15 @@ def _check_method(method, init):
         raise ValueError(f"init must be 'At' or 'gaptv', got {init!r}")
 
 
-def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same", init="At", method="deq"):
+def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same", init="At", method="deq",
+                     snapshots=None, trace=False):
     """All scored measurements of one clip through `deep_eq_module.forward(y, Phi, Phi_sum, initial_point=, train_flag=False)`.
     batch=True: one call with y (M,H,W) and the shared mask (1,H,W,B); batch=False: M calls of batch 1 (the reference's
     schedule).  With a process group the measurements are sharded over its ranks and all-gathered.  ssim=True: also the
     per-measurement SSIM (clip_ssim, after the timed part).  init: the DEQ's start, "At" (default) or "gaptv" (GAP-TV, timed with the
-    reconstruction).  method="gaptv": GAP-TV alone, no DEQ (deep_eq_module is not used; res is None)."""
+    reconstruction).  method="gaptv": GAP-TV alone, no DEQ (deep_eq_module is not used; res is None).
+    snapshots=(K1, ...): ClipResult.snapshots[K] = the clip as a run with and_maxiters=K would score it, from the same run
+    (DEQSCIEngine.reconstruct); trace=True: ClipResult.trace = PSNR and residual of every f-call, per measurement."""
     import time
     clip = as_clip(clip)
     Phi = clip['mask'].to(device)[None].contiguous()                  # (1,H,W,B)
@@ -200,12 +287,15 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     y = clip['meas'].to(device).permute(2, 0, 1)[ids].contiguous()    # (M,H,W)
     Phi_sum = operators.phi_sum(Phi)
     _check_method(method, init)
+    hz = _Horizons(deep_eq_module, snapshots, trace, method)
+    gts = _gt_batch(clip['gt'], ids, B, device) if hz.trace else None
 
-    def run(y_part, Phi_part):
+    def run(y_part, Phi_part, lo=0):
         if method == "gaptv":
             return _start("gaptv", y_part, Phi_part, Phi_sum), [None] * y_part.shape[0]
         x0 = _start(init, y_part, Phi_part, Phi_sum)
-        rec = deep_eq_module.forward(y_part, Phi_part, Phi_sum, initial_point=x0, train_flag=False)
+        rec = hz.forward(lambda: deep_eq_module.forward(y_part, Phi_part, Phi_sum, initial_point=x0, train_flag=False),
+                         None if gts is None else gts[lo:lo + y_part.shape[0]])
         res, _ = _residuals(deep_eq_module, y_part.shape[0])
         return rec.detach(), res
 
@@ -213,7 +303,7 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     res = []
     if batch:
         def run_collect(y_part, Phi_part):
-            rec, r = run(y_part, Phi_part)
+            rec, r = run(y_part, Phi_part, _shard_start(y.shape[0], group))
             res.extend(r)
             return rec
         rec = distributed.sharded_reconstruct(run_collect, y, Phi, group=group)
@@ -221,7 +311,7 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     else:
         parts = []
         for i in range(len(ids)):
-            r, rr = run(y[i:i + 1], Phi)
+            r, rr = run(y[i:i + 1], Phi, i)
             parts.append(r)
             res.extend(rr)
         rec = torch.cat(parts)
@@ -229,18 +319,20 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
         torch.cuda.synchronize(rec.device)
     dt = time.perf_counter() - t0
     ps = clip_psnr(rec, clip['gt'], ids)
+    snaps, tr = _scored(*hz.finish(y, Phi, group if batch else None), 0, len(ids), clip['gt'], ids, ssim, ssim_mode)
     return ClipResult(name=clip['file'], rec=rec, psnr=ps, res=res, frames=B * len(ids), seconds=dt,
                       info={"measurements": ids, "batched": bool(batch)},
-                      ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None)
+                      ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None, snapshots=snaps, trace=tr)
 
 
-def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same", init="At", method="deq"):
+def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same", init="At", method="deq",
+                               snapshots=None, trace=False):
     """The scored measurements of SEVERAL clips of one frame size as ONE engine batch, every measurement with its own clip's mask
     ((M,H,W,B) masks: nothing couples the measurements of a batch - alpha, residual, the ranges of the split-fp16 activations are all per
     measurement - so a measurement's reconstruction is the one it gets in any other batch, bit for bit).  What the reference's loop over
     clips and measurements (training/sci_equilibrium_training.py:157,171) becomes when the device wants eight measurements per call: the
     three shipped clips (1 + 1 + 6 measurements) are one call.  -> [ClipResult] in the clips' order; a clip's `seconds` is its share of
-    the call by frames.  ssim=True: also the per-measurement SSIM; init and method as in reconstruct_clip."""
+    the call by frames.  ssim=True: also the per-measurement SSIM; init, method, snapshots and trace as in reconstruct_clip."""
     import time
     clips = [as_clip(c) for c in clips]
     ids = [scored_measurements(c['file'], c['meas'].shape[-1]) for c in clips]
@@ -249,6 +341,8 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
     B = Phi.shape[-1]
     res = []
     _check_method(method, init)
+    hz = _Horizons(deep_eq_module, snapshots, trace, method)
+    gts = torch.cat([_gt_batch(c['gt'], i, B, device) for c, i in zip(clips, ids)]) if hz.trace else None
 
     def run(y_part, Phi_part):
         Ps = operators.phi_sum(Phi_part)
@@ -256,7 +350,9 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
             res.extend([None] * y_part.shape[0])
             return _start("gaptv", y_part, Phi_part, Ps)
         x0 = _start(init, y_part, Phi_part, Ps)
-        rec = deep_eq_module.forward(y_part, Phi_part, Ps, initial_point=x0, train_flag=False)
+        lo = _shard_start(y.shape[0], group)
+        rec = hz.forward(lambda: deep_eq_module.forward(y_part, Phi_part, Ps, initial_point=x0, train_flag=False),
+                         None if gts is None else gts[lo:lo + y_part.shape[0]])
         res.extend(_residuals(deep_eq_module, y_part.shape[0])[0])
         return rec.detach()
     t0 = time.perf_counter()
@@ -266,24 +362,30 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
         torch.cuda.synchronize(rec.device)
     dt = time.perf_counter() - t0
     out, a = [], 0
+    all_snaps, all_trace = hz.finish(y, Phi, group)
     for c, i in zip(clips, ids):
         r = rec[a:a + len(i)]
+        snaps, tr = _scored(all_snaps, all_trace, a, a + len(i), c['gt'], i, ssim, ssim_mode)
         out.append(ClipResult(name=c['file'], rec=r, psnr=clip_psnr(r, c['gt'], i), res=list(res[a:a + len(i)]), frames=B * len(i),
                               seconds=dt * len(i) / y.shape[0], info={"measurements": i, "batched": "all"},
-                              ssim=clip_ssim(r, c['gt'], i, ssim_mode) if ssim else None))
+                              ssim=clip_ssim(r, c['gt'], i, ssim_mode) if ssim else None, snapshots=snaps, trace=tr))
         a += len(i)
     return out
 
 
 def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same", init="At",
-             method="deq"):
+             method="deq", snapshots=None, trace=False):
     """-> (mean over clips of the clip's mean PSNR, [ClipResult]).  batch: False = one measurement per call (the reference's schedule),
     True = a clip's measurements per call, "all" = the measurements of consecutive clips of one frame size per call
     (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements).  ssim=True fills every ClipResult.ssim
     (window 11, ssim_mode "same" or "valid"); the mean over clips of the clip's mean SSIM is then sum(r.mean_ssim ...) / len(results).
-    init: the DEQ's start, "At" (default) or "gaptv"; method="gaptv": reconstruct by GAP-TV alone (deep_eq_module may be None)."""
+    init: the DEQ's start, "At" (default) or "gaptv"; method="gaptv": reconstruct by GAP-TV alone (deep_eq_module may be None).
+    snapshots=(K1, ...) fills every ClipResult.snapshots (the clip at and_maxiters=K, out of the same run), trace=True every
+    ClipResult.trace; `horizon_means(results)` is the mean over clips per horizon."""
     _check_method(method, init)
     kw = dict(ssim=ssim, ssim_mode=ssim_mode, init=init, method=method)
+    if snapshots is not None or trace:
+        kw.update(snapshots=snapshots, trace=trace)
     results = []
     if batch == "all":
         pending = []
@@ -310,6 +412,35 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
     return sum(r.mean_psnr for r in results) / len(results), results
 
 
+def horizon_means(results):
+    """{K: (mean over clips of the clip's mean PSNR, the same of the SSIM or None)} of results evaluated with snapshots=."""
+    out = {}
+    for K in (getattr(results[0], "snapshots", None) or {}) if results else ():
+        ps = [sum(r.snapshots[K]["psnr"]) / len(r.snapshots[K]["psnr"]) for r in results]
+        ss = None if results[0].snapshots[K]["ssim"] is None else [sum(r.snapshots[K]["ssim"]) / len(r.snapshots[K]["ssim"]) for r in results]
+        out[K] = (sum(ps) / len(ps), None if ss is None else sum(ss) / len(ss))
+    return out
+
+
+def print_horizons(results):
+    """One '[and_maxiters K] Total Average PSNR' line per snapshot horizon (and the SSIM where it was scored)."""
+    for K, (p, s) in horizon_means(results).items():
+        if s is None:
+            print('---------------------------------', '[and_maxiters %d] Total Average PSNR: %.2f dB' % (K, p))
+        else:
+            print('---------------------------------', '[and_maxiters %d] Total Average PSNR: %.2f dB' % (K, p), '  SSIM: %.4f' % s)
+
+
+def trace_document(results):
+    """{clip: {measurement: {"psnr": [...], "res": [...]}}}: what `--trace FILE.json` writes, one value per issued f-call of the iteration."""
+    doc = {}
+    for r in results:
+        if r.trace is not None:
+            doc[r.name] = {str(m): {"psnr": [float(v) for v in r.trace["psnr"][i]], "res": [float(v) for v in r.trace["res"][i]]}
+                           for i, m in enumerate(r.info["measurements"])}
+    return doc
+
+
 def png_payloads(result, prefix=""):
     """{path: (H,W,1) float image} for every frame of a clip, named like the reference's export (:185-187):
     '<prefix><file>_reconstruction_<frame index within the scored frames>.png'."""
@@ -322,7 +453,7 @@ def png_payloads(result, prefix=""):
 
 
 def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, verbose=True, save_image=True,
-                    device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq"):
+                    device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq", snapshots=None, trace=False):
     """Adapter with the reference's signature (training/sci_equilibrium_training.py:152): returns
     (average PSNR, {png path: float image}); prints one line per clip and the total; writes the PNGs.
     Default = the reference's schedule, one measurement per call (:171-181); batch_measurements="all" hands the measurements of all clips of
@@ -330,7 +461,9 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
     measurements to the engine as one batch (faster; on the chaotic FFDNet + Anderson @180 clip a different - equally valid -
     realisation, because the FFDNet head kernel is chosen by launch size).  ssim=True (this build's addition): every record gains "ssim",
     every clip line '  SSIM: %.4f' and a 'Total Average SSIM' line follows the PSNR total; the return value is unchanged.  init="gaptv"
-    starts the DEQ from GAP-TV, method="gaptv" reconstructs by GAP-TV alone (both this build's additions, as in evaluate)."""
+    starts the DEQ from GAP-TV, method="gaptv" reconstructs by GAP-TV alone (both this build's additions, as in evaluate).
+    snapshots=(K1, ...) / trace=True (this build's, as in evaluate): every record gains "snapshots" ({K: {"psnr", "res", "ssim", "rec"}}) /
+    "trace" ({"psnr", "res"} per f-call), and one '[and_maxiters K] Total Average PSNR' line per horizon follows the totals."""
     images = {}
 
     def on_clip(r):
@@ -340,17 +473,23 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
                 records.append({"id": f"{r.name}:{m}", "psnr": r.psnr[i], "res": r.res[i], "rec": r.rec[i:i + 1].cpu()})
                 if ssim:
                     records[-1]["ssim"] = r.ssim[i]
+                if r.snapshots is not None:
+                    records[-1]["snapshots"] = {K: {"psnr": v["psnr"][i], "res": v["res"][i], "ssim": None if v["ssim"] is None else v["ssim"][i],
+                                                    "rec": v["rec"][i:i + 1].cpu()} for K, v in r.snapshots.items()}
+                if r.trace is not None:
+                    records[-1]["trace"] = {k: np.asarray(v[i]) for k, v in r.trace.items()}
         if verbose:
             if ssim:
                 print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
             else:
                 print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
     avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim, init=init,
-                            method=method)
+                            method=method, snapshots=snapshots, trace=trace)
     if verbose:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
         if ssim:
             print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
+        print_horizons(results)
     if save_image:
         for path, img in images.items():
             write_png(path, img)

@@ -213,6 +213,11 @@ class DEQFixedPoint(nn.Module):
         # how the backward hook of a taped forward forms J_f(z0)^T v: "autograd" (torch.autograd.grad through f0's graph, the reference's
         # way) or "device" (EquilibriumProxGradSCI.device_vjp: the HIP kernels, falling back to autograd where the denoiser has no device
         # VJP - deqsci_amd.vjp.eligibility).  last_backward_path: the path the last hook ran; backward_fallback_reason: why not "device".
+        # this build's additions, engine path only (DEQSCIEngine.reconstruct): snapshots = iteration horizons whose reconstructions come out
+        # of the same run (-> last_snapshots, {K: {"rec", "res", "res_per_sample"}}); trace = the residual (and, with trace_gt - the ground
+        # truth (bsz,H,W,B) on the device - the PSNR) of every f-call (-> last_trace).  forward's signature stays the reference's.
+        self.snapshots, self.trace, self.trace_gt = None, False, None
+        self.last_snapshots, self.last_trace = None, None
         self.implicit_backward = "autograd"
         self.last_backward_path = None
         self.backward_fallback_reason = None
@@ -266,7 +271,11 @@ class DEQFixedPoint(nn.Module):
         (`self.backward_res`).  `train_flag=False` skips the tape even when one could be recorded (the reference has that
         switch commented out, :277-279, and always records)."""
         init_point = torch.zeros_like(x) if initial_point is None else initial_point
+        extras = self.snapshots is not None or bool(self.trace) or self.trace_gt is not None
         if train_flag and torch.is_grad_enabled() and any(p.requires_grad for p in self.f.parameters()):
+            if extras:
+                raise NotImplementedError("snapshots / trace exist on the engine's inference path only: this is the taped training forward "
+                                          "(pass train_flag=False or run under torch.no_grad())")
             with torch.no_grad():
                 z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
             z = self.f(z, x, Phi, Phi_sum)                                     # re-engage the tape (:268)
@@ -288,15 +297,21 @@ class DEQFixedPoint(nn.Module):
             z.register_hook(backward_hook)
             return z
         eng = self._engine_for()
+        self.last_snapshots = self.last_trace = None
         if eng is not None:
-            z = eng.reconstruct(x, Phi, Phi_sum, initial_point=init_point)
+            z = eng.reconstruct(x, Phi, Phi_sum, initial_point=init_point, snapshots=self.snapshots, trace=bool(self.trace), gt=self.trace_gt)
             info = eng.last_info
+            self.last_snapshots, self.last_trace = info["snapshots"], info["trace"]
             if eng.iterator == "picard":
                 rows = eng._ws[next(iter(eng._ws))].host_res
                 self.forward_res = [float(v) for v in rows[1:info["iterations"] + 1, 0]]
             else:
                 self.forward_res = info["res"]
             return z
+        if extras:
+            raise NotImplementedError("snapshots / trace exist on the engine's path only, and this call takes the generic solver (use_engine is "
+                                      "off, f is not this package's EquilibriumProxGradSCI with A_torch_ / At_torch_, an unknown denoiser tag, "
+                                      "or a solver other than andersonexp / forward_iteration)")
         with torch.no_grad():
             z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
             z = self.f(z, x, Phi, Phi_sum)

@@ -361,6 +361,19 @@ int64_t deqsci_ssim_workspace_bytes(int64_t M, int64_t H, int64_t W, int64_t B, 
 int deqsci_ssim_f32(const float* x, const float* y, double* out, int64_t M, int64_t H, int64_t W, int64_t B,
                     int layout, int window, int valid, int clamp_x, void* workspace, deqsci_stream_t stream);
 
+/* Q1+Q2  per-sample squared error of an iterate against the ground truth, the numerator of the per-f-call PSNR trace
+ *     (harness.psnr's arithmetic): out[s] = sum_i (clamp(x[s,i]) - gt[s,i])^2, the difference and the square in fp32, the sum
+ *     in float64.  x: bsz rows of N fp32, row s at x + s * x_stride (x_stride >= N, in elements: the engine passes a slot of the
+ *     Anderson history, F_hist + slot * N with x_stride = m * N); gt (bsz, N) dense; both 4-byte aligned (rows that are both
+ *     16-byte aligned are read as float4, the others element by element, in the SAME summation order).  out (bsz) float64 and
+ *     workspace 8-byte aligned.  clamp_x != 0: x is clamped to [0,1] on load (NaN kept).  A NaN in a sample makes that sample's
+ *     value NaN, no other's.  Deterministic (two stages, fixed summation order, no atomics).  bsz = 0 or N = 0: nothing is
+ *     launched.  bsz <= 65535.  workspace = deqsci_sqerr_workspace_bytes(bsz, N) bytes (0 for invalid sizes), no
+ *     initialisation needed.  Two launches on `stream`; no allocation, no host synchronisation, graph-capturable. */
+size_t deqsci_sqerr_workspace_bytes(int64_t bsz, int64_t N);
+int deqsci_sqerr_rows_f32(const float* x, const float* gt, double* out, int64_t bsz, int64_t N, int64_t x_stride, int clamp_x,
+                          void* workspace, deqsci_stream_t stream);
+
 /* ---- GAP-TV: a classical baseline and the DEQ's other starting point (not on the DEQ's path) ----
  * T0-T3  the reference's GAP_TV_rec (utils/cg_utils.py:207-224) with scikit-image 0.17.2's denoise_tv_chambolle
  *     (multichannel, each frame a (1,H,W) channel: tau = 1/6), per measurement - a batch of bsz measurements gives what bsz calls
