@@ -74,13 +74,15 @@ SIGNATURES = {
     "deqsci_relu_mask_pack_f32": [_ptr, _ptr, _i64, _ptr],
     "deqsci_conv3x3_c64_winograd_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_conv3x3_c1_to_64_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
+    "deqsci_ffdnet_head_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
+    "deqsci_power_step_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
 }
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
-                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes")
+                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -120,6 +122,8 @@ def load():
     lib.deqsci_ssim_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64, _int]
     lib.deqsci_sqerr_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_sqerr_workspace_bytes.argtypes = [_i64, _i64]
+    lib.deqsci_power_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_power_workspace_bytes.argtypes = [_i64, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -1365,6 +1369,60 @@ def sqerr_rows(x, gt, out=None, clamp_x=True, workspace=None):
         _check(load().deqsci_sqerr_rows_f32(x.data_ptr(), gt.data_ptr(), out.data_ptr(), bsz, N, x.stride(0) if bsz > 1 else max(x.stride(0), N),
                                             1 if clamp_x else 0, workspace.data_ptr(), _stream()), "sqerr_rows")
     return out
+
+
+# ----------------------------------------------------------------------------- Jacobian diagnostics (csrc/jacobian.hip)
+def pack_head_masked_weights(w):
+    """(64,4,3,3) conv weight -> [ch*9+tap (36)][cout//4 (16)][cout%4 (4)] for deqsci_ffdnet_head_masked_f32 (pack_head_weights
+    without the sigma channel)."""
+    if tuple(w.shape) != (64, 4, 3, 3):
+        raise DeqsciHipError(f"ffdnet masked head expects a (64,4,3,3) weight, got {tuple(w.shape)}")
+    return w.detach().float().reshape(16, 4, 36).permute(2, 0, 1).contiguous()
+
+
+def ffdnet_head_masked(x, w_packed, mask, out=None):
+    """x (n,1,2H,2W) planar -> conv3x3(pixel_unshuffle(x, 2), w, pad=1) * mask as a channels_last (n,64,H,W) activation (mask:
+    relu_mask_pack's words): FFDNet's first layer linearised, or - with the last layer's weight transposed - its last layer's transpose."""
+    n, c, H2, W2 = x.shape
+    if c != 1 or H2 % 2 or W2 % 2:
+        raise DeqsciHipError(f"ffdnet_head_masked: (n,1,even,even) image required, got {tuple(x.shape)}")
+    if not isinstance(w_packed, torch.Tensor) or w_packed.numel() != 36 * 64:
+        raise DeqsciHipError("ffdnet_head_masked: w_packed must hold 36*64 floats (the output of _hip.pack_head_masked_weights)")
+    H, W = H2 // 2, W2 // 2
+    o = out if out is not None else torch.empty((n, 64, H, W), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    with _dev(x):
+        _check(load().deqsci_ffdnet_head_masked_f32(_p(x, "x"), _p(w_packed, "w_packed"), _mask_ptr(mask, n, H, W, "ffdnet_head_masked"),
+                                                    o.data_ptr(), n, H, W, _stream()), "ffdnet_head_masked")
+    return o
+
+
+def power_workspace(bsz, N, device):
+    """The caller-owned workspace of power_step for (bsz, N) rows (float64 words; no initialisation needed)."""
+    return torch.empty((max(int(load().deqsci_power_workspace_bytes(bsz, N)) // 8, 1),), device=device, dtype=torch.float64)
+
+
+def power_step(w, v_prev, v_out, table_row, workspace=None):
+    """One step of a power iteration per sample (row) of w (bsz,N): table_row[s] = (|w_s|^2, <v_prev_s, w_s>) in float64 and
+    v_out_s = w_s / |w_s| - zeros, and NaN in the table, where |w_s|^2 is zero or not finite.  v_prev: None (the second entry is NaN) or
+    (bsz,N); v_out may be w or v_prev; table_row: (bsz,2) float64 on the device.  No allocation when the workspace (power_workspace) is
+    given, no host synchronisation."""
+    if w.dim() != 2:
+        raise DeqsciHipError(f"power_step: w must be (bsz,N), got {tuple(w.shape)}")
+    bsz, N = w.shape
+    for name, t in (("v_prev", v_prev), ("v_out", v_out)):
+        if t is not None and tuple(t.shape) != (bsz, N):
+            raise DeqsciHipError(f"power_step: {name} {tuple(t.shape)} must have w's shape {(bsz, N)}")
+    if (not isinstance(table_row, torch.Tensor) or table_row.dtype != torch.float64 or tuple(table_row.shape) != (bsz, 2)
+            or not table_row.is_contiguous() or table_row.device != w.device):
+        raise DeqsciHipError(f"power_step: table_row must be a contiguous float64 ({bsz},2) tensor on w's device")
+    if workspace is None:
+        workspace = power_workspace(bsz, N, w.device)
+    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < load().deqsci_power_workspace_bytes(bsz, N) or workspace.device != w.device:
+        raise DeqsciHipError("power_step: workspace too small (power_workspace(bsz, N, device))")
+    with _dev(w):
+        _check(load().deqsci_power_step_f32(_p(w, "w"), _p(v_prev, "v_prev", True), _p(v_out, "v_out"), table_row.data_ptr(), bsz, N,
+                                            workspace.data_ptr(), _stream()), "power_step")
+    return v_out
 
 
 # ----------------------------------------------------------------------------- GAP-TV (csrc/tv.hip)

@@ -14,6 +14,9 @@ reconstructs by GAP-TV alone, with no DEQ (both this build's; deqsci_amd.gaptv).
 `--snapshots 10,30,100` (this build's) also scores the clips at those iteration horizons out of the SAME run (one extra f-call each) and
 prints one '[and_maxiters K] Total Average PSNR' line per horizon after the usual lines; `--trace FILE.json` writes the PSNR and the
 residual of every f-call, per clip and measurement.
+`--jacobian [N_ITERS]` (this build's) adds the local Lipschitz constant and spectral radius of f and the Lipschitz constant of the noise
+predictor at every reconstruction (deqsci_amd.jacobian) to each clip line and one 'Total Average' line per quantity after the totals;
+`--jacobian_json FILE` writes the per-measurement values and the iterations' histories.
 """
 import argparse
 import os
@@ -23,7 +26,8 @@ import time
 import torch
 
 from . import checkpoint, distributed
-from .harness import SCITestDataset, evaluate, png_payloads, print_horizons, trace_document, write_png
+from .harness import (SCITestDataset, clip_line, evaluate, jacobian_document, png_payloads, print_horizons, print_jacobian_totals,
+                      trace_document, write_png)
 from .networks import DnCNN, FFDNet
 from .operators import A_torch_, At_torch_
 from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp
@@ -111,6 +115,12 @@ def parser():
                         "one '[and_maxiters K] Total Average PSNR' line per horizon after the usual lines (with SSIM under --ssim)")
     p.add_argument('--trace', default=None, metavar='FILE.json',
                    help="(this build) write the PSNR and the residual of every f-call, per clip and measurement, to FILE.json")
+    p.add_argument('--jacobian', nargs='?', const=30, default=None, type=int, metavar='N_ITERS',
+                   help="(this build) also report, at every reconstruction, the local Lipschitz constant Lip(f) and the spectral radius rho(f) of "
+                        "the fixed-point map and the Lipschitz constant Lip(D) of the noise predictor (power iterations of N_ITERS steps, "
+                        "default 30): per clip and one 'Total Average' line per quantity")
+    p.add_argument('--jacobian_json', default=None, metavar='FILE',
+                   help="(this build) write the per-measurement Jacobian values and the histories of their iterations to FILE.  Implies --jacobian")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
     ignored.add_argument('--n_epochs', default=80)
     ignored.add_argument('--batch_size', type=int, default=1)
@@ -141,6 +151,12 @@ def run(args):
             deq.engine_options = opts
     if args.baseline is not None and (args.snapshots is not None or args.trace):
         sys.exit("--snapshots / --trace are the DEQ iteration's: not available with --baseline")
+    jac = None
+    if args.jacobian is not None or args.jacobian_json:
+        if args.baseline is not None:
+            sys.exit("--jacobian is the DEQ map's: not available with --baseline")
+        n_it = 30 if args.jacobian is None else args.jacobian
+        jac = {"n_iters": n_it, "window": min(10, n_it)}
     if rank == 0:
         if deq is not None:
             print('loaded dict!')
@@ -151,16 +167,14 @@ def run(args):
     def on_clip(r):
         if rank == 0:
             images.update(png_payloads(r, args.savepath))
-            if ssim:
-                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
-            else:
-                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
+            print(*clip_line(r, ssim))
     t0 = time.time()
     avg, results = evaluate(deq, SCITestDataset(args.testpath), device=dev, on_clip=on_clip,
                             batch="all" if args.batch_measurements == "all" else bool(args.batch_measurements or world > 1),
                             ssim=ssim, ssim_mode=args.ssim_mode or "same", init=args.init_point,
                             method="deq" if args.baseline is None else args.baseline,
-                            **({"snapshots": args.snapshots, "trace": bool(args.trace)} if (args.snapshots is not None or args.trace) else {}))
+                            **({"snapshots": args.snapshots, "trace": bool(args.trace)} if (args.snapshots is not None or args.trace) else {}),
+                            **({} if jac is None else {"jacobian": jac}))
     dt = time.time() - t0
     if rank == 0:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
@@ -168,8 +182,14 @@ def run(args):
             print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
         if args.snapshots is not None:
             print_horizons(results)
+        print_jacobian_totals(results)
         if args.trace:
             write_trace(args.trace, results)
+        if args.jacobian_json:
+            import json
+            with open(args.jacobian_json, "w") as fh:
+                json.dump(jacobian_document(results), fh)
+                fh.write("\n")
         for path, img in images.items():
             write_png(path, img)
         n = sum(r.frames for r in results)

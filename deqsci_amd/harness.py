@@ -134,6 +134,9 @@ class ClipResult:
     # (only when asked for) {K: {"psnr": [...], "res": [...], "ssim": [...] or None, "rec": (M,H,W,B)}}: the run with and_maxiters=K, scored as above
     snapshots: dict | None = None
     trace: dict | None = None         # (only when asked for) {"psnr": (M, n_calls), "res": (M, n_calls)}: every f-call of the iteration
+    # (only when asked for) {"lipschitz_f": [...], "rho_f": [...], "lipschitz_denoiser": [...]} per measurement, at its reconstruction
+    # (deqsci_amd.jacobian), and "histories": {name: (M, n_iters)}
+    jacobian: dict | None = None
 
     @property
     def mean_psnr(self):
@@ -234,6 +237,50 @@ class _Horizons:
         return snaps, trace
 
 
+JACOBIAN_KEYS = ("lipschitz_f", "rho_f", "lipschitz_denoiser")
+_JACOBIAN_HISTORIES = ("lipschitz_f_history", "rho_f_growth", "rho_f_rayleigh", "lipschitz_denoiser_history")
+
+
+class _Jacobians:
+    """The jacobian= option around the forward calls of one harness batch: after each call the module's jacobian_report at the
+    reconstruction it returned (the batch as one call, per-sample norms), gathered over the process group as the PSNR scalars are."""
+
+    def __init__(self, module, options, method):
+        self.module, self.on = module, options is not None
+        if not self.on:
+            return
+        if method != "deq":
+            raise ValueError("jacobian= is the DEQ map's: not available with method='gaptv'")
+        if not hasattr(module, "jacobian_report"):
+            raise NotImplementedError(f"jacobian= needs this package's DEQFixedPoint, not {type(module).__name__}")
+        self.options = dict(options)
+        unknown = set(self.options) - {"n_iters", "window", "seed"}
+        if unknown:
+            raise ValueError(f"jacobian=: unknown option(s) {sorted(unknown)} (n_iters, window, seed)")
+        self.vals = {k: [] for k in JACOBIAN_KEYS + _JACOBIAN_HISTORIES}
+
+    def after(self, y_part, Phi_part, Phi_sum, rec):
+        if self.on:
+            r = self.module.jacobian_report(y_part, Phi_part, Phi_sum, rec, **self.options)
+            for k in JACOBIAN_KEYS:
+                self.vals[k].extend(float(v) for v in r[k])
+            for k in _JACOBIAN_HISTORIES:
+                self.vals[k].extend(r[k][:, j] for j in range(r[k].shape[1]))
+
+    def finish(self, group):
+        if not self.on:
+            return None
+        return {k: distributed.gather_scalars(v, group=group) for k, v in self.vals.items()}
+
+
+def _jac_slice(jac, lo, hi):
+    if jac is None:
+        return None
+    out = {k: list(jac[k][lo:hi]) for k in JACOBIAN_KEYS}
+    out["histories"] = {k: _rows(jac[k][lo:hi]) for k in _JACOBIAN_HISTORIES}
+    return out
+
+
 def _scored(snaps, trace, lo, hi, gt, ids, ssim, ssim_mode):
     """ClipResult.snapshots / .trace of the measurements [lo, hi) of a batch: every snapshot scored exactly as the final result is."""
     out = None
@@ -271,14 +318,17 @@ def _check_method(method, init):
 
 
 def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same", init="At", method="deq",
-                     snapshots=None, trace=False):
+                     snapshots=None, trace=False, jacobian=None):
     """All scored measurements of one clip through `deep_eq_module.forward(y, Phi, Phi_sum, initial_point=, train_flag=False)`.
     batch=True: one call with y (M,H,W) and the shared mask (1,H,W,B); batch=False: M calls of batch 1 (the reference's
     schedule).  With a process group the measurements are sharded over its ranks and all-gathered.  ssim=True: also the
     per-measurement SSIM (clip_ssim, after the timed part).  init: the DEQ's start, "At" (default) or "gaptv" (GAP-TV, timed with the
     reconstruction).  method="gaptv": GAP-TV alone, no DEQ (deep_eq_module is not used; res is None).
     snapshots=(K1, ...): ClipResult.snapshots[K] = the clip as a run with and_maxiters=K would score it, from the same run
-    (DEQSCIEngine.reconstruct); trace=True: ClipResult.trace = PSNR and residual of every f-call, per measurement."""
+    (DEQSCIEngine.reconstruct); trace=True: ClipResult.trace = PSNR and residual of every f-call, per measurement.
+    jacobian=dict(n_iters=, window=, seed=): ClipResult.jacobian = the local Lipschitz constant and spectral radius of f and the Lipschitz
+    constant of the noise predictor at every measurement's reconstruction (DEQFixedPoint.jacobian_report, outside the timed part's meaning:
+    it is added to `seconds`)."""
     import time
     clip = as_clip(clip)
     Phi = clip['mask'].to(device)[None].contiguous()                  # (1,H,W,B)
@@ -288,6 +338,7 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     Phi_sum = operators.phi_sum(Phi)
     _check_method(method, init)
     hz = _Horizons(deep_eq_module, snapshots, trace, method)
+    jc = _Jacobians(deep_eq_module, jacobian, method)
     gts = _gt_batch(clip['gt'], ids, B, device) if hz.trace else None
 
     def run(y_part, Phi_part, lo=0):
@@ -297,6 +348,7 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
         rec = hz.forward(lambda: deep_eq_module.forward(y_part, Phi_part, Phi_sum, initial_point=x0, train_flag=False),
                          None if gts is None else gts[lo:lo + y_part.shape[0]])
         res, _ = _residuals(deep_eq_module, y_part.shape[0])
+        jc.after(y_part, Phi_part, Phi_sum, rec.detach())
         return rec.detach(), res
 
     t0 = time.perf_counter()
@@ -322,17 +374,18 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     snaps, tr = _scored(*hz.finish(y, Phi, group if batch else None), 0, len(ids), clip['gt'], ids, ssim, ssim_mode)
     return ClipResult(name=clip['file'], rec=rec, psnr=ps, res=res, frames=B * len(ids), seconds=dt,
                       info={"measurements": ids, "batched": bool(batch)},
-                      ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None, snapshots=snaps, trace=tr)
+                      ssim=clip_ssim(rec, clip['gt'], ids, ssim_mode) if ssim else None, snapshots=snaps, trace=tr,
+                      jacobian=_jac_slice(jc.finish(group if batch else None), 0, len(ids)))
 
 
 def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same", init="At", method="deq",
-                               snapshots=None, trace=False):
+                               snapshots=None, trace=False, jacobian=None):
     """The scored measurements of SEVERAL clips of one frame size as ONE engine batch, every measurement with its own clip's mask
     ((M,H,W,B) masks: nothing couples the measurements of a batch - alpha, residual, the ranges of the split-fp16 activations are all per
     measurement - so a measurement's reconstruction is the one it gets in any other batch, bit for bit).  What the reference's loop over
     clips and measurements (training/sci_equilibrium_training.py:157,171) becomes when the device wants eight measurements per call: the
     three shipped clips (1 + 1 + 6 measurements) are one call.  -> [ClipResult] in the clips' order; a clip's `seconds` is its share of
-    the call by frames.  ssim=True: also the per-measurement SSIM; init, method, snapshots and trace as in reconstruct_clip."""
+    the call by frames.  ssim=True: also the per-measurement SSIM; init, method, snapshots, trace and jacobian as in reconstruct_clip."""
     import time
     clips = [as_clip(c) for c in clips]
     ids = [scored_measurements(c['file'], c['meas'].shape[-1]) for c in clips]
@@ -342,6 +395,7 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
     res = []
     _check_method(method, init)
     hz = _Horizons(deep_eq_module, snapshots, trace, method)
+    jc = _Jacobians(deep_eq_module, jacobian, method)
     gts = torch.cat([_gt_batch(c['gt'], i, B, device) for c, i in zip(clips, ids)]) if hz.trace else None
 
     def run(y_part, Phi_part):
@@ -354,6 +408,7 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
         rec = hz.forward(lambda: deep_eq_module.forward(y_part, Phi_part, Ps, initial_point=x0, train_flag=False),
                          None if gts is None else gts[lo:lo + y_part.shape[0]])
         res.extend(_residuals(deep_eq_module, y_part.shape[0])[0])
+        jc.after(y_part, Phi_part, Ps, rec.detach())
         return rec.detach()
     t0 = time.perf_counter()
     rec = distributed.sharded_reconstruct(run, y, Phi, group=group)
@@ -363,27 +418,34 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
     dt = time.perf_counter() - t0
     out, a = [], 0
     all_snaps, all_trace = hz.finish(y, Phi, group)
+    all_jac = jc.finish(group)
     for c, i in zip(clips, ids):
         r = rec[a:a + len(i)]
         snaps, tr = _scored(all_snaps, all_trace, a, a + len(i), c['gt'], i, ssim, ssim_mode)
         out.append(ClipResult(name=c['file'], rec=r, psnr=clip_psnr(r, c['gt'], i), res=list(res[a:a + len(i)]), frames=B * len(i),
                               seconds=dt * len(i) / y.shape[0], info={"measurements": i, "batched": "all"},
-                              ssim=clip_ssim(r, c['gt'], i, ssim_mode) if ssim else None, snapshots=snaps, trace=tr))
+                              ssim=clip_ssim(r, c['gt'], i, ssim_mode) if ssim else None, snapshots=snaps, trace=tr,
+                              jacobian=_jac_slice(all_jac, a, a + len(i))))
         a += len(i)
     return out
 
 
 def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same", init="At",
-             method="deq", snapshots=None, trace=False):
+             method="deq", snapshots=None, trace=False, jacobian=None):
     """-> (mean over clips of the clip's mean PSNR, [ClipResult]).  batch: False = one measurement per call (the reference's schedule),
     True = a clip's measurements per call, "all" = the measurements of consecutive clips of one frame size per call
     (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements).  ssim=True fills every ClipResult.ssim
     (window 11, ssim_mode "same" or "valid"); the mean over clips of the clip's mean SSIM is then sum(r.mean_ssim ...) / len(results).
     init: the DEQ's start, "At" (default) or "gaptv"; method="gaptv": reconstruct by GAP-TV alone (deep_eq_module may be None).
     snapshots=(K1, ...) fills every ClipResult.snapshots (the clip at and_maxiters=K, out of the same run), trace=True every
-    ClipResult.trace; `horizon_means(results)` is the mean over clips per horizon."""
+    ClipResult.trace; `horizon_means(results)` is the mean over clips per horizon.  jacobian=dict(n_iters=, window=, seed=) fills every
+    ClipResult.jacobian (ValueError with method="gaptv")."""
     _check_method(method, init)
     kw = dict(ssim=ssim, ssim_mode=ssim_mode, init=init, method=method)
+    if jacobian is not None:
+        if method != "deq":
+            raise ValueError("jacobian= is the DEQ map's: not available with method='gaptv'")
+        kw.update(jacobian=jacobian)
     if snapshots is not None or trace:
         kw.update(snapshots=snapshots, trace=trace)
     results = []
@@ -431,6 +493,36 @@ def print_horizons(results):
             print('---------------------------------', '[and_maxiters %d] Total Average PSNR: %.2f dB' % (K, p), '  SSIM: %.4f' % s)
 
 
+def clip_line(r, ssim=False):
+    """The pieces of a clip's printed line: the reference's, then this build's additions that were asked for."""
+    parts = [[r.name], '  PSNR: %.2f dB' % r.mean_psnr]
+    if ssim:
+        parts.append('  SSIM: %.4f' % r.mean_ssim)
+    if getattr(r, "jacobian", None) is not None:
+        m = {k: float(np.mean(r.jacobian[k])) for k in JACOBIAN_KEYS}
+        parts.append('  Lip(f): %.4f  rho(f): %.4f  Lip(D): %.4f' % (m["lipschitz_f"], m["rho_f"], m["lipschitz_denoiser"]))
+    return parts
+
+
+def print_jacobian_totals(results):
+    """One 'Total Average' line per Jacobian quantity (the mean over clips of the clip's mean), when jacobian= was asked for."""
+    if not results or getattr(results[0], "jacobian", None) is None:
+        return
+    for k, label in zip(JACOBIAN_KEYS, ("Lip(f)", "rho(f)", "Lip(D)")):
+        print('---------------------------------', 'Total Average %s: %.4f' % (label, sum(float(np.mean(r.jacobian[k])) for r in results) / len(results)))
+
+
+def jacobian_document(results):
+    """{clip: {measurement: {"lipschitz_f", "rho_f", "lipschitz_denoiser", "histories": {...}}}}: what `--jacobian_json FILE` writes."""
+    doc = {}
+    for r in results:
+        if r.jacobian is not None:
+            doc[r.name] = {str(m): {**{k: float(r.jacobian[k][i]) for k in JACOBIAN_KEYS},
+                                    "histories": {k: [float(v) for v in h[i]] for k, h in r.jacobian["histories"].items()}}
+                           for i, m in enumerate(r.info["measurements"])}
+    return doc
+
+
 def trace_document(results):
     """{clip: {measurement: {"psnr": [...], "res": [...]}}}: what `--trace FILE.json` writes, one value per issued f-call of the iteration."""
     doc = {}
@@ -453,7 +545,8 @@ def png_payloads(result, prefix=""):
 
 
 def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, verbose=True, save_image=True,
-                    device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq", snapshots=None, trace=False):
+                    device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq", snapshots=None, trace=False,
+                    jacobian=None):
     """Adapter with the reference's signature (training/sci_equilibrium_training.py:152): returns
     (average PSNR, {png path: float image}); prints one line per clip and the total; writes the PNGs.
     Default = the reference's schedule, one measurement per call (:171-181); batch_measurements="all" hands the measurements of all clips of
@@ -463,7 +556,9 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
     every clip line '  SSIM: %.4f' and a 'Total Average SSIM' line follows the PSNR total; the return value is unchanged.  init="gaptv"
     starts the DEQ from GAP-TV, method="gaptv" reconstructs by GAP-TV alone (both this build's additions, as in evaluate).
     snapshots=(K1, ...) / trace=True (this build's, as in evaluate): every record gains "snapshots" ({K: {"psnr", "res", "ssim", "rec"}}) /
-    "trace" ({"psnr", "res"} per f-call), and one '[and_maxiters K] Total Average PSNR' line per horizon follows the totals."""
+    "trace" ({"psnr", "res"} per f-call), and one '[and_maxiters K] Total Average PSNR' line per horizon follows the totals.
+    jacobian=dict(n_iters=, window=, seed=) (this build's): every record gains "jacobian" ({"lipschitz_f", "rho_f", "lipschitz_denoiser"}),
+    every clip line '  Lip(f): %.4f  rho(f): %.4f  Lip(D): %.4f' (means over the clip's measurements), and one 'Total Average' line per quantity follows."""
     images = {}
 
     def on_clip(r):
@@ -478,18 +573,18 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
                                                     "rec": v["rec"][i:i + 1].cpu()} for K, v in r.snapshots.items()}
                 if r.trace is not None:
                     records[-1]["trace"] = {k: np.asarray(v[i]) for k, v in r.trace.items()}
+                if r.jacobian is not None:
+                    records[-1]["jacobian"] = {k: r.jacobian[k][i] for k in JACOBIAN_KEYS}
         if verbose:
-            if ssim:
-                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr, '  SSIM: %.4f' % r.mean_ssim)
-            else:
-                print([r.name], '  PSNR: %.2f dB' % r.mean_psnr)
+            print(*clip_line(r, ssim))
     avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim, init=init,
-                            method=method, snapshots=snapshots, trace=trace)
+                            method=method, snapshots=snapshots, trace=trace, **({} if jacobian is None else {"jacobian": jacobian}))
     if verbose:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
         if ssim:
             print('---------------------------------', 'Total Average SSIM: %.4f' % (sum(r.mean_ssim for r in results) / len(results)))
         print_horizons(results)
+        print_jacobian_totals(results)
     if save_image:
         for path, img in images.items():
             write_png(path, img)

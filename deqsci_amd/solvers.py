@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _hip, autograd as _ag, vjp as _vjp
 from ._hip import LAYOUT_BHW, LAYOUT_HWB
-from .engine import SIGMA0, SIGMA_DECAY, DEQSCIEngine
+from .engine import SIGMA0, SIGMA_DECAY, DEQSCIEngine, sigma_schedule
 from .operators import A_torch_, At_torch_
 
 
@@ -114,6 +114,30 @@ class EquilibriumProxGradSCI(nn.Module):
             return _hip.gap_update(v, Phi, zero_y, Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
         return jmap
 
+    def device_jacobian_eligibility(self):
+        """(ok, reason): whether device_jacobian can serve this map (HIP GAP operators and a denoiser vjp.jacobian_eligibility accepts)."""
+        if not (self.A is A_torch_ and self.At is At_torch_):
+            return False, "custom A / At: the device map uses the HIP GAP projection"
+        return _vjp.jacobian_eligibility(self.nonlinear_op)
+
+    def device_jacobian(self, z, y, Phi, Phi_sum, sigma=None):
+        """The Jacobian of this map at an explicit point z (bsz,H,W,B), in both directions on the HIP kernels (a diagnostic:
+        deqsci_amd.jacobian.power_report).  z1 = P z + c comes from the GAP kernel itself; nothing here calls f or advances the sigma
+        state - FFDNet is linearised through its input at the given sigma (a float or a tensor of 1 or bsz*B elements).  -> a
+        MapJacobian: .jv(v) = (I - J_D(z1)) (P v), .jtv(v) = P (v - J_D(z1)^T v) on (bsz,H,W,B) fp32 GPU tensors, P = gap_update with
+        y = 0 as in device_vjp, and .denoiser, the DenoiserJacobian at z1.  No host synchronisation."""
+        ok, why = self.device_jacobian_eligibility()
+        if not ok:
+            raise ValueError(f"device_jacobian: {why}")
+        if z.dim() != 4 or not z.is_cuda:
+            raise _hip.DeqsciHipError(f"device_jacobian: z must be a (bsz,H,W,B) GPU tensor, got {tuple(z.shape)} on {z.device}")
+        bsz, H, W, B = z.shape
+        Phi, Phi_sum = _hip.f32c(Phi), _hip.f32c(Phi_sum)
+        with torch.no_grad():
+            z1 = _hip.gap_update(_hip.f32c(z.detach()), Phi, _hip.f32c(y), Phi_sum, LAYOUT_HWB, LAYOUT_BHW)
+            jd = _vjp.DenoiserJacobian(self.nonlinear_op, z1.view(bsz * B, 1, H, W), sigma)
+        return MapJacobian(jd, Phi, Phi_sum, (bsz, H, W, B))
+
     def forward(self, z, y, Phi, Phi_sum):
         bsz, w, h, c = z.shape
         op = self.nonlinear_op
@@ -142,6 +166,28 @@ class EquilibriumProxGradSCI(nn.Module):
             print('unknown nonlinear_op tag!')
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return _hip.residual_out(z1, _hip.f32c(noise.reshape(bsz, c, w, h)), LAYOUT_HWB)
+
+
+class MapJacobian:
+    """J_f at a point, f(z) = z1 - D(z1), z1 = P z + c (EquilibriumProxGradSCI.device_jacobian): v and the results (bsz,H,W,B) fp32."""
+
+    def __init__(self, denoiser, Phi, Phi_sum, shape):
+        self.denoiser, self.Phi, self.Phi_sum, self.shape = denoiser, Phi, Phi_sum, tuple(shape)
+        self._zero_y = torch.zeros(self.shape[:3], device=Phi.device, dtype=torch.float32)
+
+    def _v(self, v):
+        if tuple(v.shape) != self.shape:
+            raise _hip.DeqsciHipError(f"MapJacobian: v must have the shape {self.shape} of z, got {tuple(v.shape)}")
+        return _hip.f32c(v)
+
+    def jv(self, v):
+        pv = _hip.gap_update(self._v(v), self.Phi, self._zero_y, self.Phi_sum, LAYOUT_HWB, LAYOUT_BHW)      # P v, planar
+        return _hip.residual_out(pv, self.denoiser.jvp(pv.view(self.denoiser.shape)).view(pv.shape), LAYOUT_HWB)
+
+    def jtv(self, v):
+        vp = _hip.transpose(self._v(v), LAYOUT_BHW)
+        u = _hip.residual_out(vp, self.denoiser.vjp(vp.view(self.denoiser.shape)).view(vp.shape), LAYOUT_HWB)
+        return _hip.gap_update(u, self.Phi, self._zero_y, self.Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
 
 
 def andersonexp(f, x0, m=5, lam=1e-4, max_iter=50, tol=1e-5, beta=1.0, *, anderson_arith="reference"):
@@ -263,6 +309,37 @@ class DEQFixedPoint(nn.Module):
             self.backward_fallback_reason = why
             return None
         return f.device_vjp(Phi, Phi_sum)
+
+    def jacobian_at(self, y, Phi, Phi_sum, z):
+        """f's Jacobian at z - the reconstruction the last forward(y, ...) returned - as EquilibriumProxGradSCI.device_jacobian gives it
+        (.jv, .jtv, .denoiser).  FFDNet is linearised at the sigma of the f-call that produced that reconstruction: row rec_call of the
+        engine's sigma table, rec_call = the engine's call count less the calls behind it (the extra call, the snapshots' extra calls).
+        NotImplementedError with the reason for what cannot be served: custom A / At, a denoiser without a device Jacobian, FFDNet
+        off the engine's path."""
+        f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
+        if not isinstance(f, EquilibriumProxGradSCI):
+            raise NotImplementedError(f"jacobian_report: f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI")
+        ok, why = f.device_jacobian_eligibility()
+        if not ok:
+            raise NotImplementedError(f"jacobian_report: {why}")
+        sigma = None
+        if getattr(f.nonlinear_op, "tag", None) == "ffdnet":
+            eng = self._engine[1] if self._engine else None
+            info = getattr(eng, "last_info", None)
+            if not info:
+                raise NotImplementedError("jacobian_report: FFDNet's sigma is read from the engine's table at the call count of the last "
+                                          "forward, and no forward has run on the engine's path")
+            snaps = info.get("snapshots") or {}
+            rec_call = info["f_calls"] - 1 - int(bool(eng.extra_call)) - sum(1 for K in snaps if info["iterations"] >= K - 1)
+            sigma = torch.from_numpy(sigma_schedule(rec_call + 1)[rec_call:]).to(z.device)      # (the engine's table: row rec_call)
+        return f.device_jacobian(z, y, Phi, Phi_sum, sigma=sigma)
+
+    def jacobian_report(self, y, Phi, Phi_sum, z, **kw):
+        """The local Lipschitz constant and the spectral radius of f, and the Lipschitz constant of the noise predictor, at z - the
+        reconstruction the last forward(y, ...) returned: deqsci_amd.jacobian.power_report (**kw: its n_iters, window, seed, of) on
+        self.jacobian_at(y, Phi, Phi_sum, z), whose refusals (NotImplementedError) are this method's."""
+        from . import jacobian as _jac
+        return _jac.power_report(self.jacobian_at(y, Phi, Phi_sum, z), tuple(z.shape), **kw)
 
     def forward(self, x, Phi, Phi_sum, initial_point=None, train_flag=True):
         """x is the measurement y.  Without a tape (torch.no_grad(), or no parameter of f requiring a gradient) this is the

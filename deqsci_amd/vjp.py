@@ -16,6 +16,11 @@ product is linear in v:
 the masked epilogue, and the existing 64 -> 1 stencil (the head's transpose); the masks are packed one 64-bit word per pixel by
 csrc/vjp.hip.  FFDNet detaches its input (networks/ffdnet/models.py in the reference, deqsci_amd/networks/ffdnet.py), so for it
 J_D^T = 0 and the hook's product is P v alone.
+
+The same masked kernels compute J_D(x) v (forward mode) when they are handed the untransposed weights in forward order: DenoiserJacobian
+(the diagnostics of deqsci_amd/jacobian.py) has both directions, and for FFDNet it differentiates THROUGH the input - the Jacobian of
+the map the iteration applies, sigma a constant of the linearisation - on csrc/jacobian.hip's masked first layer and the existing last
+layer's kernel.  DenoiserVJP and eligibility are the training hook's and do not change.
 """
 import torch
 import torch.nn.functional as F
@@ -107,9 +112,8 @@ def _transposed(w):
     return w.transpose(0, 1).flip(2, 3).contiguous()
 
 
-def plan_vjp(layers, x, v):
-    """J_D(x)^T v of the stack `layers` (host_plan) evaluated in x's dtype with F.conv2d and explicit masks - the host statement of what
-    DenoiserVJP runs (tests: float64 against torch.autograd.grad).  Returns (vjp, masks)."""
+def plan_masks(layers, x):
+    """The ReLU masks of one forward pass of the stack `layers` at x, in x's dtype: one (n,C,H,W) bool tensor (or None) per layer but the last."""
     h, masks = x, []
     for w, b, relu in layers[:-1]:
         h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
@@ -118,12 +122,204 @@ def plan_vjp(layers, x, v):
             h = torch.relu(h)
         else:
             masks.append(None)
+    return masks
+
+
+def plan_vjp(layers, x, v, masks=None):
+    """J_D(x)^T v of the stack `layers` (host_plan) evaluated in x's dtype with F.conv2d and explicit masks - the host statement of what
+    DenoiserVJP runs (tests: float64 against torch.autograd.grad).  masks: those of another forward pass (the device's, unpack_masks)
+    instead of the ones at x.  Returns (vjp, masks)."""
+    if masks is None:
+        masks = plan_masks(layers, x)
     g = v
     for i in range(len(layers) - 1, 0, -1):
         g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
         if masks[i - 1] is not None:
             g = g * masks[i - 1]
     return F.conv2d(g, _transposed(layers[0][0].to(v)), padding=1), masks
+
+
+def plan_jvp(layers, x, v, masks=None):
+    """J_D(x) v of the stack `layers`: the layers in forward order, every conv without its bias, every ReLU replaced by its mask - the host
+    statement of DenoiserJacobian.jvp, next to plan_vjp.  Returns (jvp, masks)."""
+    if masks is None:
+        masks = plan_masks(layers, x)
+    t = v
+    for i, (w, _, _) in enumerate(layers[:-1]):
+        t = F.conv2d(t, w.to(v), padding=1)
+        if masks[i] is not None:
+            t = t * masks[i]
+    return F.conv2d(t, layers[-1][0].to(v), padding=1), masks
+
+
+# ----------------------------------------------------------------------------- FFDNet, differentiated through its input
+def ffdnet_plan(net):
+    """Grayscale FFDNet in eval mode as [(weight, bias or None, relu)]: (64,5,3,3) first, 13 x (64,64,3,3) with the BatchNorm folded
+    (engine._fold_bn), (4,64,3,3) last.  Functional: ffdnet_plan_forward does not detach its input.  Usable on the CPU."""
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    if not isinstance(net, FFDNet) or net.num_input_channels != 1:
+        raise ValueError("ffdnet_plan: a grayscale FFDNet is required")
+    from .engine import _fold_bn
+    mods = list(net.intermediate_dncnn.itermediate_dncnn)
+    layers, i = [], 0
+    while i < len(mods):
+        conv = mods[i]
+        if not isinstance(conv, torch.nn.Conv2d) or not _conv_ok(conv) or conv.bias is not None:
+            raise ValueError(f"ffdnet_plan: module {i} is not a 3x3, stride 1, padding 1 convolution without bias")
+        w, b = conv.weight.detach(), None
+        i += 1
+        if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
+            if mods[i].training:
+                raise ValueError("ffdnet_plan: BatchNorm2d in train mode")
+            w, b = _fold_bn(w, mods[i])
+            w, b = w.detach(), b.detach()
+            i += 1
+        relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
+        i += int(relu)
+        layers.append((w, b, relu))
+    shapes = [tuple(w.shape) for w, _, _ in layers]
+    if (len(layers) < 3 or shapes[0] != (64, 5, 3, 3) or shapes[-1] != (4, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1])
+            or not all(r for _, _, r in layers[:-1]) or layers[-1][2] or layers[0][1] is not None or layers[-1][1] is not None):
+        raise ValueError(f"ffdnet_plan: layer shapes {shapes} are not the grayscale network's")
+    return layers
+
+
+def _even(x, what):
+    if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] % 2 or x.shape[3] % 2:
+        raise ValueError(f"{what}: FFDNet needs a (n,1,even,even) image (its first layer is a 2x2 pixel-unshuffle), got {tuple(x.shape)}")
+
+
+def _sigma_map(sigma, x):
+    n, _, H, W = x.shape
+    s = torch.as_tensor(sigma, dtype=x.dtype, device=x.device).reshape(-1)
+    return (s.expand(n) if s.numel() == 1 else s).reshape(n, 1, 1, 1).expand(n, 1, H // 2, W // 2)
+
+
+def ffdnet_plan_forward(layers, x, sigma):
+    """(noise, masks) of FFDNet at (x, sigma) in x's dtype, through the input (no detach): masks[i] is the ReLU decision behind layer i."""
+    _even(x, "ffdnet_plan_forward")
+    h, masks = torch.cat((_sigma_map(sigma, x), F.pixel_unshuffle(x, 2)), 1), []
+    for w, b, _ in layers[:-1]:
+        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
+        masks.append(h > 0)
+        h = torch.relu(h)
+    return F.pixel_shuffle(F.conv2d(h, layers[-1][0].to(x), padding=1), 2), masks
+
+
+def ffdnet_plan_jvp(layers, x, sigma, v, masks=None):
+    """J_D(x; sigma) v of FFDNet through its input (sigma a constant: its channel of the first layer carries no tangent).  -> (jvp, masks)"""
+    _even(x, "ffdnet_plan_jvp")
+    if masks is None:
+        masks = ffdnet_plan_forward(layers, x, sigma)[1]
+    t = F.conv2d(F.pixel_unshuffle(v, 2), layers[0][0][:, 1:5].to(v), padding=1) * masks[0]
+    for i in range(1, len(layers) - 1):
+        t = F.conv2d(t, layers[i][0].to(v), padding=1) * masks[i]
+    return F.pixel_shuffle(F.conv2d(t, layers[-1][0].to(v), padding=1), 2), masks
+
+
+def ffdnet_plan_vjp(layers, x, sigma, v, masks=None):
+    """J_D(x; sigma)^T v of FFDNet through its input.  -> (vjp, masks)"""
+    _even(x, "ffdnet_plan_vjp")
+    if masks is None:
+        masks = ffdnet_plan_forward(layers, x, sigma)[1]
+    g = F.conv2d(F.pixel_unshuffle(v, 2), _transposed(layers[-1][0].to(v)), padding=1) * masks[-1]
+    for i in range(len(layers) - 2, 0, -1):
+        g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1) * masks[i - 1]
+    return F.pixel_shuffle(F.conv2d(g, _transposed(layers[0][0][:, 1:5].to(v)), padding=1), 2), masks
+
+
+def unpack_masks(words):
+    """relu_mask_pack's (n,H,W) int64 words -> the (n,64,H,W) bool mask the host plans take (bit c = channel c)."""
+    bits = torch.arange(64, device=words.device, dtype=torch.int64).view(1, 64, 1, 1)
+    return ((words.unsqueeze(1) >> bits) & 1).bool()
+
+
+FFDNET_THROUGH_INPUT = "FFDNet: through the input"          # jacobian_eligibility's reason for the one net that is not a plain stack
+
+
+def jacobian_eligibility(net):
+    """(ok, reason): whether DenoiserJacobian can linearise `net`.  eligibility's refusals; FFDNet is differentiated through its input.  CPU-safe."""
+    ok, why = eligibility(net)
+    if ok and why == _FFDNET_OK:
+        return True, FFDNET_THROUGH_INPUT
+    return ok, why
+
+
+class DenoiserJacobian:
+    """v -> J_D(x) v (.jvp) and v -> J_D(x)^T v (.vjp) for a (n,1,H,W) fp32 GPU image x and v of its shape, on the HIP kernels: a
+    diagnostic of the map the iteration applies, so FFDNet (grayscale, eval mode) is differentiated through its input at the noise level
+    sigma, a constant of the linearisation.  One forward pass at x on the fp32 kernels (first layer stencil, Winograd F(2x2,3x3) with the
+    folded BN bias) builds the ReLU masks (.masks, relu_mask_pack's words per layer); every product is then linear in v: masked layers
+    enqueued on the current stream with no host synchronisation.  Conv stacks: .vjp is what DenoiserVJP runs, .jvp the same kernels in
+    forward order with the untransposed weights.  FFDNet: csrc/jacobian.hip's masked first layer serves the linearised head and the
+    transposed tail, deqsci_ffdnet_tail_f32 without bias the linearised tail and the transposed head.  Raises ValueError for a net
+    jacobian_eligibility refuses and for an FFDNet image with an odd side, before any launch."""
+
+    def __init__(self, net, x, sigma=None):
+        ok, why = jacobian_eligibility(net)
+        if not ok:
+            raise ValueError(f"DenoiserJacobian: {why}")
+        if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
+            raise _hip.DeqsciHipError(f"DenoiserJacobian: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
+        self.shape = tuple(x.shape)
+        self.ffdnet = why == FFDNET_THROUGH_INPUT
+        if self.ffdnet:
+            _even(x, "DenoiserJacobian")
+            if sigma is None:
+                raise ValueError("DenoiserJacobian: FFDNet is linearised at a noise level: sigma is required")
+        x = _hip.f32c(x.detach())
+        dev = x.device
+        f32 = lambda t: t.to(dev, torch.float32)
+        self.masks = []
+        with torch.no_grad():
+            if self.ffdnet:
+                layers = ffdnet_plan(net)
+                w0, wt = f32(layers[0][0]), f32(layers[-1][0])
+                sg = torch.as_tensor(sigma, dtype=torch.float32, device=dev).reshape(-1)
+                if sg.numel() not in (1, x.shape[0]):
+                    raise ValueError(f"DenoiserJacobian: sigma must have 1 or {x.shape[0]} elements, got {sg.numel()}")
+                self.sigma = sg.contiguous()
+                h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), self.sigma)
+                self.head_f = _hip.pack_head_masked_weights(w0[:, 1:5].contiguous())
+                self.tail_f = _hip.pack_tail_weights(wt)
+                self.tail_t = _hip.pack_head_masked_weights(_transposed(wt))
+                self.head_t = _hip.pack_tail_weights(_transposed(w0[:, 1:5]))
+            else:
+                layers, _ = host_plan(net)
+                w0, wt = f32(layers[0][0]), f32(layers[-1][0])
+                h = _hip.conv3x3_c1_to_64(x, _hip.pack_c1_to_64_weights(w0), relu=True)
+                self.head_f = _hip.pack_c1_to_64_weights(w0)
+                self.tail_f = _hip.pack_c64_to_1_weights(wt)
+                self.tail_t = _hip.pack_c1_to_64_weights(_transposed(wt))
+                self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
+            self.masks.append(_hip.relu_mask_pack(h))
+            for w, b, _ in layers[1:-1]:
+                h = _hip.conv3x3_c64_winograd(h, _hip.pack_winograd_weights(f32(w)), None if b is None else f32(b).contiguous(), True)
+                self.masks.append(_hip.relu_mask_pack(h))
+            del h
+            self.mid_f = [_hip.pack_winograd_weights(f32(w)) for w, _, _ in layers[1:-1]]
+            self.mid_t = [_hip.pack_winograd_weights(_transposed(f32(w))) for w, _, _ in layers[1:-1]]
+
+    def _v(self, v, what):
+        if tuple(v.shape) != self.shape:
+            raise _hip.DeqsciHipError(f"DenoiserJacobian.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
+        return _hip.f32c(v)
+
+    def jvp(self, v):
+        v = self._v(v, "jvp")
+        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
+        t = first(v, self.head_f, self.masks[0])
+        for i, u in enumerate(self.mid_f):
+            t = _hip.conv3x3_c64_winograd_masked(t, u, self.masks[i + 1])
+        return _hip.ffdnet_tail(t, self.tail_f) if self.ffdnet else _hip.conv3x3_c64_to_1(t, self.tail_f)
+
+    def vjp(self, v):
+        v = self._v(v, "vjp")
+        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
+        g = first(v, self.tail_t, self.masks[-1])
+        for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
+            g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
+        return _hip.ffdnet_tail(g, self.head_t) if self.ffdnet else _hip.conv3x3_c64_to_1(g, self.head_t)
 
 
 class DenoiserVJP:

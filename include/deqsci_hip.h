@@ -416,6 +416,26 @@ int deqsci_conv3x3_c64_winograd_masked_f32(const float* x, const float* u_packed
 int deqsci_conv3x3_c1_to_64_masked_f32(const float* x, const float* w_packed, const uint64_t* mask, float* h,
                                        int64_t n, int64_t H, int64_t W, deqsci_stream_t stream);
 
+/* ---- Jacobian diagnostics (deqsci_amd/jacobian.py: the local Lipschitz constant and the spectral radius of f at a point) ----
+ * J1  FFDNet's first layer without its sigma channel, bias and ReLU, masked: h = conv3x3(pixel_unshuffle_2(x)) * mask.  x planar
+ *     (n,1,2H,2W), w_packed the (64,4,3,3) weight packed as deqsci_ffdnet_head_f32's is but over 36 rows ([ch*9+tap][cout/4][cout%4]),
+ *     mask the words of V0 in the pixel order of h (8-byte aligned), h channels_last (n,H,W,64), 16-byte aligned.  With the forward
+ *     weights of image channels 1..4 and the first ReLU's mask: the linearised first layer; with the last layer's weight transposed
+ *     and flipped and the last ReLU's mask: the transpose of the last layer.  (The other two edge products are
+ *     deqsci_ffdnet_tail_f32 with in_bias = NULL.)  Scale-free fp32 arithmetic.
+ * J2  one step of a power iteration, per sample: a = |w|^2 and b = <v_prev, w> with float64 products and sums, (a, b) written to
+ *     table_row[2 s], table_row[2 s + 1] (the caller passes the row of the current iteration of its float64 table), and
+ *     v_out = w / sqrt(a).  a zero or not finite: v_out = 0 and (NaN, NaN) in the table.  v_prev may be NULL (b = NaN); v_out may be
+ *     w or v_prev.  w, v_prev, v_out (bsz,N) dense fp32, 4-byte aligned; table_row and workspace 8-byte aligned.  Deterministic
+ *     (two stages, fixed summation order, no atomics).  bsz = 0 or N = 0: nothing is launched.  bsz <= 65535.  workspace =
+ *     deqsci_power_workspace_bytes(bsz, N) bytes (0 for invalid sizes), no initialisation needed.  Two launches on `stream`; no
+ *     allocation, no host synchronisation, graph-capturable. */
+int deqsci_ffdnet_head_masked_f32(const float* x, const float* w_packed, const uint64_t* mask, float* h,
+                                  int64_t n, int64_t H, int64_t W, deqsci_stream_t stream);
+size_t deqsci_power_workspace_bytes(int64_t bsz, int64_t N);
+int deqsci_power_step_f32(const float* w, const float* v_prev, float* v_out, double* table_row, int64_t bsz, int64_t N,
+                          void* workspace, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
