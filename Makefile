@@ -18,6 +18,7 @@ $(ORACLE_LIB): oracle/deqsci_oracle.c include/deqsci_hip.h
 
 # diagnostic variant for tools/ (env knobs DEQSCI_GRAM_NOISE, DEQSCI_K4_BLOCKS, DEQSCI_FORCE_POLICY, DEQSCI_HEAD_VALU); never loaded by the
 # package unless DEQSCI_HIP_LIB points at it
+# (the kernels carry no other compile-time variants; the -D..._STAMP profiling builds come from tools/lib_variants.sh)
 DIAG_LIB   := build/diag/libdeqsci_hip_diag.so
 diag: $(DIAG_LIB)
 $(DIAG_LIB): $(SRCS) $(HDRS)

@@ -15,7 +15,7 @@ LAYOUT_BHW = 1   # (bsz,B,H,W)  planar / denoiser layout
 MAX_M = 8
 PART_STRIDE = MAX_M + 1
 
-# DEQSCI_HIP_LIB: another build of the SAME library (tools only: the -DDEQSCI_DIAG variant of `make diag`, an ablation build)
+# DEQSCI_HIP_LIB: another build of the SAME library (tools only: the -DDEQSCI_DIAG variant of `make diag`, a stamp build of tools/lib_variants.sh)
 _LIB_PATH = os.environ.get("DEQSCI_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libdeqsci_hip.so")
 _lib = None
 

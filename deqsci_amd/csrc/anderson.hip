@@ -475,10 +475,6 @@ __global__ __launch_bounds__(TB) void gram_round_kernel(const float* __restrict_
 // F / G / x_next, records of the same meaning: the launch replaces residual_store_kernel + gram_round_kernel for chunks of 2048 elements (N bsz <= 2^25)
 // when N is a whole number of at most 256 of them (deqsci_gram_ref_fusable).
 constexpr unsigned LOOKBACK_SPINS = 1u << 11;                // re-asks per granule (~0.1 us each) before a block stops waiting: ~0.2 ms
-#ifndef RSR_ABL
-#define RSR_ABL 0     // timing ablations only (tools/gram_fused_time.py; results wrong): 1 = no term stores, 2 = no waiting in the look-back, 4 = no rounding
-                      // arithmetic, 16 = no look-back at all
-#endif
 
 template <int NF, int POL>
 __global__ __launch_bounds__(TB, 4) void residual_store_round_kernel(const float* __restrict__ z1, const float* __restrict__ noise, const float* x_cur,
@@ -556,7 +552,7 @@ __global__ __launch_bounds__(TB, 4) void residual_store_round_kernel(const float
         for (int j = 0; j < NF; ++j) x[j] = 0.0f;
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         constexpr int NP = (NF + 1) / 2;                        // 16-byte pieces of a block's granules: {sum, tag, sum, tag}
-        for (int bb = t; bb < ((RSR_ABL & 16) ? 0 : b); bb += TB) {
+        for (int bb = t; bb < b; bb += TB) {
             const u32x4* src = reinterpret_cast<const u32x4*>(pub + (int64_t)bb * MAXM);
             u32x4 gk[NP];
 #pragma unroll
@@ -565,7 +561,7 @@ __global__ __launch_bounds__(TB, 4) void residual_store_round_kernel(const float
             for (int p = 0; p < NP; ++p) {
                 asm volatile("s_waitcnt vmcnt(%1)" : "+v"(gk[p]) : "n"(NP - 1 - p) : "memory");
                 unsigned spins = 0;
-                while (!(RSR_ABL & 2) && (gk[p].y != epoch || (2 * p + 1 < NF && gk[p].w != epoch)) && ++spins < LOOKBACK_SPINS) {
+                while ((gk[p].y != epoch || (2 * p + 1 < NF && gk[p].w != epoch)) && ++spins < LOOKBACK_SPINS) {
                     __builtin_amdgcn_s_sleep(2);
                     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(gk[p]) : "v"(src + p) : "memory");
                 }
@@ -640,10 +636,10 @@ __global__ __launch_bounds__(TB, 4) void residual_store_round_kernel(const float
 #pragma unroll
             for (int j = 0; j < NF; ++j) {
                 const float bb = tile[j][w];
-                if (slot_s[j] >= 0 && !(RSR_ABL & 1))           // (uniform)
+                if (slot_s[j] >= 0)                             // (uniform)
                     *reinterpret_cast<float2*>(terms + ((((int64_t)j * TSLOTS + slot_s[j]) * C16 + c) * PF_TERMS + (tl * (RND_TILE / C16) + ix)) * 2) = make_float2(a, bb);
 #pragma unroll
-                for (int q = 0; q < ((RSR_ABL & 4) ? 0 : REF_CAND); ++q) {
+                for (int q = 0; q < REF_CAND; ++q) {
                     const float tt = fmaf(a, bb, cM[j][q]);
                     const unsigned ti = __float_as_uint(tt), mi = __float_as_uint(cM[j][q]);
                     const unsigned dl = ti > mi ? ti - mi : mi - ti;

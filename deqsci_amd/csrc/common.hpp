@@ -90,6 +90,27 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// ---- small pieces the persistent matrix-core kernels share (csrc/conv_s16.hip, csrc/conv_w16.hip)
+// Workgroup barrier that orders LDS traffic only: __syncthreads() is a fence + s_barrier, and the fence would drain the loads and LDS-DMA
+// instructions deliberately left in flight across the barrier
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int mdiv(int t, uint32_t mg, uint32_t sh) { return (int)(((uint64_t)(uint32_t)t * mg) >> sh); }
+// host side of mdiv: t / d = (t * mg) >> sh for 0 <= t < 2^31
+inline void mdiv_magic(uint32_t d, uint32_t* mg, uint32_t* sh) {
+    uint32_t s = 0;
+    while ((1ull << s) < d) ++s;
+    *sh = 31 + s;
+    *mg = (uint32_t)(((1ull << (31 + s)) + d - 1) / d);
+}
+// hi + lo of an fp32 pair in three instructions: hi = v_cvt_pk_f16_f32 (round to nearest even), lo = fp16(a - hi) by v_fma_mixlo / mixhi
+// (a - hi is exact in fp32: one rounding, the same bits as subtracting in fp32 and converting)
+__device__ __forceinline__ void split_pair(float a0, float a1, unsigned& hi, unsigned& lo) {
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(a0), "v"(a1));
+    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a0));
+    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(a1));
+}
+
 // ---- power-of-two scales of the "sp16" activations (csrc/conv_s16.hip: a tensor stored as the fp16 pieces hi + lo of 2^e x).
 // fp32 is scale-free, fp16 is not, so the exponent e FOLLOWS THE DATA, per image of the batch: an activation's range is the pair (amax, exp)
 // - `amax` a device pointer to one word per image, max |x| of that image of the activation as measured by the kernel that produced it
@@ -106,6 +127,7 @@ __host__ __device__ inline int sp16_act_exp(float amax) {
     const int a = SP16_TARGET_EXP - (e - 127);
     return a < -SP16_EXP_LIMIT ? -SP16_EXP_LIMIT : a > SP16_EXP_LIMIT ? SP16_EXP_LIMIT : a;
 }
+inline bool sp16_bad_exp(int e) { return e < -SP16_EXP_LIMIT || e > SP16_EXP_LIMIT; }
 __device__ __forceinline__ int sp16_resolve_exp(const float* amax, int exp) { return amax ? sp16_act_exp(*amax) : exp; }
 // 2^e as a float; NaN beyond the normal range, so that an absurd combination of ranges is loud instead of silently mis-scaled
 __device__ __forceinline__ float sp16_pow2(int e) {

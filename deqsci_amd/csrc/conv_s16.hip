@@ -35,66 +35,11 @@
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"
 
-#ifndef S16_RAW_NT
-#define S16_RAW_NT 0  // 1: the halo-tile DMA with the non-temporal hint (A/B: tools/s16_variants.sh)
-#endif
-#if S16_RAW_NT
-#define S16_NT " nt"
-#else
-#define S16_NT ""
-#endif
-#ifndef S16_EPI_LOCKSTEP
-#define S16_EPI_LOCKSTEP 0  // 1: both waves of a SIMD run their epilogue behind the last stage's barrier (the form before the out-of-step one; A/B)
-#endif
-#ifndef S16_INTERLEAVE
-#define S16_INTERLEAVE 1    // 0: a group's operand reads and DMA instruction in front of its six MFMAs, order left to hipcc (A/B)
-#endif
-#ifndef S16_ST_SEL
-#define S16_ST_SEL 0        // cache policy of the output stores (A/B, tools/s16_variants.sh): 0 nt, 1 default, 2 sc1, 3 sc0 sc1, 4 sc0 sc1 nt
-#endif
-#if S16_ST_SEL == 0
-#define S16_ST " nt"
-#elif S16_ST_SEL == 1
-#define S16_ST ""
-#elif S16_ST_SEL == 2
-#define S16_ST " sc1"
-#elif S16_ST_SEL == 3
-#define S16_ST " sc0 sc1"
-#else
-#define S16_ST " sc0 sc1 nt"
-#endif
-#ifndef S16_TAIL_XCD
-#define S16_TAIL_XCD 1      // 0: the last layer's tiles dealt round-robin over the XCDs (A/B)
-#endif
-#ifndef S16_ROWS4
-#define S16_ROWS4 1   // wave geometry inside the 8-wave workgroup: 1 (shipped since round 4) = FOUR pixel rows x ONE cout group per wave (54 operand
-                      // reads from LDS per stage and wave: 18 weight + 36 activation fragments; 242 registers); 0 = two pixel rows x both cout
-                      // groups (60: 36 + 24; 256 registers - the round-3 form, kept for the A/B: tools/s16_variants.sh "rows2:-DS16_ROWS4=0")
-#endif
-#ifndef S16_ZEROC
-#define S16_ZEROC S16_ROWS4   // 1: a tile's first MFMA into each accumulator takes the constant 0 as its C operand instead of 128 v_mov_b32 per tile and wave
-#endif
-#ifndef S16_TILE_VOFF
-#define S16_TILE_VOFF S16_ROWS4   // 1: the per-lane offsets of the halo-tile DMA are formed once per TILE (5 registers) instead of once per DMA instruction
-#endif
-#ifndef S16_ABL
-#define S16_ABL 0     // timing ablations only (results wrong; tools/s16_variants.sh): 1 = no DMA inside the stages, 2 = no wait + barrier at the end
-                      // of a stage, 4 = no epilogue, 8 = no LDS operand reads (registers reused), 16 = one EXTRA operand read per MFMA group
-                      // (S16_ROWS4: + 9 on 54 per stage; what a read costs with the MFMA operands unchanged)
-#endif
-
 namespace deqsci {
 namespace s16 {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-// hi + lo of an fp32 pair in three instructions (csrc/conv_w16.hip: split_pair): hi = v_cvt_pk_f16_f32 (round to nearest even), lo = fp16(a - hi) by
-// v_fma_mixlo / mixhi (a - hi is exact in fp32: one rounding - the bits of converting, converting back, subtracting and converting again)
-__device__ __forceinline__ void split_pair(float a0, float a1, unsigned& hi, unsigned& lo) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(a0), "v"(a1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(a1));
-}
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -112,10 +57,6 @@ constexpr int RAW_BUF = WAVES * RAW_INSTR * 1024;              // 40960 bytes
 constexpr int W_CHUNK = 9 * 2 * 2 * 1024;                      // 36864 bytes: [tap][hl][cout group][lane][8 halfs]
 constexpr uint32_t RAW_BIAS = 4096;                            // the descriptor starts this far below the image (see set_fetch_tile)
 constexpr uint32_t RAW_OOB = 0x80000000u;                      // beyond num_records: the hardware writes zeros
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int mdiv(int t, uint32_t mg, uint32_t sh) { return (int)(((uint64_t)(uint32_t)t * mg) >> sh); }
 
 // OUT_F32 = 0: sp16 output (the next 64->64 layer's input); 1: fp32 channels_last (n, H, W, 64) output (the consumer is not this kernel)
 // TRACK = 1: the range MEASUREMENT - the same arithmetic, but instead of storing y the launch folds max |y| (true units, pixels of the
@@ -142,10 +83,7 @@ __device__ __forceinline__ int mdiv(int t, uint32_t mg, uint32_t sh) { return (i
 // launch was not resident) - the launch never hangs, the result is invalid and says so.
 struct StackLayer { const char* w; const float* bias; int w_exp; int relu; };
 constexpr unsigned STACK_SPIN_LIMIT = 1u << 21;                // polls, one every ~0.1 us: a wait gives up after a quarter of a second
-#ifndef S16_STACK_POLLS
-#define S16_STACK_POLLS 8
-#endif
-constexpr int STACK_POLLS = S16_STACK_POLLS;                   // polls of the neighbours' words in flight
+constexpr int STACK_POLLS = 8;                                 // polls of the neighbours' words in flight
 constexpr int STACK_FLAG_STRIDE = 32;                          // words between two tiles' progress words: a 128-byte line each (256 pollers would queue on eight lines)
 template <int OUT_F32, int TRACK, int STACK>
 __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict__ x, const char* __restrict__ Wp, const float* __restrict__ bias,
@@ -210,18 +148,14 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
         asm volatile("" : "+v"(off));                          // (a select, not a branch around the arithmetic)
         return ok ? off : RAW_OOB;
     };
-    uint32_t voff[RAW_INSTR];                                  // (S16_TILE_VOFF) the lane offsets of the tile whose chunks are being fetched
+    uint32_t voff[RAW_INSTR];                                  // the lane offsets of the tile whose chunks are being fetched
     const uint32_t raw_lds = (uint32_t)(uintptr_t)(lds_char*)Raw, wt_lds = (uint32_t)(uintptr_t)(lds_char*)Wt;
     auto raw_piece = [&](int c, int buf, int j) __attribute__((always_inline)) {
         int w_ = wave;
         asm volatile("" : "+s"(w_));                           // (recomputed at every use: hoisted out of the tile loop, these scalars fill the SGPR file)
         const uint32_t soff = uniform((uint32_t)c * (uint32_t)HW * 64u);                               // 4 planes of 16 HW bytes per chunk
         const uint32_t m0v = uniform(raw_lds + (uint32_t)(buf * RAW_BUF + RAW_INSTR * w_ * 1024 + (j == 4 ? 4096 : 0)));
-#if S16_TILE_VOFF
-        const uint32_t voj = voff[j];
-#else
-        const uint32_t voj = fetch_lane_offset(j);             // (a dozen vector instructions, in the shadow of the group's MFMAs)
-#endif
+        const uint32_t voj = voff[j];                          // (formed once per tile, not once per DMA instruction)
 #define S16_RAW_LOAD(OFFS, MOD) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" OFFS MOD " lds" ::"s"(m0v), "v"(voj), "s"(rsrc), "s"(soff) : "m0")
         if (STACK) {                                           // agent-scope loads: what another XCD's workgroup wrote through a moment ago
             if (j == 0 || j == 4) S16_RAW_LOAD("", " sc1");
@@ -229,10 +163,10 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
             else if (j == 2) S16_RAW_LOAD(" offset:2048", " sc1");
             else S16_RAW_LOAD(" offset:3072", " sc1");
         } else {
-            if (j == 0 || j == 4) S16_RAW_LOAD("", S16_NT);
-            else if (j == 1) S16_RAW_LOAD(" offset:1024", S16_NT);
-            else if (j == 2) S16_RAW_LOAD(" offset:2048", S16_NT);
-            else S16_RAW_LOAD(" offset:3072", S16_NT);
+            if (j == 0 || j == 4) S16_RAW_LOAD("", "");
+            else if (j == 1) S16_RAW_LOAD(" offset:1024", "");
+            else if (j == 2) S16_RAW_LOAD(" offset:2048", "");
+            else S16_RAW_LOAD(" offset:3072", "");
         }
 #undef S16_RAW_LOAD
     };
@@ -266,36 +200,27 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
     // (The measuring launch keeps ONE chain - it only has to find the binary exponent of max |y| - and has its registers to spare.)
     constexpr int CH1 = TRACK ? 0 : 1;
     f32x16 acc[CH1 + 1][2][2];
-    // where the finished tile goes: descriptor of its image, per-lane offsets of rows r (S16_ROWS4: of the lane's COLUMN - the rows of a wave
-    // are wave-uniform and go into the stores' scalar offset, an out-of-image row is a uniform branch), first pixel row of the wave
+    // where the finished tile goes: descriptor of its image, per-lane offset of the lane's COLUMN (the rows of a wave are wave-uniform
+    // and go into the stores' scalar offset, an out-of-image row is a uniform branch), first pixel row of the wave
     // ... and the tile's scales: acc = 2^(e_in + w_exp) sum w x  ->  oscale acc + bscale bias = 2^e_out y (e of the tile's image)
     struct Done { i32x4 orsrc; uint32_t pix[2]; int oy0; float oscale, bscale; int img; };
     const int pl = lane & 31, kb = lane >> 5;
-#if S16_ROWS4
+    // (FOUR pixel rows x ONE cout group per wave: 54 operand reads from LDS per stage and wave - 18 weight + 36 activation fragments -, 242 registers;
+    // two pixel rows x both cout groups, the form before, read 60 and took all 256.)
     const int wg = wave & 1, wr4 = 4 * (wave >> 1);             // the wave's cout group and its first pixel row; acc[.][r >> 1][r & 1] is row r
     const lds_char* bbase = (const lds_char*)Raw + kb * PLANE_B + (wr4 * RAW_COLS + pl) * 16;
     const lds_char* abase = (const lds_char*)Wt + wg * 1024 + lane * 16;
-#else
-    const lds_char* bbase = (const lds_char*)Raw + kb * PLANE_B + (2 * wave * RAW_COLS + pl) * 16;
-    const lds_char* abase = (const lds_char*)Wt + lane * 16;
-#endif
 
     // One stage = chunk c of the current tile: Raw[c & 1], Wt[c & 1] hold it; chunk c + 1 (of this tile, or chunk 0 of the next one) is
     // fetched into the other buffers from inside the MFMA stream, one DMA instruction at a time.
     // ---- epilogue of one (r, g, gp) piece: acc[.][g][r][i] is cout 32 g + 8 (i >> 2) + 4 kb + (i & 3) of pixel (2 wave + r, pl)
     typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
     auto ep_piece = [&](const Done& d, int k, const f32x4 (&bz4)[2][4], float& tmax) __attribute__((always_inline)) {
-#if S16_ROWS4
         const int r = k >> 1, gp = k & 1, ga = r >> 1, ra = r & 1, gb = 0;   // (ga, ra): where row r sits in acc; gb: the bias set
         const int g = wg;                                      // (wave-uniform, not a constant: the stores' scalar offsets)
         const bool row_ok = d.oy0 + r < H;                     // (uniform)
         const uint32_t pixv = d.pix[0];
         const uint32_t rowoff = (uint32_t)((d.oy0 + r) * W) * (OUT_F32 ? 256u : 16u);
-#else
-        const int r = k >> 2, g = (k >> 1) & 1, gp = k & 1, ga = g, ra = r, gb = g;
-        const bool row_ok = true;
-        const uint32_t pixv = d.pix[r], rowoff = 0;
-#endif
         // values in PAIRS (k, k + 1): every step below is one packed instruction per pair where the hardware has one.  ReLU is the
         // NaN-propagating maximum (v_maximum3_f32) against 0, or against -inf when the layer has none: an overflow upstream (inf in the
         // fp16 pieces -> inf - inf in the accumulators) stays a NaN all the way to the output instead of being clamped to 0.
@@ -325,7 +250,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
             for (int q = 0; q < 2; ++q) {
                 const f32x4 o = {v2[2 * q].x, v2[2 * q].y, v2[2 * q + 1].x, v2[2 * q + 1].y};
                 const uint32_t so = uniform((uint32_t)((32 * g + 8 * (2 * gp + q)) * 4) + rowoff);
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" S16_ST "\n\ts_nop 1" ::"v"(o), "v"(pixv), "s"(d.orsrc), "s"(so) : "memory");
+                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(o), "v"(pixv), "s"(d.orsrc), "s"(so) : "memory");
             }
         } else {
             // sp16: split, pack, and trade halves with the lane 32 away so that each lane holds one whole 16-byte pixel of
@@ -354,8 +279,8 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
                 asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1\n\ts_nop 1" ::"v"(oh), "v"(pixv), "s"(d.orsrc), "s"(so_h) : "memory");
                 asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1\n\ts_nop 1" ::"v"(ol), "v"(pixv), "s"(d.orsrc), "s"(so_l) : "memory");
             } else {
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" S16_ST "\n\ts_nop 1" ::"v"(oh), "v"(pixv), "s"(d.orsrc), "s"(so_h) : "memory");
-                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen" S16_ST "\n\ts_nop 1" ::"v"(ol), "v"(pixv), "s"(d.orsrc), "s"(so_l) : "memory");
+                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(oh), "v"(pixv), "s"(d.orsrc), "s"(so_h) : "memory");
+                asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(ol), "v"(pixv), "s"(d.orsrc), "s"(so_l) : "memory");
             }
         }
     };
@@ -380,18 +305,8 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
             d.bscale = sp16_pow2(e_out);
             d.img = n;
         }
-#if S16_ROWS4
         d.oy0 = OUT_ROWS * by + wr4;
         d.pix[0] = d.pix[1] = ox >= W ? RAW_OOB : OUT_F32 ? (uint32_t)(ox * 256 + 16 * kb) : (uint32_t)((kb * (int)HW + ox) * 16);
-#else
-        d.oy0 = 0;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int oy = OUT_ROWS * by + 2 * wave + r;
-            const bool ok = oy < H && ox < W;
-            d.pix[r] = !ok ? RAW_OOB : OUT_F32 ? (uint32_t)((oy * W + ox) * 256 + 16 * kb) : (uint32_t)((kb * (int)HW + oy * W + ox) * 16);
-        }
-#endif
         return d;
     };
 
@@ -405,14 +320,13 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
         const int buf = c & 1, nb = buf ^ 1, cn = (c + 1) & 3;
         const lds_char* bb = bbase + buf * RAW_BUF;
         const lds_char* ab = abase + buf * W_CHUNK;
-#if S16_ROWS4
         // 9 groups (dx, dy) of 12 MFMAs: the wave's four pixel rows x three products of one tap.  Operands are read from LDS ONE group
-        // ahead (= the same twelve MFMAs ahead as in the other geometry): per group the tap's two weight fragments (hi, lo) and the halo
+        // ahead: per group the tap's two weight fragments (hi, lo) and the halo
         // rows that come into play - rows 0..3 at dy = 0, row 4 at dy = 1, row 5 at dy = 2 of every dx - into a ring of EIGHT row slots
         // (slot = (6 dx + row) mod 8: while (dx, 2) multiplies rows 2..5, the four dead slots take rows 0..3 of dx + 1).
         h8 Ah[2], Al[2], Bh[8], Bl[8];
         auto loads = [&](int i) __attribute__((always_inline)) {
-            if (i >= 9 || ((S16_ABL & 8) && i >= 1)) return;
+            if (i >= 9) return;
             const int dx = i / 3, dy = i % 3, tap = dy * 3 + dx;
             Ah[i & 1] = *reinterpret_cast<const lds_h8*>(ab + ((tap * 2 + 0) * 2) * 1024);
             Al[i & 1] = *reinterpret_cast<const lds_h8*>(ab + ((tap * 2 + 1) * 2) * 1024);
@@ -423,7 +337,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
             }
         };
         auto dma = [&](int j) __attribute__((always_inline)) {    // the next chunk: 10 DMA instructions, two per group in the first five groups
-            if (more && j < 2 * RAW_INSTR && !(S16_ABL & 1)) {
+            if (more && j < 2 * RAW_INSTR) {
                 // (STACK, last stage: the next chunk is chunk 0 of the next tile - maybe of the NEXT LAYER: its weights can come now, its
                 // activations only if the tiles it reads have been written: s3_raw)
                 if (j < RAW_INSTR) { if (!(STACK && c == 3) || s3_raw) raw_piece(cn, nb, j); }
@@ -434,20 +348,15 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
         loads(0);
         __builtin_amdgcn_sched_barrier(0);
         const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        h8 extra[2];                                           // (S16_ABL & 16)
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const int dx = i / 3, dy = i % 3;
-            const bool z1st = S16_ZEROC && c == 0 && i == 0;   // a tile's first MFMA into an accumulator: C = 0 (an inline constant)
+            const bool z1st = c == 0 && i == 0;                // a tile's first MFMA into an accumulator: C = 0 (an inline constant)
 #define S16_SLOT(r) ((6 * dx + dy + (r)) & 7)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[CH1][r >> 1][r & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[i & 1], Bh[S16_SLOT(r)], z1st ? zero16 : acc[CH1][r >> 1][r & 1], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             loads(i + 1);
-            if (S16_ABL & 16) {
-                extra[i & 1] = *reinterpret_cast<const lds_h8*>(bb + PLANE_B + i * 16);
-                if (i > 0) asm volatile("" ::"v"(extra[(i - 1) & 1]));
-            }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[CH1][r >> 1][r & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i & 1], Bl[S16_SLOT(r)], acc[CH1][r >> 1][r & 1], 0, 0, 0);
@@ -466,78 +375,16 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
             __builtin_amdgcn_sched_barrier(0);
 #undef S16_SLOT
         }
-        if (S16_ABL & 16) asm volatile("" ::"v"(extra[0]));
-#else
-        // 18 groups (dx, dy, g) of 6 MFMAs: the two pixel rows x three products of one tap and cout group.  Operands are read from LDS
-        // TWO groups ahead (software pipeline pinned by sched_barriers: left to itself hipcc reads each fragment one MFMA before its use
-        // and waits for it): per group two weight fragments (hi, lo) and, when a new halo row comes into play, its hi and lo fragments
-        // (rows 0, 1 at dy = 0, row 2 at dy = 1, row 3 at dy = 2 of every dx; kept per dx parity).
-        h8 Ah[3], Al[3], Bh[2][4], Bl[2][4];
-        auto loads = [&](int i) __attribute__((always_inline)) {
-            if (i >= 18 || ((S16_ABL & 8) && i >= 2)) return;
-            const int dx = i / 6, dy = (i % 6) >> 1, g = i & 1, tap = dy * 3 + dx;
-            Ah[i % 3] = *reinterpret_cast<const lds_h8*>(ab + ((tap * 2 + 0) * 2 + g) * 1024);
-            Al[i % 3] = *reinterpret_cast<const lds_h8*>(ab + ((tap * 2 + 1) * 2 + g) * 1024);
-            if (g == 0) {
-#pragma unroll
-                for (int rr = (dy == 0 ? 0 : dy + 1); rr <= dy + 1; ++rr) {
-                    Bh[dx & 1][rr] = *reinterpret_cast<const lds_h8*>(bb + (rr * RAW_COLS + dx) * 16);
-                    Bl[dx & 1][rr] = *reinterpret_cast<const lds_h8*>(bb + 2 * PLANE_B + (rr * RAW_COLS + dx) * 16);
-                }
-            }
-        };
-        S16_MARK(4);
-        loads(0);
-        loads(1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 18; ++i) {
-            const int dx = i / 6, dy = (i % 6) >> 1, g = i & 1;
-            // (hipcc left to itself issues a group's six MFMAs first and everything else behind them: the wave's next MFMA then waits for
-            // its own operand reads, DMA set-up and scalar arithmetic to issue - pinned here in the MFMAs' shadow instead)
-#pragma unroll
-            for (int r = 0; r < 2; ++r) acc[CH1][g][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[i % 3], Bh[dx & 1][dy + r], acc[CH1][g][r], 0, 0, 0);
-#if S16_INTERLEAVE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            loads(i + 2);
-#if S16_INTERLEAVE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int r = 0; r < 2; ++r) acc[CH1][g][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i % 3], Bl[dx & 1][dy + r], acc[CH1][g][r], 0, 0, 0);
-#if S16_INTERLEAVE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-            if (more && i < 2 * RAW_INSTR && !(S16_ABL & 1)) {   // the next chunk: 10 DMA instructions, one per group in the FIRST half of the
-                                                               // stage - the last one needs the second half (an HBM round trip) to land
-                if (i < RAW_INSTR) { if (!(STACK && c == 3) || s3_raw) raw_piece(cn, nb, i); }
-                else w_piece((STACK && c == 3) ? s3_w : Wp, cn, nb, i - RAW_INSTR);
-            }
-            shadow(i);                                         // (tile bookkeeping rides here, behind four of the group's MFMAs)
-#if S16_INTERLEAVE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int r = 0; r < 2; ++r) acc[0][g][r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i % 3], Bh[dx & 1][dy + r], acc[0][g][r], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
         S16_MARK(0);
-        if (!(S16_ABL & 2)) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            S16_MARK(1);
-            before_barrier();
-            lds_barrier();
-            S16_MARK(2);
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        S16_MARK(1);
+        before_barrier();
+        lds_barrier();
+        S16_MARK(2);
     };
     auto nothing = [] {};
     auto no_shadow = [](int) {};
 
-#ifdef S16_PRIO
-    if (wave >= 4) asm volatile("s_setprio 1");               // (A/B: static priority for the second-dispatched half of the workgroup)
-#endif
     const Done none = {(i32x4){0, 0, 0, 0}, {RAW_OOB, RAW_OOB}, 0, 0.0f, 0.0f, 0};
     char* const y_even = y;
     unsigned fbase = 0, fgiveup = 0;
@@ -554,17 +401,15 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
     if (wave == 0) bias_s[lane] = bias ? bias[lane] : 0.0f;     // (scaled per tile: the sp16 output of image i carries 2^e_out(i) y, so does its bias)
 #endif
     fetch_tile_uniform(t_first, x);
-#if S16_TILE_VOFF
 #pragma unroll
     for (int j = 0; j < RAW_INSTR; ++j) voff[j] = fetch_lane_offset(j);
-#endif
 #pragma unroll
     for (int j = 0; j < RAW_INSTR; ++j) { raw_piece(0, 0, j); w_piece(Wp, 0, 0, j); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     // (A "loader + 4" form - four compute waves, one per SIMD, each 4 pixel rows x 64 couts, and a fifth wave issuing all 76 DMA
     // instructions of a stage: 40 % less LDS operand traffic, no compute wave ever at the memory pipeline's door - was built and measured
-    // (tools/ubench/variants/conv_s16_with_loader_variant.hip, -DS16_V2): 212 us against 193 us.  Five waves put two on one SIMD, so the
+    // (conv_s16_with_loader_variant.hip, last present at commit 666c1e4): 212 us against 193 us.  Five waves put two on one SIMD, so the
     // register budget stays 256 and only one accumulation chain fits; and a wave alone on its SIMD has nobody to cover its stalls.)
     // (Spreading a tile's epilogue over the MFMA stream of the next tile - a second accumulator set, one piece behind every other group -
     // was built and measured: 192 us against 187 us at 64 x 128 x 128.  On random data this kernel runs against the chip's POWER limit
@@ -595,14 +440,6 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
         const int L_next = L + (new_layer ? 1 : 0);
         const bool poll = STACK && next && L_next > 0;         // (a tile of layer 0 reads the run's input: nothing to wait for)
         if (STACK && new_layer && next) Wnx = layers[L + 1].w;
-#if !(S16_ZEROC && S16_ROWS4)
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[0][g][r][i] = acc[CH1][g][r][i] = 0.0f;
-#endif
         stage(0, true, nothing, no_shadow);
         // (STACK) behind stage 0's wait and barrier every store of the tile before has been acknowledged: its word goes out
         stage(1, true, nothing, [&](int i) __attribute__((always_inline)) {
@@ -631,9 +468,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
                 asm volatile("global_load_dword %0, %1, off sc1" : "=v"(pv) : "v"(pf) : "memory");
             }
             if (i == 10 && next) fetch_tile_uniform(t_next, (STACK && new_layer) ? y : x);
-#if S16_TILE_VOFF
             if (i >= 11 && i < 11 + RAW_INSTR) voff[i - 11] = fetch_lane_offset(i - 11);     // (this tile's last raw pieces went out in groups 0..4)
-#endif
         });
         bool ready = true;
         if (STACK) {
@@ -648,37 +483,23 @@ __global__ __launch_bounds__(TBW, 2) void conv_s16_kernel(const char* __restrict
         // a tile: tools/s16_stamps.py, profiles/r03_s16_stamps_before.txt).
         Done d = none;
         auto epilogue = [&]() __attribute__((always_inline)) {
-            if (!(S16_ABL & 4) || relu == 77) {
-                // the lane's 32 bias values in one burst of LDS reads (operand registers are free here): read piece by piece, each read
-                // was a round trip through an LDS the partner wave keeps busy - 16 of them made the epilogue twice as long
-                f32x4 bz4[2][4];
-                const __attribute__((address_space(3))) float* bsl = (const __attribute__((address_space(3))) float*)bias_s + (STACK ? 64 * (L & 1) : 0);
-#if S16_ROWS4
+            // the lane's 32 bias values in one burst of LDS reads (operand registers are free here): read piece by piece, each read
+            // was a round trip through an LDS the partner wave keeps busy - 16 of them made the epilogue twice as long
+            f32x4 bz4[2][4];
+            const __attribute__((address_space(3))) float* bsl = (const __attribute__((address_space(3))) float*)bias_s + (STACK ? 64 * (L & 1) : 0);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) bz4[0][q] = bz4[1][q] = *reinterpret_cast<const lds_f32x4*>(bsl + 32 * wg + 8 * q + 4 * kb) * d.bscale;
-#else
+            for (int q = 0; q < 4; ++q) bz4[0][q] = bz4[1][q] = *reinterpret_cast<const lds_f32x4*>(bsl + 32 * wg + 8 * q + 4 * kb) * d.bscale;
+            float tmax = 0.0f;
 #pragma unroll
-                for (int g = 0; g < 2; ++g)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) bz4[g][q] = *reinterpret_cast<const lds_f32x4*>(bsl + 32 * g + 8 * q + 4 * kb) * d.bscale;
-#endif
-                float tmax = 0.0f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) ep_piece(d, k, bz4, tmax);
-                if (TRACK) {                                   // (the measuring launch only: one atomic per tile and wave, on the tile's image)
-                    const uint32_t tb = sp16_wave_max_bits(tmax);
-                    if (lane == 0 && track) atomicMax(reinterpret_cast<unsigned int*>(track) + d.img, tb);
-                }
+            for (int k = 0; k < 8; ++k) ep_piece(d, k, bz4, tmax);
+            if (TRACK) {                                   // (the measuring launch only: one atomic per tile and wave, on the tile's image)
+                const uint32_t tb = sp16_wave_max_bits(tmax);
+                if (lane == 0 && track) atomicMax(reinterpret_cast<unsigned int*>(track) + d.img, tb);
             }
         };
-#if S16_EPI_LOCKSTEP
-        stage(3, next, nothing, [&](int i) __attribute__((always_inline)) { if (i == 12) d = tile_done(t_cur); });
-        epilogue();
-#else
         stage(3, next, [&]() __attribute__((always_inline)) { if (wave < 4) epilogue(); },
               [&](int i) __attribute__((always_inline)) { if (i == 12) d = tile_done(t_cur); });
         if (wave >= 4) epilogue();
-#endif
         S16_MARK(3);
         if (STACK) {
             const unsigned done_v = fbase + (unsigned)(L + 1);     // this tile's word once its stores have landed
@@ -830,11 +651,7 @@ __global__ __launch_bounds__(256) void tail_s16_kernel(const char* __restrict__ 
     // Workgroup b runs on XCD b % 8: every XCD takes a contiguous range of tiles (image-major, then rows), so that the two halo rows a
     // tile shares with the tile above and below it are re-read from THAT XCD's L2 while they are hot - with tiles dealt round-robin
     // over the XCDs every halo row came from HBM again (10 rows fetched per 8 produced)
-#if S16_TAIL_XCD
     const int per_xcd = (n_tiles + 7) >> 3, t = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
-#else
-    const int t = (int)blockIdx.x;
-#endif
     if (t >= n_tiles) return;
     const int n = t / (tiles_x * tiles_y), rt = t - n * (tiles_x * tiles_y), by = rt / tiles_x;
     const int r0 = by * TL_H, c0 = (rt - by * tiles_x) * TL_W;
@@ -952,13 +769,7 @@ __global__ __launch_bounds__(256) void tail_s16_kernel(const char* __restrict__ 
 // steps); the B operand (k x 32 positions) is GATHERED: lane (position, k block) reads its eight taps from the full-resolution patch /
 // the sigma plane in LDS, multiplies by 2^8 and splits them into hi + lo fp16 on the fly; the weight operands (12 fragments) stay in
 // registers.  18 f16 MFMAs per 32 positions instead of 96 fp32 ones: the layer is left with its 256 B/position store.
-#ifndef S16_HEAD_NT
-#define S16_HEAD_NT 1        // (A/B) the p32 head's stores: 1 = nt (streaming), 0 = default policy (the lines stay in the XCD's L2 / the Infinity Cache)
-#endif
-#ifndef S16_HEAD_ROWS
-#define S16_HEAD_ROWS 8      // (A/B) rows of half-resolution positions per workgroup tile of head_s16_kernel
-#endif
-constexpr int HS_H = S16_HEAD_ROWS, HS_W = 32, HS_P = 2 * HS_H + 4, HS_Q = 2 * HS_W + 4, HS_QS = HS_Q + 2, HS_SW = HS_W + 2, HS_SS = HS_SW + 1;   // 20 x 68 patch, 10 x 34 sigma plane
+constexpr int HS_H = 8, HS_W = 32, HS_P = 2 * HS_H + 4, HS_Q = 2 * HS_W + 4, HS_QS = HS_Q + 2, HS_SW = HS_W + 2, HS_SS = HS_SW + 1;   // 20 x 68 patch, 10 x 34 sigma plane
 template <int TRACK, int P32>   // TRACK = 1: additionally folds max |output| into *track (the measuring launch of the first f-call; the per-value maximum
                                 // costs the gather-bound kernel a quarter of its time, so the other 180 calls run without it); P32 = 1: the output is
                                 // "p32" (csrc/conv_w16.hip): 2^e y as fp32, the lane's four consecutive couts = its pixel's 16 bytes of plane 2 b8 + kb
@@ -1089,11 +900,7 @@ __global__ __launch_bounds__(256) void head_s16_kernel(const float* __restrict__
                         if (TRACK && pix != RAW_OOB) tmax = fmaxf(tmax, t[k]);
                     }
                     const uint32_t so = uniform((uint32_t)(2 * (4 * g + gq)) * (uint32_t)HW * 16u);
-#if S16_HEAD_NT
                     asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(t), "v"(pix), "s"(orsrc), "s"(so) : "memory");
-#else
-                    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(t), "v"(pix), "s"(orsrc), "s"(so) : "memory");
-#endif
                 }
             continue;
         }
@@ -1135,22 +942,13 @@ __global__ __launch_bounds__(256) void head_s16_kernel(const float* __restrict__
 
 using namespace deqsci;
 
-static void s16_magic(uint32_t d, uint32_t* mg, uint32_t* sh) {
-    uint32_t s = 0;
-    while ((1ull << s) < d) ++s;
-    *sh = 31 + s;
-    *mg = (uint32_t)(((1ull << (31 + s)) + d - 1) / d);
-}
-
-static bool bad_exp(int e) { return e < -SP16_EXP_LIMIT || e > SP16_EXP_LIMIT; }
-
 extern "C" int deqsci_conv3x3_c64_split16(const void* x_sp16, const void* w_packed, const float* bias, void* y, int64_t n, int64_t H, int64_t W,
                                           int relu, int w_exp, const float* in_amax, int in_exp, const float* out_amax, int out_exp,
                                           float* track_amax, int out_f32, deqsci_stream_t stream, void* start_event, void* stop_event) {
     if (!x_sp16 || !w_packed || (!y && !track_amax)) return DEQSCI_ERR_NULL;             // (a measuring launch writes no y: it may be NULL)
     if ((start_event == nullptr) != (stop_event == nullptr)) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
-    if (x_sp16 == y || (out_f32 != 0 && out_f32 != 1) || bad_exp(w_exp) || bad_exp(in_exp) || bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (x_sp16 == y || (out_f32 != 0 && out_f32 != 1) || sp16_bad_exp(w_exp) || sp16_bad_exp(in_exp) || sp16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (track_amax && out_f32) return DEQSCI_ERR_UNSUPPORTED;        // (the range measurement serves the sp16 output)
     if (!aligned16(x_sp16) || !aligned16(w_packed) || !aligned16(y)) return DEQSCI_ERR_ALIGN;
     const int64_t tiles_x = ceil_div(W, s16::OUT_COLS), tiles_y = ceil_div(H, s16::OUT_ROWS);
@@ -1161,8 +959,8 @@ extern "C" int deqsci_conv3x3_c64_split16(const void* x_sp16, const void* w_pack
     const int64_t resident = (int64_t)num_cus();
     const dim3 grid((unsigned)(n_tiles < resident ? n_tiles : resident));
     uint32_t mg_img, sh_img, mg_tx, sh_tx;
-    s16_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
-    s16_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
+    mdiv_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
+    mdiv_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
     hipEvent_t ev0 = static_cast<hipEvent_t>(start_event), ev1 = static_cast<hipEvent_t>(stop_event);
 #define S16_LAUNCH(KERNEL)                                                                                                                  \
     hipExtLaunchKernelGGL(KERNEL, grid, dim3(s16::TBW), 0, st, ev0, ev1, 0, static_cast<const char*>(x_sp16), static_cast<const char*>(w_packed), \
@@ -1184,7 +982,7 @@ extern "C" int deqsci_conv3x3_c64_split16_stack(const void* x_sp16, void* y_even
     if (!x_sp16 || !y_even || !layers || !flags || (n_layers > 1 && !y_odd)) return DEQSCI_ERR_NULL;
     if ((start_event == nullptr) != (stop_event == nullptr)) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0 || n_layers <= 0 || (ranges && (range_stride < n || range_stride > INT32_MAX))) return DEQSCI_ERR_SHAPE;
-    if (x_sp16 == y_even || x_sp16 == y_odd || y_even == y_odd || n_layers > 64 || bad_exp(in_exp) || bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (x_sp16 == y_even || x_sp16 == y_odd || y_even == y_odd || n_layers > 64 || sp16_bad_exp(in_exp) || sp16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(x_sp16) || !aligned16(y_even) || !aligned16(y_odd) || (reinterpret_cast<uintptr_t>(layers) & 7u) || (reinterpret_cast<uintptr_t>(flags) & 3u))
         return DEQSCI_ERR_ALIGN;
     const int64_t tiles_x = ceil_div(W, s16::OUT_COLS), tiles_y = ceil_div(H, s16::OUT_ROWS);
@@ -1199,8 +997,8 @@ extern "C" int deqsci_conv3x3_c64_split16_stack(const void* x_sp16, void* y_even
     const int64_t resident = fit < (int64_t)num_cus() ? fit : (int64_t)num_cus();
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t mg_img, sh_img, mg_tx, sh_tx;
-    s16_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
-    s16_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
+    mdiv_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
+    mdiv_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
     hipEvent_t ev0 = static_cast<hipEvent_t>(start_event), ev1 = static_cast<hipEvent_t>(stop_event);
     hipExtLaunchKernelGGL((s16::conv_s16_kernel<0, 0, 1>), dim3((unsigned)(n_tiles < resident ? n_tiles : resident)), dim3(s16::TBW), 0, st, ev0, ev1, 0, static_cast<const char*>(x_sp16),
                           static_cast<const char*>(nullptr), static_cast<const float*>(nullptr), static_cast<char*>(y_even), (int)H, (int)W, 0, 0, ranges,
@@ -1214,7 +1012,7 @@ extern "C" int deqsci_f32_to_split16(const float* x_nhwc, void* y_sp16, int64_t 
                                      deqsci_stream_t stream) {
     if (!x_nhwc || !y_sp16) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
-    if (bad_exp(exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (sp16_bad_exp(exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(x_nhwc) || !aligned16(y_sp16)) return DEQSCI_ERR_ALIGN;
     const int64_t total = n * H * W * 8;
     hipLaunchKernelGGL(s16::f32_to_sp16_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x_nhwc,
@@ -1239,7 +1037,7 @@ static int tail_s16_impl(const void* x_sp16, const void* w_packed, float* out, i
                          int in_exp, deqsci_stream_t stream) {
     if (!x_sp16 || !w_packed || !out) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
-    if (n > 65535 || H > (1 << 20) || W > (1 << 20) || bad_exp(w_exp) || bad_exp(in_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (n > 65535 || H > (1 << 20) || W > (1 << 20) || sp16_bad_exp(w_exp) || sp16_bad_exp(in_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(x_sp16) || !aligned16(w_packed) || !aligned16(out)) return DEQSCI_ERR_ALIGN;
     const int64_t tiles_x = ceil_div(W, s16::TL_W), tiles_y = ceil_div(H, s16::TL_H), n_tiles = n * tiles_x * tiles_y;
     if (n_tiles > (1 << 30)) return DEQSCI_ERR_UNSUPPORTED;
@@ -1278,7 +1076,7 @@ static int head_s16_impl(const float* x, const void* w_packed, const float* sigm
     if (n <= 0 || H <= 0 || W <= 0 || sigma_stride < 0) return DEQSCI_ERR_SHAPE;
     const int64_t pitch = P32 ? 64 * ceil_div(W, 64) : W;
     if (n > 65535 || H > (1 << 20) || W > (1 << 20) || H * pitch * 256 + 16 > (int64_t)s16::RAW_OOB) return DEQSCI_ERR_UNSUPPORTED;
-    if (bad_exp(w_exp) || bad_exp(in_exp) || bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (sp16_bad_exp(w_exp) || sp16_bad_exp(in_exp) || sp16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(w_packed) || !aligned16(h_out)) return DEQSCI_ERR_ALIGN;
     const dim3 grid((unsigned)ceil_div(W, s16::HS_W), (unsigned)ceil_div(H, s16::HS_H), (unsigned)n);
     if (track_amax)

@@ -10,7 +10,7 @@
 // registers the positions are split over waves and every output crosses the LDS once more (DESIGN section 6.5 has the arithmetic).  The
 // nested form holds 4 accumulators per 2 outputs, transforms ROWS, and its operand traffic is the direct kernel's.
 //
-// Two forms were built (profiles/r05_w16_form1_*; tools/ubench/variants/conv_w16_form1_4waves_variant.hip).  Form 1 - FOUR waves of 512
+// Two forms were built (profiles/r05_w16_form1_*; conv_w16_form1_4waves_variant.hip, last present at commit 666c1e4).  Form 1 - FOUR waves of 512
 // registers, a wave = two output rows x 64 couts, each halo row transformed once per wave - was instruction-issue bound: a wave alone on
 // its SIMD issues one instruction every 5-8 cycles (tools/ubench/mfma_f16_fillers.hip: v_sub_f32 5, v_cvt_pk_f16_f32 / v_fma_mix* 8,
 // ds_read_b128 ~8, an LDS-DMA instruction 60+), its ~550 instructions per 72 MFMAs took 4100-4300 cycles against the MFMAs' 2304, and the
@@ -42,34 +42,6 @@
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"
 
-#ifndef W16_PHASES
-#define W16_PHASES 1        // (A/B) > 1: the workgroups start in this many phases spread over W16_SPREAD shader cycles (see the kernel's prologue)
-#endif
-#ifndef W16_SPREAD
-#define W16_SPREAD 40000    // ~ one tile
-#endif
-#ifndef W16_PRIO
-#define W16_PRIO 0          // (A/B) issue priority of the two waves of a SIMD (w, w + 4): 0 = left to the arbiter (the older wave, 0-3, wins), 1 = waves 4-7
-                            // at s_setprio 1 throughout, 2 = the winner alternates half-stage by half-stage, 3 = group by group
-#endif
-#ifndef W16_DMA4
-#define W16_DMA4 0          // (A/B) 1: waves 0-3 - the older wave of every SIMD, which the arbiter serves first and which then waits ~1300 cycles per
-                            // half-stage at the barrier for its partner - issue ALL the LDS-DMA instructions (two per slot), waves 4-7 none
-#endif
-#ifndef W16_EPI_PK
-#define W16_EPI_PK 1        // (A/B) 0: round 5 - the epilogue's additions and multiply-adds one cout at a time
-#endif
-#ifndef W16_STORE_NOW
-#define W16_STORE_NOW 1     // (A/B) 0: round 5 - a tile's outputs always wait for the end of its epilogue
-#endif
-#ifndef W16_XF_PK
-#define W16_XF_PK 0         // (A/B) 1: the input transform's subtractions as packed fp32 (two channels per instruction, the same bits)
-#endif
-#ifndef W16_ABL
-#define W16_ABL 0     // timing ablations only (results wrong): 1 = no DMA inside the half-stages, 2 = no transform, 4 = no epilogue, 8 = epilogue without its stores,
-                      // 16 = what-if: the transform shared through LDS, 32 = what-if: the instruction mix of 4 x 64 tiles with one cout group per wave (see xf_step)
-#endif
-
 namespace deqsci {
 namespace w16 {
 
@@ -95,17 +67,6 @@ constexpr int W_HALF = W_FRAGS * 1024;                         // 24576 bytes
 constexpr int W_INSTR = W_FRAGS / WAVES;                       // 3 per wave and half-stage
 constexpr uint32_t RAW_OOB = 0x80000000u;                      // beyond num_records: the hardware writes zeros
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int mdiv(int t, uint32_t mg, uint32_t sh) { return (int)(((uint64_t)(uint32_t)t * mg) >> sh); }
-
-// hi + lo of an fp32 pair in three instructions: hi = v_cvt_pk_f16_f32 (round to nearest even), lo = fp16(a - hi) by v_fma_mixlo / mixhi
-// (a - hi is exact in fp32: one rounding, the same bits as subtracting in fp32 and converting)
-__device__ __forceinline__ void split_pair(float a0, float a1, unsigned& hi, unsigned& lo) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(a0), "v"(a1));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a0));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(a1));
-}
 // (single v_sub / v_add by inline asm: left to itself hipcc pairs them into v_pk_add_f32, 19 cycles beside an MFMA against 2 x 5)
 __device__ __forceinline__ float sub1(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float add1(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -137,7 +98,6 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     __shared__ uint32_t poll_s[64];                            // (STACK) the words wave 0 polled in the shadow of half-stage 4 (by LDS-DMA: no register
                                                                // waits for a load that lands a half-stage later)
     __shared__ uint32_t voff_s[RAW_INSTR * TBW];               // per-lane global offsets of the halo-tile DMA instructions (see voff_set)
-    __shared__ __attribute__((aligned(16))) char abl_v[(W16_ABL & 48) ? 4096 : 16];      // (W16_ABL & 16: the what-if's dummy V tile)
     const int lane = (int)(threadIdx.x & 63);
     const int wave = (int)uniform((uint32_t)(threadIdx.x >> 6));
     int t_first, t_step, t_end;
@@ -155,13 +115,9 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     const int64_t HW = (int64_t)H * Wq;                        // pixels of a plane
     const int pl = lane & 31, kb = lane >> 5;
     const bool six = wave < RAW_TOTAL - 8 * (RAW_INSTR - 1);   // (uniform) this wave issues a sixth halo-tile instruction
-    const bool mover = !W16_DMA4 || wave < 4;                  // (uniform) this wave issues LDS-DMA instructions at all
-    // "everything but the halo tile issued last has landed": the instructions of one halo tile that may stay in flight (W16_DMA4: waves 0 and
-    // 1 issue 11 of the 42, waves 2 and 3 ten; the others have only stores in flight and keep the old count)
+    // "everything but the halo tile issued last has landed": the instructions of one halo tile that may stay in flight
     auto wait_all_but_a_tile = [&]() __attribute__((always_inline)) {
-        if (W16_DMA4 && wave < 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RAW_INSTR - 1) : "memory");
-        else if (W16_DMA4 && wave < 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RAW_INSTR - 2) : "memory");
-        else if (six) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RAW_INSTR) : "memory");
+        if (six) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RAW_INSTR) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RAW_INSTR - 1) : "memory");
     };
 
@@ -180,10 +136,10 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
         ft_py0 = OUT_ROWS * by - 1;
         ft_px0 = OUT_COLS * bx - 1;
     };
-    auto fetch_lane_offset = [&](int j) __attribute__((always_inline)) -> uint32_t {       // (W16_DMA4: j = 2 x slot + which of its two instructions)
+    auto fetch_lane_offset = [&](int j) __attribute__((always_inline)) -> uint32_t {
         int w_ = wave;
         asm volatile("" : "+s"(w_));                           // (recomputed at every use: once per tile and instruction)
-        const int s = W16_DMA4 ? 64 * (8 * (j >> 1) + w_ + 4 * (j & 1)) + lane : 64 * (8 * j + w_) + lane;
+        const int s = 64 * (8 * j + w_) + lane;
         const int p = (s * 6356) >> 22;                        // s / 660 for s < 2816
         const int q = s - p * RAW_PIX;
         const int row = (q * 993) >> 16, rem = q - row * RAW_COLS;           // q / 66 for q < 660
@@ -196,35 +152,14 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     };
     // the lane offsets of the tile whose chunks are being fetched live in LDS (registers the accumulators need): written once per tile,
     // read one DMA instruction ahead
-    uint32_t vo_next = 0, vo_next1 = 0;
-    auto voff_set = [&](int j, uint32_t v) __attribute__((always_inline)) {
-        if (W16_DMA4) voff_s[j * (TBW / 2) + (int)(threadIdx.x & (TBW / 2 - 1))] = v;
-        else voff_s[j * TBW + (int)threadIdx.x] = v;
-    };
-    auto voff_get = [&](int j) __attribute__((always_inline)) {
-        if (W16_DMA4) {
-            vo_next = voff_s[(2 * j) * (TBW / 2) + (int)(threadIdx.x & (TBW / 2 - 1))];
-            vo_next1 = voff_s[(2 * j + 1) * (TBW / 2) + (int)(threadIdx.x & (TBW / 2 - 1))];
-        } else vo_next = voff_s[j * TBW + (int)threadIdx.x];
-    };
+    uint32_t vo_next = 0;
+    auto voff_set = [&](int j, uint32_t v) __attribute__((always_inline)) { voff_s[j * TBW + (int)threadIdx.x] = v; };
+    auto voff_get = [&](int j) __attribute__((always_inline)) { vo_next = voff_s[j * TBW + (int)threadIdx.x]; };
     const uint32_t raw_lds = (uint32_t)(uintptr_t)(lds_char*)Raw, wt_lds = (uint32_t)(uintptr_t)(lds_char*)Wt;
     auto raw_piece = [&](int c, int buf, int j) __attribute__((always_inline)) {
         int w_ = wave;
         asm volatile("" : "+s"(w_));
         const uint32_t soff = uniform((uint32_t)c * (uint32_t)HW * 64u);                               // 4 planes of 16 HW bytes per chunk
-        if (W16_DMA4) {                                        // instructions 8 j + w and 8 j + w + 4, waves 0-3 only
-            const uint32_t vo[2] = {vo_next, vo_next1};
-            if (j + 1 < RAW_INSTR) voff_get(j + 1);
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const int I = 8 * j + w_ + 4 * p;
-                if (I >= RAW_TOTAL) continue;                  // (uniform)
-                const uint32_t m0p = uniform(raw_lds + (uint32_t)(buf * RAW_BUF + I * 1024));
-                if (STACK) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds" ::"s"(m0p), "v"(vo[p]), "s"(rsrc), "s"(soff) : "m0");
-                else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(m0p), "v"(vo[p]), "s"(rsrc), "s"(soff) : "m0");
-            }
-            return;
-        }
         const uint32_t m0v = uniform(raw_lds + (uint32_t)(buf * RAW_BUF + (8 * j + w_) * 1024));
         const uint32_t voj = vo_next;                          // (voff_get(j) ran a gap ago)
         if (j + 1 < RAW_INSTR) voff_get(j + 1);
@@ -236,7 +171,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     auto w_piece = [&](const char* Wl, int hs, int buf, int j) __attribute__((always_inline)) {
         int w_ = wave;
         asm volatile("" : "+s"(w_));
-        const uint32_t off = (uint32_t)(((W16_DMA4 ? 2 * W_INSTR : W_INSTR) * w_ + j) * 1024);        // (W16_DMA4: j = 0 .. 5, waves 0-3)
+        const uint32_t off = (uint32_t)((W_INSTR * w_ + j) * 1024);
         const uint64_t g = (uint64_t)(Wl + (int64_t)hs * W_HALF) + off;
         const uint32_t m0v = uniform(wt_lds + (uint32_t)(buf * W_HALF) + off);
         const uint64_t gs = ((uint64_t)uniform((uint32_t)(g >> 32)) << 32) | uniform((uint32_t)g);
@@ -276,14 +211,6 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
         return __builtin_bit_cast(float, u);
     };
     auto t_xf = [&](int s, int hh) __attribute__((always_inline)) {  // s = 0, 1: channels 2 s, 2 s + 1 of the half
-#if W16_XF_PK
-        {
-            const f32x2 d0 = {px(0, 2 * s), px(0, 2 * s + 1)}, d1 = {px(1, 2 * s), px(1, 2 * s + 1)}, d2 = {px(2, 2 * s), px(2, 2 * s + 1)};
-            const f32x2 a = hh == 0 ? pk_sub(d0, d2) : pk_sub(d1, d0), b = hh == 0 ? pk_add(d1, d2) : pk_sub(d0, d2);
-            va[2 * s] = a[0]; va[2 * s + 1] = a[1]; vb[2 * s] = b[0]; vb[2 * s + 1] = b[1];
-            return;
-        }
-#endif
 #pragma unroll
         for (int k = 2 * s; k < 2 * s + 2; ++k) {
             if (hh == 0) { va[k] = sub1(px(0, k), px(2, k)); vb[k] = add1(px(1, k), px(2, k)); }
@@ -299,41 +226,6 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     };
     // the micro-step of gap i (0 .. 11) of a group:  [load f0][-][-][-][xf][xf][split + load f1][split][xf][xf][split][split]
     auto xf_step = [&](int i, int rb, int rho, int hh, int ns) __attribute__((always_inline)) {
-        if (W16_ABL & 2) return;
-        if (W16_ABL & 32) {
-            // WHAT-IF (results wrong): the instruction mix of block tiles of 4 x 64 pixels with a wave = one row x ONE cout group (the geometry whose
-            // shared V fits the LDS), per 36 MFMAs: two row transforms instead of three (78 vector instructions, 12 raw
-            // reads), 6 V writes and 24 V reads from the dummy tile beside the 24 weight-fragment reads
-            __attribute__((address_space(3))) u32x4* dv = (__attribute__((address_space(3))) u32x4*)abl_v + lane;
-            if (rho == 2) {
-                if (i < 8) { u32x4 t_ = dv[64 * (i & 3)]; asm volatile("" :: "v"(t_)); }
-                if (i == 0) { Vh[ns][0] = dv[0]; Vl[ns][0] = dv[64]; Vh[ns][1] = dv[128]; Vl[ns][1] = dv[192]; }
-                return;
-            }
-            if (i < 8) { u32x4 t_ = dv[64 * (i & 3)]; asm volatile("" :: "v"(t_)); }      // (16 more V reads over the two transformed rows)
-            if (i == 11) {
-                t_split(1, ns, 1);
-                dv[0] = Vh[ns][0]; dv[64] = Vl[ns][0]; dv[128] = Vh[ns][1];
-                return;
-            }
-        }
-        if (W16_ABL & 16) {
-            // WHAT-IF (results wrong): every halo row transformed ONCE per workgroup and shared through LDS - a wave transforms 1.25 rows per
-            // half-stage instead of 3 (its middle row; the first row of its successor only in waves 0 and 1) and WRITES their V (4 x 16 bytes per
-            // lane) to LDS; the rows it skips it READS there (4 x 16 bytes).  The LDS the real thing needs (80 KB of V) does not exist beside
-            // the raw tiles: all waves use one 4 KB dummy tile, so this prices the instruction streams only
-            const bool mine = rho == 1 || (rho == 0 && wave < 2);
-            __attribute__((address_space(3))) u32x4* dv = (__attribute__((address_space(3))) u32x4*)abl_v + lane;
-            if (!mine) {
-                if (i == 0) { Vh[ns][0] = dv[0]; Vl[ns][0] = dv[64]; Vh[ns][1] = dv[128]; Vl[ns][1] = dv[192]; }
-                return;
-            }
-            if (i == 11) {
-                t_split(1, ns, 1);
-                dv[0] = Vh[ns][0]; dv[64] = Vl[ns][0]; dv[128] = Vh[ns][1]; dv[192] = Vl[ns][1];
-                return;
-            }
-        }
         if (i == 0) t_load(rb, rho, hh, 0);
         else if (i == 4 || i == 5) t_xf(i - 4, hh);
         else if (i == 6) { t_split(0, ns, 0); t_load(rb, rho, hh, 1); }       // (the half's pixels are dead once its V is formed)
@@ -404,25 +296,19 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
         // DMA instruction k of the half-stage (group 2 only): the weights of half-stage hs + 2 (wnext: there is one; the next tile's come from
         // s3_w, its layer's), then - h = 1 - the halo tile (rnext: there is one and the tiles it reads are written)
         auto dma = [&](int k) __attribute__((always_inline)) {
-            if ((W16_ABL & 1) || !mover) return;
             if (k < W_INSTR) {
-                if (wnext) {
-                    if (W16_DMA4) { w_piece((STACK && hs >= 6) ? s3_w : Wp, (hs + 2) & 7, wb, 2 * k); w_piece((STACK && hs >= 6) ? s3_w : Wp, (hs + 2) & 7, wb, 2 * k + 1); }
-                    else w_piece((STACK && hs >= 6) ? s3_w : Wp, (hs + 2) & 7, wb, k);
-                }
+                if (wnext) w_piece((STACK && hs >= 6) ? s3_w : Wp, (hs + 2) & 7, wb, k);
             } else if (h == 1 && k < W_INSTR + RAW_INSTR) { if (rnext) raw_piece((c + 2) & 3, c & 1, k - W_INSTR); }
         };
         const f32x16 zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (W16_PRIO == 2) { if (((wave >> 2) ^ hs) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int slot = (3 * hs + dy) & 1;
-            if (W16_PRIO == 3) { if (((wave >> 2) ^ (3 * hs + dy)) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
             if (dy == 2) {
                 W16_MARK(h);
                 // what the successor reads has to be there: its weights (issued a half-stage ago) and - h = 1 - its halo chunk (two ago); a halo
                 // tile issued behind the weights in the half-stage before has another half-stage to land
-                if (h == 0 && raw_prev && !(W16_ABL & 1)) wait_all_but_a_tile();
+                if (h == 0 && raw_prev) wait_all_but_a_tile();
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 W16_MARK(2 + h);
                 before_barrier();
@@ -443,7 +329,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
                 if (i >= 4 && i < 8) loadA(dy < 2 ? wb : wb ^ 1, dy < 2 ? dy + 1 : 0, 1, ((i - 4) >> 1) & 1, (i - 4) & 1);
                 if (i >= 8) loadA(dy < 2 ? wb : wb ^ 1, dy < 2 ? dy + 1 : 0, 0, ((i - 8) >> 1) & 1, (i - 8) & 1);
                 if (dy == 2) {
-                    if (h == 1 && i == 0 && rnext && mover) voff_get(0);
+                    if (h == 1 && i == 0 && rnext) voff_get(0);
                     if (i >= 1 && i <= 3) dma(i - 1);                  // weights
                     if (i >= 4 && i <= 9) dma(i - 1);                  // halo tile (h = 1)
                 }
@@ -457,14 +343,12 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     // what a tile starts from when nothing was fetched ahead (prologue, slow path): its first two halo chunks (2 x (6 | 5) instructions), the
     // first row's transform, the first group's weight fragments
     auto fetch_two_chunks_and_wait = [&]() __attribute__((always_inline)) {
-        if (mover) {
-            voff_get(0);
+        voff_get(0);
 #pragma unroll
-            for (int j = 0; j < RAW_INSTR; ++j) raw_piece(0, 0, j);
-            voff_get(0);
+        for (int j = 0; j < RAW_INSTR; ++j) raw_piece(0, 0, j);
+        voff_get(0);
 #pragma unroll
-            for (int j = 0; j < RAW_INSTR; ++j) raw_piece(1, 1, j);
-        }
+        for (int j = 0; j < RAW_INSTR; ++j) raw_piece(1, 1, j);
         wait_all_but_a_tile();
     };
     auto first_row_and_fragments = [&]() __attribute__((always_inline)) {
@@ -481,14 +365,8 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
         fbase = __hip_atomic_load(flags + (int64_t)t_first * STACK_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         fgiveup = __hip_atomic_load(flags + (int64_t)n_tiles * STACK_FLAG_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // ---- (A/B, off) de-phasing: every workgroup does the same work from the same start and stores its tile at the same moment.  Starting them in
-    // phases took 18 % off a launch while the kernel's stores were half-line writes (116 -> 95 us at 32 images); with the column parities
-    // apart (full 128-byte lines) a tile's stores are 6 % of a launch and the phases change nothing (profiles/r05_w16_form2_phases*.txt).
-    if (W16_PHASES > 1 && t_first + t_step < t_end) {
-        const int phase = ((int)blockIdx.x >> 3) % W16_PHASES;
-        for (int i = 0; i < phase * (W16_SPREAD / W16_PHASES / (64 * 100)); ++i) __builtin_amdgcn_s_sleep(100);
-    }
-    if (W16_PRIO == 1 && wave >= 4) __builtin_amdgcn_s_setprio(1);
+    // (Starting the workgroups in phases took 18 % off a launch while the kernel's stores were half-line writes; with the column parities apart a
+    // tile's stores are 6 % of a launch and the phases change nothing: profiles/r05_w16_form2_phases*.txt.)
     // ---- prologue: bias, chunks 0 and 1 and the first weight half of the first tile, the transform of its first halo row
 #ifdef W16_STAMP
     if (wave == 0) bias_s[lane] = 0.0f;                       // (the profiling build takes its stamp buffer through the bias pointer)
@@ -496,14 +374,12 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     if (wave == 0) bias_s[lane] = bias ? bias[lane] : 0.0f;
 #endif
     fetch_tile_uniform(t_first, x);
-    if (mover) {
 #pragma unroll
-        for (int j = 0; j < (W16_DMA4 ? 2 : 1) * RAW_INSTR; ++j) voff_set(j, fetch_lane_offset(j));
+    for (int j = 0; j < RAW_INSTR; ++j) voff_set(j, fetch_lane_offset(j));
 #pragma unroll
-        for (int j = 0; j < (W16_DMA4 ? 2 : 1) * W_INSTR; ++j) w_piece(Wp, 0, 0, j);
+    for (int j = 0; j < W_INSTR; ++j) w_piece(Wp, 0, 0, j);
 #pragma unroll
-        for (int j = 0; j < (W16_DMA4 ? 2 : 1) * W_INSTR; ++j) w_piece(Wp, 1, 1, j);
-    }
+    for (int j = 0; j < W_INSTR; ++j) w_piece(Wp, 1, 1, j);
     fetch_two_chunks_and_wait();
     __syncthreads();
     first_row_and_fragments();
@@ -526,13 +402,9 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
     bool have_o = false;
     auto store_step = [&](int k) __attribute__((always_inline)) {    // k = 0 .. 15
         const int g = k >> 3, gq = (k >> 1) & 3, p = k & 1;
-        if (!(dp.oy < H) || ((W16_ABL & 8) && relu != 77)) return;       // (uniform)
+        if (!(dp.oy < H)) return;       // (uniform)
         const uint32_t so = uniform((uint32_t)(2 * (4 * g + gq)) * (uint32_t)HW * 16u + (uint32_t)(dp.oy * Wq) * 16u);
-#ifdef W16_STACK_NT   // (timing experiment only: not coherent)
-        if (STACK) asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(o[g][gq][p]), "v"(dp.pix[p]), "s"(dp.orsrc), "s"(so) : "memory");
-#else
         if (STACK) asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1\n\ts_nop 1" ::"v"(o[g][gq][p]), "v"(dp.pix[p]), "s"(dp.orsrc), "s"(so) : "memory");
-#endif
         else asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(o[g][gq][p]), "v"(dp.pix[p]), "s"(dp.orsrc), "s"(so) : "memory");
     };
     bool raw_flying = true;                                    // a halo tile went out behind the last weights (the prologue's did)
@@ -576,8 +448,7 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
             }
         }, [&](int m) __attribute__((always_inline)) {
             if (m == 1 && next) fetch_tile_uniform(t_next, (STACK && new_layer) ? y : x);
-            if (W16_DMA4) { if (m >= 2 && m < 2 + 2 * RAW_INSTR && next && mover) voff_set(m - 2, fetch_lane_offset(m - 2)); }
-            else if (m >= 2 && m < 2 + 2 * RAW_INSTR && !(m & 1) && next) voff_set((m - 2) >> 1, fetch_lane_offset((m - 2) >> 1));
+            if (m >= 2 && m < 2 + 2 * RAW_INSTR && !(m & 1) && next) voff_set((m - 2) >> 1, fetch_lane_offset((m - 2) >> 1));
         });
         bool ready = true;
         if (STACK) {
@@ -598,49 +469,36 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
         // (round 6) a tile whose outputs cannot wait for the next tile's first half-stage - the slow path below, the launch's last tile - stores each
         // pair of pixels as soon as it exists: the 16 stores take ~150 cycles each to issue, and behind the epilogue's arithmetic they were 2400
         // cycles of the hand-over between two layers at one tile per workgroup (one measurement per call)
-        const bool store_now = W16_STORE_NOW && (STACK ? (!next || !ready) : !next);
-        if (!(W16_ABL & 4) || relu == 77) {
-            const float floor_ = relu ? 0.0f : -__builtin_inff();
-            const __attribute__((address_space(3))) float* bsl = (const __attribute__((address_space(3))) float*)bias_s + (STACK ? 64 * (L & 1) : 0);
+        const bool store_now = STACK ? (!next || !ready) : !next;
+        const float floor_ = relu ? 0.0f : -__builtin_inff();
+        const __attribute__((address_space(3))) float* bsl = (const __attribute__((address_space(3))) float*)bias_s + (STACK ? 64 * (L & 1) : 0);
 #pragma unroll
-            for (int g = 0; g < 2; ++g) {
+        for (int g = 0; g < 2; ++g) {
 #pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const f32x4 bz = *reinterpret_cast<const lds_f32x4*>(bsl + 32 * g + 8 * gq + 4 * kb) * dp.bscale;
-#if W16_EPI_PK
-                    // (round 6) two couts per instruction: v_pk_add_f32 / v_pk_fma_f32 - the same IEEE operations lane by lane (the same bits), half the
-                    // issue slots; nothing competes for them here: both waves of the SIMD are in their epilogues, no MFMA runs beside them
+            for (int gq = 0; gq < 4; ++gq) {
+                const f32x4 bz = *reinterpret_cast<const lds_f32x4*>(bsl + 32 * g + 8 * gq + 4 * kb) * dp.bscale;
+                // (round 6) two couts per instruction: v_pk_add_f32 / v_pk_fma_f32 - the same IEEE operations lane by lane (the same bits), half the
+                // issue slots; nothing competes for them here: both waves of the SIMD are in their epilogues, no MFMA runs beside them
 #pragma unroll
-                    for (int k = 0; k < 4; k += 2) {
-                        const int i = 4 * gq + k;
-                        const f32x2 m0 = {acc[0][g][i], acc[0][g][i + 1]}, m1 = {acc[1][g][i], acc[1][g][i + 1]};
-                        const f32x2 m2 = {acc[2][g][i], acc[2][g][i + 1]}, m3 = {acc[3][g][i], acc[3][g][i + 1]};
-                        const f32x2 y0 = pk_add(pk_add(m0, m1), m2), y1 = pk_sub(pk_sub(m1, m2), m3);
-                        const f32x2 sc = {dp.oscale, dp.oscale}, b2 = {bz[k], bz[k + 1]};
-                        const f32x2 z0 = pk_fma(y0, sc, b2), z1 = pk_fma(y1, sc, b2);
-                        o[g][gq][0][k] = __builtin_elementwise_maximum(z0.x, floor_);
-                        o[g][gq][0][k + 1] = __builtin_elementwise_maximum(z0.y, floor_);
-                        o[g][gq][1][k] = __builtin_elementwise_maximum(z1.x, floor_);
-                        o[g][gq][1][k + 1] = __builtin_elementwise_maximum(z1.y, floor_);
-                    }
-#else
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int i = 4 * gq + k;
-                        const float m0 = acc[0][g][i], m1 = acc[1][g][i], m2 = acc[2][g][i], m3 = acc[3][g][i];
-                        const float y0 = (m0 + m1) + m2, y1 = (m1 - m2) - m3;
-                        o[g][gq][0][k] = __builtin_elementwise_maximum(__builtin_fmaf(y0, dp.oscale, bz[k]), floor_);
-                        o[g][gq][1][k] = __builtin_elementwise_maximum(__builtin_fmaf(y1, dp.oscale, bz[k]), floor_);
-                    }
-#endif
-                    if (store_now) { store_step(2 * (4 * g + gq)); store_step(2 * (4 * g + gq) + 1); }
+                for (int k = 0; k < 4; k += 2) {
+                    const int i = 4 * gq + k;
+                    const f32x2 m0 = {acc[0][g][i], acc[0][g][i + 1]}, m1 = {acc[1][g][i], acc[1][g][i + 1]};
+                    const f32x2 m2 = {acc[2][g][i], acc[2][g][i + 1]}, m3 = {acc[3][g][i], acc[3][g][i + 1]};
+                    const f32x2 y0 = pk_add(pk_add(m0, m1), m2), y1 = pk_sub(pk_sub(m1, m2), m3);
+                    const f32x2 sc = {dp.oscale, dp.oscale}, b2 = {bz[k], bz[k + 1]};
+                    const f32x2 z0 = pk_fma(y0, sc, b2), z1 = pk_fma(y1, sc, b2);
+                    o[g][gq][0][k] = __builtin_elementwise_maximum(z0.x, floor_);
+                    o[g][gq][0][k + 1] = __builtin_elementwise_maximum(z0.y, floor_);
+                    o[g][gq][1][k] = __builtin_elementwise_maximum(z1.x, floor_);
+                    o[g][gq][1][k + 1] = __builtin_elementwise_maximum(z1.y, floor_);
                 }
+                if (store_now) { store_step(2 * (4 * g + gq)); store_step(2 * (4 * g + gq) + 1); }
             }
-            have_o = !store_now;
         }
+        have_o = !store_now;
         // the next tile's second weight half (issued in half-stage 7's last group, in front of a halo tile that may still fly) has to be there
         // before a store goes out behind it: vmcnt counts loads and stores alike
-        if (rn && !(W16_ABL & 1)) wait_all_but_a_tile();
+        if (rn) wait_all_but_a_tile();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         W16_MARK(5);
         if (STACK) {
@@ -732,15 +590,6 @@ __global__ __launch_bounds__(TBW, 2) void conv_w16_kernel(const char* __restrict
 
 using namespace deqsci;
 
-static void w16_magic(uint32_t d, uint32_t* mg, uint32_t* sh) {
-    uint32_t s = 0;
-    while ((1ull << s) < d) ++s;
-    *sh = 31 + s;
-    *mg = (uint32_t)(((1ull << (31 + s)) + d - 1) / d);
-}
-
-static bool w16_bad_exp(int e) { return e < -SP16_EXP_LIMIT || e > SP16_EXP_LIMIT; }
-
 static_assert(sizeof(w16::StackLayer) == 24, "the layer table of deqsci_conv3x3_c64_wino16_stack is three 8-byte words per layer");
 
 extern "C" int deqsci_conv3x3_c64_wino16(const void* x_p32, const void* u_packed, const float* bias, void* y_p32, int64_t n, int64_t H, int64_t W,
@@ -749,7 +598,7 @@ extern "C" int deqsci_conv3x3_c64_wino16(const void* x_p32, const void* u_packed
     if (!x_p32 || !u_packed || !y_p32) return DEQSCI_ERR_NULL;
     if ((start_event == nullptr) != (stop_event == nullptr)) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
-    if (x_p32 == y_p32 || w16_bad_exp(w_exp) || w16_bad_exp(in_exp) || w16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (x_p32 == y_p32 || sp16_bad_exp(w_exp) || sp16_bad_exp(in_exp) || sp16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(x_p32) || !aligned16(u_packed) || !aligned16(y_p32)) return DEQSCI_ERR_ALIGN;
     const int64_t tiles_x = ceil_div(W, w16::OUT_COLS), tiles_y = ceil_div(H, w16::OUT_ROWS);
     const int64_t n_tiles = n * tiles_x * tiles_y;
@@ -759,8 +608,8 @@ extern "C" int deqsci_conv3x3_c64_wino16(const void* x_p32, const void* u_packed
     const int64_t resident = (int64_t)num_cus();
     const dim3 grid((unsigned)(n_tiles < resident ? n_tiles : resident));
     uint32_t mg_img, sh_img, mg_tx, sh_tx;
-    w16_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
-    w16_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
+    mdiv_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
+    mdiv_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
     hipEvent_t ev0 = static_cast<hipEvent_t>(start_event), ev1 = static_cast<hipEvent_t>(stop_event);
     hipExtLaunchKernelGGL((w16::conv_w16_kernel<0>), grid, dim3(w16::TBW), 0, st, ev0, ev1, 0, static_cast<const char*>(x_p32), static_cast<const char*>(u_packed),
                           bias, static_cast<char*>(y_p32), (int)H, (int)W, relu, w_exp, in_amax, in_exp, out_amax, out_exp, (int)tiles_x,
@@ -775,7 +624,7 @@ extern "C" int deqsci_conv3x3_c64_wino16_stack(const void* x_p32, void* y_even, 
     if (!x_p32 || !y_even || !layers || !flags || (n_layers > 1 && !y_odd)) return DEQSCI_ERR_NULL;
     if ((start_event == nullptr) != (stop_event == nullptr)) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0 || n_layers <= 0 || (ranges && (range_stride < n || range_stride > INT32_MAX))) return DEQSCI_ERR_SHAPE;
-    if (x_p32 == y_even || x_p32 == y_odd || y_even == y_odd || n_layers > 64 || w16_bad_exp(in_exp) || w16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
+    if (x_p32 == y_even || x_p32 == y_odd || y_even == y_odd || n_layers > 64 || sp16_bad_exp(in_exp) || sp16_bad_exp(out_exp)) return DEQSCI_ERR_UNSUPPORTED;
     if (!aligned16(x_p32) || !aligned16(y_even) || !aligned16(y_odd) || (reinterpret_cast<uintptr_t>(layers) & 7u) || (reinterpret_cast<uintptr_t>(flags) & 3u))
         return DEQSCI_ERR_ALIGN;
     const int64_t tiles_x = ceil_div(W, w16::OUT_COLS), tiles_y = ceil_div(H, w16::OUT_ROWS);
@@ -790,8 +639,8 @@ extern "C" int deqsci_conv3x3_c64_wino16_stack(const void* x_p32, void* y_even, 
     const int64_t resident = fit < (int64_t)num_cus() ? fit : (int64_t)num_cus();
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t mg_img, sh_img, mg_tx, sh_tx;
-    w16_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
-    w16_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
+    mdiv_magic((uint32_t)(tiles_x * tiles_y), &mg_img, &sh_img);
+    mdiv_magic((uint32_t)tiles_x, &mg_tx, &sh_tx);
     hipEvent_t ev0 = static_cast<hipEvent_t>(start_event), ev1 = static_cast<hipEvent_t>(stop_event);
     hipExtLaunchKernelGGL((w16::conv_w16_kernel<1>), dim3((unsigned)(n_tiles < resident ? n_tiles : resident)), dim3(w16::TBW), 0, st, ev0, ev1, 0,
                           static_cast<const char*>(x_p32), static_cast<const char*>(nullptr), static_cast<const float*>(nullptr), static_cast<char*>(y_even),

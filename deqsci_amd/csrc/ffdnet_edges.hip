@@ -285,9 +285,6 @@ __global__ __launch_bounds__(TB) void ffdnet_head_kernel(const float* __restrict
 // left with one LDS gather per k-step (the P operand: lane (k, position) reads ITS tap of ITS position from the patch), the
 // ReLU and the 16-byte stores.  A wave keeps all 48 weight operands in registers and walks 16 groups of its 32 x 32 tile.
 typedef float f32x4m __attribute__((ext_vector_type(4)));
-#ifndef HEAD_ST
-#define HEAD_ST st4
-#endif
 __global__ __launch_bounds__(TB) void ffdnet_head_mfma_kernel(const float* __restrict__ x, const float* __restrict__ wq,
                                                               const float* __restrict__ sigma, int sigma_stride,
                                                               float* __restrict__ h, int H, int W) {
@@ -351,7 +348,7 @@ __global__ __launch_bounds__(TB) void ffdnet_head_mfma_kernel(const float* __res
                 float* o = hn + ((int64_t)r * W + c) * 64 + 4 * kq;    // D: column = position pn, rows 4 kq .. 4 kq + 3 of the cout group
 #pragma unroll
                 for (int cg = 0; cg < 4; ++cg)
-                    HEAD_ST(o + 16 * cg, make_float4(fmaxf(acc[cg][0], 0.0f), fmaxf(acc[cg][1], 0.0f), fmaxf(acc[cg][2], 0.0f), fmaxf(acc[cg][3], 0.0f)));
+                    st4(o + 16 * cg, make_float4(fmaxf(acc[cg][0], 0.0f), fmaxf(acc[cg][1], 0.0f), fmaxf(acc[cg][2], 0.0f), fmaxf(acc[cg][3], 0.0f)));
             }
         }
     }

@@ -46,7 +46,7 @@
 //         front of the next ds_read of ANY LDS array -> the DMA is inline asm and its wait is placed by hand;
 //       - a register load hipcc believes pending on some path makes it wait before the registers' next use - and with it
 //         for every younger DMA piece -> raw_landed() tells it, on every path, that the raw loads are complete.
-//   (WG_WAVES=4 builds the 32-tile variant with two independent workgroups per CU; it measures 2-3 % slower.)
+//   (A 4-wave, 32-tile form with two independent workgroups per CU measured 2-3 % slower.)
 #include "common.hpp"
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -59,12 +59,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int WG_CK = 8;                      // input channels per chunk
 constexpr int WG_NCHUNK = 64 / WG_CK;
-#ifndef WG_ABL
-#define WG_ABL 0                              // timing ablations only (tools/ubench): 1 = no patch reads, 2 = no DMA / raw fetch
-#endif
-#ifndef WG_WAVES
-#define WG_WAVES 8                            // wavefronts per workgroup: 8 (one workgroup per CU) or 4 (two per CU)
-#endif
+constexpr int WG_WAVES = 8;                   // wavefronts per workgroup: one workgroup per CU
 constexpr int WG_TB = 64 * WG_WAVES;
 constexpr int WG_TROWS = WG_WAVES;            // Winograd tile rows of a block tile (8 tiles per row, 16 tiles per wave pair)
 constexpr int WG_RAW_PS = 10;                 // floats per staged pixel (8 channels + 2)
@@ -190,7 +185,7 @@ __device__ __forceinline__ void winograd_conv64_body(const float* __restrict__ x
     // moves bytes [8 KiB * w, +8 KiB) in 8 instructions that differ only in their immediate offset (which the hardware adds
     // to the global AND the LDS address): one scalar base and one M0 value per chunk, no address arithmetic per piece.
     const uint32_t us_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)Us;
-    constexpr int DMA_WAVE_BYTES = WG_U_CHUNK * 4 / WG_WAVES;                          // 4 KiB (8 waves) or 8 KiB (4 waves)
+    constexpr int DMA_WAVE_BYTES = WG_U_CHUNK * 4 / WG_WAVES;                          // 4 KiB
     const uint32_t dma_voff = (uint32_t)(wave * DMA_WAVE_BYTES + lane * 16);            // bytes
     // returns the scalar global base of the chunk (+ half a wave share); sets M0 = LDS base of this wave's share (+ half).
     // The base is handed to the pieces as a VALUE: kept in a by-reference variable it ended up in vector registers.
@@ -397,7 +392,7 @@ __device__ __forceinline__ void winograd_conv64_body(const float* __restrict__ x
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi) {
             if (xi + PF < 16) bq[(xi + PF) % (PF + 1)] = *reinterpret_cast<const float4*>(ubc + (xi + PF) * (2 * 64 * 4));
-            if ((xi & 1) == 0 && !(WG_ABL & 1)) {             // two patch elements per instruction (ds_read2_b64)
+            if ((xi & 1) == 0) {                             // two patch elements per instruction (ds_read2_b64)
                 dn[xi] = *reinterpret_cast<const f32x2*>(ppn + prow[xi >> 2] + (xi & 3) * WG_RAW_PS);
                 dn[xi + 1] = *reinterpret_cast<const f32x2*>(ppn + prow[xi >> 2] + ((xi & 3) + 1) * WG_RAW_PS);
             }
@@ -406,8 +401,7 @@ __device__ __forceinline__ void winograd_conv64_body(const float* __restrict__ x
             __builtin_amdgcn_sched_barrier(0);
             acc[xi][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(b.x, v[xi].x, FIRST ? (xi == 5 ? init5[0] : zero) : acc[xi][0], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if (WG_ABL & 2) { }
-            else if (xi < DMA_PIECES) dma_u_piece(dg, xi);    // weights first: they are needed one stage from now,
+            if (xi < DMA_PIECES) dma_u_piece(dg, xi);         // weights first: they are needed one stage from now,
             else if (xi == DMA_PIECES) fetch_raw_k(PAR, cf, 0);   // the raw chunk three stages from now, into the set
             else if (xi == DMA_PIECES + 1) fetch_raw_k(PAR, cf, 1);   // stage c-1 stored from
             __builtin_amdgcn_sched_barrier(0);

@@ -39,20 +39,12 @@
 // LDS: 72 KB weights + 2 x 21 KB raw + 32 KB exchange + 6 KB DMA offsets + bias = 152.3 KB.  Rounding: 1.2-1.7e-6 per layer
 // against fp64 (F(2x2,3x3): 2.1e-7); end to end the FFDNet gates do not move (tools/f44_numerics.py,
 // profiles/r02_f44_numerics.jsonl).  64 images of 128 x 128: 242-245 us against 303-314 us for F(2x2,3x3) on the same box; where the
-// rest goes (tools/w44_variants.sh + w44_check.py, profiles/r02_w44_*): MFMA phases alone 158 us, input transform +50,
-// weight DMA +10, raw DMA +15, output transform + exchange + stores +25.  (W44_ABL=1, "no raw DMA", once measured 190 us:
-// hipcc had deleted the input transform together with it - a shared array that nothing writes.  Count the instructions of a
-// stage before believing an ablation.)
+// rest goes (timing ablations, since removed; profiles/r02_w44_*): MFMA phases alone 158 us, input transform +50,
+// weight DMA +10, raw DMA +15, output transform + exchange + stores +25.
 #include "common.hpp"
 #include <hip/hip_ext.h>
 #include <type_traits>
 #pragma clang diagnostic ignored "-Winline-asm"   // m0 is named as a clobber of the LDS-DMA asm below, on purpose
-
-#ifndef W44_ABL
-#define W44_ABL 0     // timing ablations only (results wrong; tools/w44_variants.sh): 1 = no raw DMA, 2 = no weight DMA, 16 = no input
-                      // transform, 64 = no patch reads, 128 = raw DMA folded into 64 KB (cache hits), 4096 = no output stores (but
-                      // everything in front of them), 8192 = no exchange between the two row groups
-#endif
 
 namespace deqsci {
 namespace w44 {
@@ -200,11 +192,8 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
             } else {
                 pix_bytes = (uint32_t)(iy * W + ix) * 256u;
             }
-            uint32_t vo = ok ? pix_bytes + 16u * (uint32_t)half + (RAW_BIAS - 1024u * j) : RAW_OOB;
-#if W44_ABL & 128     // timing experiment (wrong results): the same scatter pattern, folded into the first 64 KB of the image (cache hits)
-            vo = ok ? vo & 0xffffu : RAW_OOB;
-#endif
-            if (!(W44_ABL & 1)) Voff[j * TBW + wave * 64 + el] = vo;
+            const uint32_t vo = ok ? pix_bytes + 16u * (uint32_t)half + (RAW_BIAS - 1024u * j) : RAW_OOB;
+            Voff[j * TBW + wave * 64 + el] = vo;
         }
     };
     const uint32_t raw_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)Raw;
@@ -225,7 +214,6 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
         return d;
     };
     auto raw_piece = [&](const RawDma& d, int j) __attribute__((always_inline)) {
-        if (W44_ABL & 1) return;
         if (j == 0) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(d.m0v), "v"(d.v[0]), "s"(rsrc), "s"(d.soff) : "memory", "m0");
         else if (j == 1) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:1024 lds" ::"s"(d.m0v), "v"(d.v[1]), "s"(rsrc), "s"(d.soff) : "memory", "m0");
         else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen offset:2048 lds" ::"s"(d.m0v), "v"(d.v[2]), "s"(rsrc), "s"(d.soff) : "memory", "m0");
@@ -252,7 +240,6 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
         const uint64_t dg = dma_setup(c, half);
         const int dl = lane_id();
         const uint32_t dma_voff = (uint32_t)(dl * 16);
-        if (W44_ABL & 2) return;
         W44_DMA(-2048); W44_DMA(-1024); W44_DMA(0); W44_DMA(1024);
         if (half == 0) W44_DMA(2048);
     };
@@ -281,7 +268,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
             for (int j = 0; j < 6; ++j) {
                 f32x2 d[6];
 #pragma unroll
-                for (int pr = 0; pr < 5; ++pr) d[pr] = (W44_ABL & 64) ? v[pr + j] : *reinterpret_cast<const volatile lds_f32x2*>(pp + (pr < 4 ? pbaseA : pbaseB) + patch_off(pr, j));
+                for (int pr = 0; pr < 5; ++pr) d[pr] = *reinterpret_cast<const volatile lds_f32x2*>(pp + (pr < 4 ? pbaseA : pbaseB) + patch_off(pr, j));
                 bt_lo(d, t[0][j], t[1][j], t[2][j]);          // (rows 0..2 of B^T do not touch patch row 5, rows 3..5 not row 0: a volatile load is not dropped for being unused)
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -290,7 +277,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
             for (int j = 0; j < 6; ++j) {
                 f32x2 d[6];
 #pragma unroll
-                for (int pr = 1; pr < 6; ++pr) d[pr] = (W44_ABL & 64) ? v[pr + j] : *reinterpret_cast<const volatile lds_f32x2*>(pp + (pr < 4 ? pbaseA : pbaseB) + patch_off(pr, j));
+                for (int pr = 1; pr < 6; ++pr) d[pr] = *reinterpret_cast<const volatile lds_f32x2*>(pp + (pr < 4 ? pbaseA : pbaseB) + patch_off(pr, j));
                 bt_hi(d, t[0][j], t[1][j], t[2][j]);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -378,24 +365,19 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
                         send[2 + c][2 * h] = s1.x; send[2 + c][2 * h + 1] = s1.y;
                     }
                 }
-#if W44_ABL & 8192     // timing experiment: no exchange
-#pragma unroll
-                for (int q = 0; q < 4; ++q) mine[q] += send[q];
-#else
 #pragma unroll
                 for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4*>(xw + q * 256) = send[q];
                 lds_barrier();
 #pragma unroll
                 for (int q = 0; q < 4; ++q) mine[q] += *reinterpret_cast<const f32x4*>(xr + q * 256);
                 if (!(j == 1 && cp == 1)) lds_barrier();              // the partner has read before the next round overwrites
-#endif
 #pragma unroll
                 for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {
                         f32x4 val = mine[rr * 2 + c];
                         if (relu) { val.x = fmaxf(val.x, 0.0f); val.y = fmaxf(val.y, 0.0f); val.z = fmaxf(val.z, 0.0f); val.w = fmaxf(val.w, 0.0f); }
-                        if ((!(W44_ABL & 4096) || relu == 77) && oy + rr < H && ox + 2 * cp + c < W) {
+                        if (oy + rr < H && ox + 2 * cp + c < W) {
                             // blk32: position 8 ((col+1)&3) + tx of the block.  Non-temporal; (s_nop: the wait states between a 16-byte
                             // store and the next write of its data registers, which the compiler cannot see into the asm to insert)
                             const uint32_t so = uniform(OUT_BLK ? osb + (uint32_t)(2 * j) * plane_b + (uint32_t)(rr * tiles_x) * 1024u
@@ -426,7 +408,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
     // stage), vmcnt(0) in front of X2.  A register spill inside the loop would be a scratch access = one more vector memory
     // operation (the counts stay safe: extra younger operations only make a wait stricter) with a vmcnt(0) in front of its
     // use - and, between the asm MFMAs, a read of an accumulator without the wait states the compiler gives real MFMAs:
-    // the loop must compile without spill STORES inside the MFMA parts (tools/w44_variants.sh prints the spill count).
+    // the loop must compile without spill STORES inside the MFMA parts (tools/lib_variants.sh prints the spill count).
     auto stage = [&](auto rg_c, auto par_c, auto first_c, int c, int t_cur) __attribute__((always_inline)) {
         constexpr int RG = decltype(rg_c)::value;
         constexpr int PAR = decltype(par_c)::value;
@@ -500,7 +482,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
         }
         __builtin_amdgcn_sched_barrier(0);                    // (hipcc otherwise starts the transform above the MFMAs that still read v)
         // (the last stage of a tile transforms BEHIND the epilogue: V would otherwise be live across it, 36 registers too many)
-        if (!(W44_ABL & 16) && c != 7) transform(rg_c, PAR ^ 1);    // V(c+1)
+        if (c != 7) transform(rg_c, PAR ^ 1);    // V(c+1)
         __builtin_amdgcn_sched_barrier(0);
         W44_MARK(2);                                          // second MFMA part + transform
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // first half of U(c+1) and raw(c+2) are in LDS
@@ -510,7 +492,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
         if (c == 7) {
             epilogue(rg_c, t_cur);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(W44_ABL & 16)) transform(rg_c, PAR ^ 1);   // V(0) of the next tile: the raw buffer is rewritten behind X1 of its stage 0 at the earliest
+            transform(rg_c, PAR ^ 1);   // V(0) of the next tile: the raw buffer is rewritten behind X1 of its stage 0 at the earliest
             __builtin_amdgcn_sched_barrier(0);
         }
         if (c == 5) {                                         // chunks c+3.. of the fetch stream belong to the next tile

@@ -146,6 +146,27 @@ def test_shipped_library_reads_no_environment():
         assert "getenv" not in outside and "static const" not in outside.replace("static constexpr", ""), src
 
 
+def test_kernel_sources_carry_no_experiment_switches():
+    """The kernels hold ONE form each: a settled A/B or ablation is deleted, not parked behind a -D (DESIGN section 6 and profiles/ keep
+    the measurement).  Every preprocessor conditional of csrc/ tests only the diagnostic build, the cycle-stamp profiling builds and
+    WG_NO_CABI."""
+    allowed = {"DEQSCI_DIAG", "S16_STAMP", "W16_STAMP", "W44_STAMP", "WG_STAMP", "WG_STAMP_TID", "WG_STAMP_SKIP", "WG_NO_CABI"}
+    csrc = sorted(f for f in os.listdir(os.path.join(ROOT, "deqsci_amd", "csrc")) if f.endswith(".hip") or f == "common.hpp")
+    assert "conv_s16.hip" in csrc and "conv_w16.hip" in csrc and "common.hpp" in csrc
+    offending, seen = [], 0
+    for src in csrc:
+        for no, line in enumerate(open(os.path.join(ROOT, "deqsci_amd", "csrc", src)), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            seen += 1
+            names = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+            if not names or names - allowed:                      # (a conditional on a bare number is a switch too)
+                offending.append("%s:%d: %s" % (src, no, line.strip()))
+    assert seen >= 10                                             # (the DEQSCI_DIAG and *_STAMP blocks are there: the scan sees conditionals)
+    assert not offending, "conditionals on names outside the allow-list:\n" + "\n".join(offending)
+
+
 def test_gfx950_code_object_present():
     from deqsci_amd import _hip
     blob = open(_hip.lib_path(), "rb").read()

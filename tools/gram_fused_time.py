@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """K4 alone, K4 + the reference Gram's first pass as two launches, and the fused launch (deqsci_residual_store_ref_f32), timed on a history like the
-loop's (correlated heavy-tailed rows), bsz 8 and 4 at N = 2^19, m = 5; then the apply kernel + solve.  DEQSCI_HIP_LIB selects an ablation build."""
+loop's (correlated heavy-tailed rows), bsz 8 and 4 at N = 2^19, m = 5; then the apply kernel + solve.  DEQSCI_HIP_LIB selects another build of the library."""
 import json
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Socket power and shader clock while the split-fp16 conv kernel (or a variant library, DEQSCI_HIP_LIB) runs back to back for a few seconds:
+"""Socket power and shader clock while the split-fp16 conv kernel (or another build of the library, DEQSCI_HIP_LIB) runs back to back for a few seconds:
 is the launch time energy / power?  Samples the amdgpu hwmon files (power1_average / power1_input in uW, freq1_input in Hz) from a thread;
 prints what it finds when the files are missing (then `rocm-smi` is tried once per phase)."""
 import glob

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase timing of the split-fp16 STACK launch (a run of 64->64 layers in one launch, csrc/conv_s16.hip; build with -DS16_STAMP:
-tools/s16_variants.sh "stamp:-DS16_STAMP"): shader cycles per layer each wave spends in the MFMA groups, at the stage barriers, in the
+tools/lib_variants.sh conv_s16 "stamp:-DS16_STAMP"): shader cycles per layer each wave spends in the MFMA groups, at the stage barriers, in the
 epilogue, and BETWEEN two layers - waiting for its stores, at the barrier behind them, publishing its progress word and waiting for the
 eight neighbours', fetching the first chunk of the next layer."""
 import os
@@ -10,7 +10,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/s16v/lib_stamp.so"))
+os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/var_conv_s16/lib_stamp.so"))
 from deqsci_amd import _hip  # noqa: E402
 
 n, H, W, L = int(os.environ.get("S16_IMAGES", "8")), 128, 128, int(os.environ.get("S16_LAYERS", "13"))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timing of the split-fp16 conv kernel (build with -DS16_STAMP: tools/s16_variants.sh "stamp:-DS16_STAMP"): shader cycles each wave spends
+"""Phase timing of the split-fp16 conv kernel (build with -DS16_STAMP: tools/lib_variants.sh conv_s16 "stamp:-DS16_STAMP"): shader cycles each wave spends
 in the 18 MFMA groups of a stage, waiting for the next chunk's DMA (s_waitcnt vmcnt(0)), at the stage barrier, in the epilogue, and in the rest."""
 import os
 import sys
@@ -8,7 +8,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/s16v/lib_stamp.so"))
+os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/var_conv_s16/lib_stamp.so"))
 from deqsci_amd import _hip  # noqa: E402
 
 g = torch.Generator(device="cuda").manual_seed(5)
@@ -18,7 +18,7 @@ x = torch.randn(n, 64, 128, 128, device="cuda", generator=g).contiguous(memory_f
 xs = _hip.to_split16(x)
 out = _hip.Sp16.empty(n, 128, 128, "cuda")
 Wsp = _hip.Split16Weights(w)
-NW = int(os.environ.get("S16_NW", "8"))                 # waves per workgroup of the build under test (-DS16_GEOM_NW)
+NW = 8                                                  # waves per workgroup
 stamps = torch.zeros(256 * NW * 5, dtype=torch.int32, device="cuda")
 for _ in range(3):
     _hip.conv3x3_c64_split16(xs, Wsp, stamps.view(torch.float32), True, out=out)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time of the split-fp16 conv kernel alone (sp16 -> sp16, 64 x 128 x 128) for the library in DEQSCI_HIP_LIB (variants of tools/s16_variants.sh);
+"""Time of the split-fp16 conv kernel alone (sp16 -> sp16, 64 x 128 x 128) for the library in DEQSCI_HIP_LIB (a build of tools/lib_variants.sh; default: the product);
 S16_ZERO=1 runs it on all-zero operands (less switching power: what the clock gives back)."""
 import json, os, statistics, sys
 import torch

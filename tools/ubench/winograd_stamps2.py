@@ -1,5 +1,5 @@
 """Fine timeline of the two waves of one SIMD (waves 0 and 4 of a workgroup) of the Winograd kernel, from s_memtime stamps
-(variant library built with -DWG_STAMP -DWG_STAMP_SKIP=n, tools/wg_variants.sh; WG_LIB points at it).  Nine marks per
+(variant library built with -DWG_STAMP -DWG_STAMP_SKIP=n, tools/lib_variants.sh winograd "stamp:-DWG_STAMP -DWG_STAMP_SKIP=n"; WG_LIB points at it).  Nine marks per
 pipeline stage: start | raw DMA issued | operands preloaded | after xi 3 | 7 | 11 | 15 (MFMA phase done) | before barrier |
 after barrier.  Prints, for the median block, every stage of both waves as offsets from the stage's first mark of wave 0."""
 import os, sys, torch, numpy as np

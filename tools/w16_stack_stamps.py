@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timing of the STACK launch of csrc/conv_w16.hip (build with -DW16_STAMP: tools/w16_variants.sh "stamp:-DW16_STAMP") at ONE tile per CU -
+"""Phase timing of the STACK launch of csrc/conv_w16.hip (build with -DW16_STAMP: tools/lib_variants.sh conv_w16 "stamp:-DW16_STAMP") at ONE tile per CU -
 8 images of 128 x 128 = one measurement per call, the reference's usage: shader cycles each wave spends per LAYER in its MFMA streams, waiting for
 DMA, at barriers, in the epilogue, in the prologue / tile setup, and in the slow path (= waiting for the neighbours' progress words)."""
 import os
@@ -9,7 +9,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/w16v/lib_stamp.so"))
+os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/var_conv_w16/lib_stamp.so"))
 from deqsci_amd import _hip  # noqa: E402
 
 n, L = int(os.environ.get("W16_IMAGES", "8")), int(os.environ.get("W16_LAYERS", "13"))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timing of the split-fp16 Winograd kernel (build with -DW16_STAMP: tools/w16_variants.sh "stamp:-DW16_STAMP"): shader cycles each wave
+"""Phase timing of the split-fp16 Winograd kernel (build with -DW16_STAMP: tools/lib_variants.sh conv_w16 "stamp:-DW16_STAMP"): shader cycles each wave
 spends in the MFMA stream of a half-stage (72 MFMAs + transform + DMA issue + operand reads), waiting for the DMA, at the barrier, in the
 epilogue, in the rest.  W16_IMAGES (64)."""
 import os
@@ -9,7 +9,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/w16v/lib_stamp.so"))
+os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/var_conv_w16/lib_stamp.so"))
 from deqsci_amd import _hip  # noqa: E402
 
 g = torch.Generator(device="cuda").manual_seed(5)

@@ -13,9 +13,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from deqsci_amd import _hip  # noqa: E402
 
-if os.environ.get("W44_LIB"):                      # a variant build (tools: build/w44v/lib_<name>.so) instead of the product library
-    _hip._LIB_PATH = os.path.join(ROOT, os.environ["W44_LIB"])
-
 
 def check():
     g = torch.Generator(device="cuda").manual_seed(3)
@@ -72,8 +69,6 @@ def timeit():
             x.zero_()
         out = torch.empty_like(x)
         fns = {"f22": (lambda: _hip.conv3x3_c64_winograd(x, U2, b, True, out=out)), "f44": (lambda: _hip.conv3x3_c64_winograd44(x, U4, b, True, out=out))}
-        if os.environ.get("W44_LIB"):
-            fns.pop("f22")
         U2, U4 = _hip.pack_winograd_weights(w), _hip.pack_winograd44_weights(w)
         res = {k: [] for k in fns}
         for rnd in range(9):
@@ -87,7 +82,7 @@ def timeit():
                 e1.record()
                 torch.cuda.synchronize()
                 res[k].append(e0.elapsed_time(e1) / 20 * 1e3)
-        print(json.dumps({"lib": os.environ.get("W44_LIB", "product"), "shape": shape, **{k + "_us": round(statistics.median(v), 1) for k, v in res.items()}}), flush=True)
+        print(json.dumps({"lib": os.environ.get("DEQSCI_HIP_LIB", "product"), "shape": shape, **{k + "_us": round(statistics.median(v), 1) for k, v in res.items()}}), flush=True)
 
 
 if __name__ == "__main__":

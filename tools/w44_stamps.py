@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timing of the F(4x4,3x3) kernel (build with -DW44_STAMP: tools/w44_variants.sh "stamp:-DW44_STAMP"): cycles each wave spends in
+"""Phase timing of the F(4x4,3x3) kernel (build with -DW44_STAMP: tools/lib_variants.sh winograd44 "stamp:-DW44_STAMP"): cycles each wave spends in
 the first MFMA part, at barrier X1 (with its vmcnt wait), in the second MFMA part + input transform, at X2, and in the rest."""
 import os
 import sys
@@ -8,9 +8,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+os.environ.setdefault("DEQSCI_HIP_LIB", os.path.join(ROOT, "build/var_winograd44/lib_stamp.so"))
 from deqsci_amd import _hip  # noqa: E402
 
-_hip._LIB_PATH = os.path.join(ROOT, os.environ.get("W44_LIB", "build/w44v/lib_stamp.so"))
 g = torch.Generator(device="cuda").manual_seed(5)
 w = torch.randn(64, 64, 3, 3, device="cuda", generator=g) * 0.05
 x = torch.randn(64, 64, 128, 128, device="cuda", generator=g).contiguous(memory_format=torch.channels_last)

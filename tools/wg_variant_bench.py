@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Correctness + timing of every Winograd-kernel variant library under build/wgv/ (tools/wg_variants.sh)."""
+"""Correctness + timing of every build of csrc/winograd.hip under build/var_winograd/ (tools/lib_variants.sh winograd "name:defs" ...)."""
 import ctypes
 import glob
 import json
@@ -50,7 +50,7 @@ def main():
         U = torch.zeros_like(U)
     outs = {s: torch.empty_like(xs[s]) for s in shapes}
     libs = []
-    for path in sorted(glob.glob(os.path.join(ROOT, "build", "wgv", "lib_*.so"))):
+    for path in sorted(glob.glob(os.path.join(ROOT, "build", "var_winograd", "lib_*.so"))):
         name = os.path.basename(path)[4:-3]
         if (only and name not in only) or (not only and name.startswith("stamp")):
             continue                                   # stamp builds scribble over the bias pointer: never next to a check
