@@ -37,6 +37,7 @@ import torch.nn.functional as F
 
 from . import _hip
 from ._hip import LAYOUT_BHW, LAYOUT_HWB
+from .layers import _fold_bn, conv_stack                    # noqa: F401  (engine._fold_bn stays importable)
 
 SIGMA0 = 60 / 255
 SIGMA_DECAY = 0.971
@@ -86,11 +87,6 @@ def check_snapshots(snapshots, max_iter, iterator="anderson"):
     if out[-1] >= max_iter:
         raise ValueError(f"snapshots={tuple(out)}: every horizon must be smaller than max_iter={max_iter} (the run's own result is the last one)")
     return tuple(out)
-
-
-def _fold_bn(conv_w, bn):
-    scale = bn.weight / torch.sqrt(bn.running_var + bn.eps)
-    return (conv_w * scale.view(-1, 1, 1, 1)).contiguous(), (bn.bias - bn.running_mean * scale).contiguous()
 
 
 class _Denoiser:
@@ -160,7 +156,7 @@ class _Denoiser:
     def _refresh(self):
         """(Re)build the BN-folded functional FFDNet whenever the module's tensors changed
         (e.g. load_state_dict after the engine was created)."""
-        from .networks import FFDNet
+        from .networks import DnCNN, FFDNet
         net = self.net
         key = (self._weights_key(), net.training)
         if key == self._wkey:
@@ -170,32 +166,17 @@ class _Denoiser:
         self.wino = None
         self.tail_w = self.head_w = self.tail_w16 = self.head_w16 = None
         self.plain_head_w = self.plain_tail_w = self.plain_tail_w16 = None
-        from .networks import DnCNN
-        from .networks.simplecnn import RealSNConv2d
         seq = None
         if isinstance(net, FFDNet) and not net.training and net.num_input_channels == 1 and self.fold_bn:
             seq = net.intermediate_dncnn.itermediate_dncnn
-        elif isinstance(net, DnCNN) and not net.training and self.fold_bn and all(
-                isinstance(mod, (torch.nn.Conv2d, RealSNConv2d, torch.nn.BatchNorm2d, torch.nn.ReLU)) for mod in net.dncnn):
+        elif isinstance(net, DnCNN) and not net.training and self.fold_bn:
             seq = net.dncnn                       # SimpleCNN / RealSN_SimpleCNN / DnCNN-17: conv [+BN] + ReLU blocks
-        if seq is not None:
-            mods = list(seq)
-            layers, i = [], 0
-            while i < len(mods):
-                conv = mods[i]
-                # RealSNConv2d in eval mode = conv2d with its stored, already normalised `weight` buffer
-                # (networks/provable/model/conv_sn_chen.py:65-67): the same HIP kernels run it
-                assert isinstance(conv, RealSNConv2d) or (isinstance(conv, torch.nn.Conv2d) and conv.bias is None)
-                w, b = conv.weight.detach(), None
-                i += 1
-                if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
-                    w, b = _fold_bn(w, mods[i])
-                    i += 1
-                relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
-                if relu:
-                    i += 1
-                w = w.contiguous(memory_format=torch.channels_last) if self.channels_last else w.contiguous()
-                layers.append((w, b, relu))
+        # a sequence the walker refuses (a bias, a kernel other than 3x3 pad 1, BatchNorm in train mode, ...) keeps fast = None: _route
+        # answers "module" and the plugin's own forward runs
+        layers = None if seq is None else conv_stack(seq)[0]
+        if layers is not None:
+            layers = [(w.contiguous(memory_format=torch.channels_last) if self.channels_last else w.contiguous(), b, relu)
+                      for w, b, relu in layers]
             self.fast = layers
             # 64->64 layers: Winograd on the fp32 matrix cores with bias+ReLU fused: F(4x4,3x3) (csrc/winograd44.hip) when the
             # launch has more than a wave of block tiles, F(2x2,3x3) (csrc/winograd.hip) below that - _hip.conv3x3_c64 picks

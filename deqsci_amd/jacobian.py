@@ -157,31 +157,26 @@ class _HostDenoiser:
         ok, why = _vjp.jacobian_eligibility(net)
         if not ok:
             raise ValueError(f"HostMapJacobian: {why}")
-        self.x, self.sigma = x, sigma
-        self.ffdnet = why == _vjp.FFDNET_THROUGH_INPUT
         xm = x if mask_dtype is None else x.to(mask_dtype)
-        if self.ffdnet:
+        if why == _vjp.FFDNET_THROUGH_INPUT:
             if sigma is None:
                 raise ValueError("HostMapJacobian: FFDNet is linearised at a noise level: sigma is required")
-            self.layers = _vjp.ffdnet_plan(net)
+            _vjp._even(x, "HostMapJacobian")
+            self.layers, self.edges = _vjp.ffdnet_plan(net), _vjp.FFDNET_EDGES
             self.masks = masks if masks is not None else _vjp.ffdnet_plan_forward(self.layers, xm, sigma)[1]
         else:
-            self.layers, _ = _vjp.host_plan(net)
+            self.layers, self.edges = _vjp.host_plan(net)[0], _vjp.PLAIN_EDGES
             self.masks = masks if masks is not None else _vjp.plan_masks(self.layers, xm)
 
     def jvp(self, v):
-        if self.ffdnet:
-            return _vjp.ffdnet_plan_jvp(self.layers, self.x, self.sigma, v, self.masks)[0]
-        return _vjp.plan_jvp(self.layers, self.x, v, self.masks)[0]
+        return _vjp.masked_jvp(self.layers, self.masks, v, self.edges)
 
     def vjp(self, v):
-        if self.ffdnet:
-            return _vjp.ffdnet_plan_vjp(self.layers, self.x, self.sigma, v, self.masks)[0]
-        return _vjp.plan_vjp(self.layers, self.x, v, self.masks)[0]
+        return _vjp.masked_vjp(self.layers, self.masks, v, self.edges)
 
 
 class HostMapJacobian:
-    """MapJacobian's host statement in `dtype` (float64) on the CPU over plan_jvp / plan_vjp / ffdnet_plan_*: the same four products.
+    """MapJacobian's host statement in `dtype` (float64) on the CPU over vjp.masked_jvp / masked_vjp: the same four products.
     masks: explicit ReLU masks ((bsz*B,64,H,W) bool per layer, e.g. the device's through vjp.unpack_masks) instead of those of the
     forward pass at z1; mask_dtype: the precision of that forward pass (torch.float32: the decisions an fp32 forward takes)."""
 

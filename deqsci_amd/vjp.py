@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .layers import conv_stack
 
 _FFDNET_OK = "FFDNet detaches its input: J_D^T = 0"
 
@@ -36,51 +37,14 @@ def _modules():
     return DnCNN, FFDNet, RealSNConv2d
 
 
-def _conv_ok(conv):
-    return (tuple(conv.kernel_size) == (3, 3) and tuple(conv.padding) == (1, 1) and tuple(conv.stride) == (1, 1)
-            and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
-
-
 def host_plan(net):
-    """(layers, reason): the denoiser as [(weight, bias or None, relu)] with eval-mode BatchNorm folded into the conv the way
-    engine._fold_bn does it (weight * s, bias = beta - mean * s), or (None, why not) when the net is not a conv [+BN-eval] + ReLU
-    stack of 3x3, pad-1 convolutions without bias.  Usable on the CPU."""
+    """(layers, reason): the denoiser as [(weight, bias or None, relu)] with eval-mode BatchNorm folded into the conv (layers.conv_stack:
+    weight * s, bias = beta - mean * s), or (None, why not) when the net is not a conv [+BN-eval] + ReLU stack of 3x3, pad-1
+    convolutions without bias.  Usable on the CPU."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     if not isinstance(net, DnCNN):
         return None, f"not a conv [+BN] + ReLU stack: {type(net).__name__}"
-    mods = list(net.dncnn)
-    layers, i = [], 0
-    while i < len(mods):
-        conv = mods[i]
-        if isinstance(conv, RealSNConv2d):
-            if conv.training:
-                return None, "RealSNConv2d in train mode (its weight is renormalised by the power iteration)"
-            w = conv.weight.detach()
-        elif isinstance(conv, torch.nn.Conv2d):
-            if not _conv_ok(conv):
-                return None, "Conv2d other than 3x3, stride 1, padding 1"
-            if conv.bias is not None:
-                return None, "Conv2d with a bias"
-            w = conv.weight.detach()
-        else:
-            return None, f"unknown module {type(conv).__name__} where a convolution was expected"
-        b = None
-        i += 1
-        if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
-            bn = mods[i]
-            if bn.training or not bn.track_running_stats:
-                return None, "BatchNorm2d in train mode (batch statistics: its Jacobian is not a fixed scale)"
-            from .engine import _fold_bn
-            w, b = _fold_bn(w, bn)
-            w, b = w.detach(), b.detach()
-            i += 1
-        relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
-        if relu:
-            i += 1
-        elif i < len(mods) and not isinstance(mods[i], (torch.nn.Conv2d, RealSNConv2d)):
-            return None, f"unknown module {type(mods[i]).__name__}"
-        layers.append((w, b, relu))
-    return layers, None
+    return conv_stack(net.dncnn)
 
 
 def eligibility(net):
@@ -112,71 +76,80 @@ def _transposed(w):
     return w.transpose(0, 1).flip(2, 3).contiguous()
 
 
+# ----------------------------------------------------------------------------- the host plans: one masked walk in each direction
+# How a stack's edge layers meet the image: (what the first layer reads of it, the input channels of the first weight that carry it, what
+# the last layer's output becomes).  FFDNet: 2x2 pixel-unshuffle in (channel 0 of its first weight is sigma's, a constant of the
+# linearisation), pixel-shuffle out.  The shuffles are permutations, so the transposed walk reads and writes the same way.
+PLAIN_EDGES = (lambda v: v, slice(None), lambda t: t)
+FFDNET_EDGES = (lambda v: F.pixel_unshuffle(v, 2), slice(1, 5), lambda t: F.pixel_shuffle(t, 2))
+
+
+def masked_forward(layers, h):
+    """One forward pass of all layers but the last on the first layer's input h, in h's dtype.  -> (the last layer's input, masks):
+    masks[i] is the (n,C,H,W) bool ReLU decision behind layer i, None for a layer without ReLU."""
+    masks = []
+    for w, b, relu in layers[:-1]:
+        h = F.conv2d(h, w.to(h), None if b is None else b.to(h), padding=1)
+        masks.append(h > 0 if relu else None)
+        if relu:
+            h = torch.relu(h)
+    return h, masks
+
+
+def masked_jvp(layers, masks, v, edges=PLAIN_EDGES):
+    """J v: the layers in forward order, every conv without its bias, every ReLU replaced by its mask."""
+    read, cin, write = edges
+    t = read(v)
+    for i, (w, _, _) in enumerate(layers[:-1]):
+        t = F.conv2d(t, (w[:, cin] if i == 0 else w).to(v), padding=1)
+        if masks[i] is not None:
+            t = t * masks[i]
+    return write(F.conv2d(t, layers[-1][0].to(v), padding=1))
+
+
+def masked_vjp(layers, masks, v, edges=PLAIN_EDGES):
+    """J^T v: the layers in reverse order, every conv transposed, layer i's output masked by the ReLU in front of it."""
+    read, cin, write = edges
+    g = read(v)
+    for i in range(len(layers) - 1, 0, -1):
+        g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
+        if masks[i - 1] is not None:
+            g = g * masks[i - 1]
+    return write(F.conv2d(g, _transposed(layers[0][0][:, cin].to(v)), padding=1))
+
+
 def plan_masks(layers, x):
     """The ReLU masks of one forward pass of the stack `layers` at x, in x's dtype: one (n,C,H,W) bool tensor (or None) per layer but the last."""
-    h, masks = x, []
-    for w, b, relu in layers[:-1]:
-        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
-        if relu:
-            masks.append(h > 0)
-            h = torch.relu(h)
-        else:
-            masks.append(None)
-    return masks
+    return masked_forward(layers, x)[1]
 
 
 def plan_vjp(layers, x, v, masks=None):
     """J_D(x)^T v of the stack `layers` (host_plan) evaluated in x's dtype with F.conv2d and explicit masks - the host statement of what
     DenoiserVJP runs (tests: float64 against torch.autograd.grad).  masks: those of another forward pass (the device's, unpack_masks)
     instead of the ones at x.  Returns (vjp, masks)."""
-    if masks is None:
-        masks = plan_masks(layers, x)
-    g = v
-    for i in range(len(layers) - 1, 0, -1):
-        g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
-        if masks[i - 1] is not None:
-            g = g * masks[i - 1]
-    return F.conv2d(g, _transposed(layers[0][0].to(v)), padding=1), masks
+    masks = plan_masks(layers, x) if masks is None else masks
+    return masked_vjp(layers, masks, v), masks
 
 
 def plan_jvp(layers, x, v, masks=None):
-    """J_D(x) v of the stack `layers`: the layers in forward order, every conv without its bias, every ReLU replaced by its mask - the host
-    statement of DenoiserJacobian.jvp, next to plan_vjp.  Returns (jvp, masks)."""
-    if masks is None:
-        masks = plan_masks(layers, x)
-    t = v
-    for i, (w, _, _) in enumerate(layers[:-1]):
-        t = F.conv2d(t, w.to(v), padding=1)
-        if masks[i] is not None:
-            t = t * masks[i]
-    return F.conv2d(t, layers[-1][0].to(v), padding=1), masks
+    """J_D(x) v of the stack `layers` - the host statement of DenoiserJacobian.jvp, next to plan_vjp.  Returns (jvp, masks)."""
+    masks = plan_masks(layers, x) if masks is None else masks
+    return masked_jvp(layers, masks, v), masks
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
 def ffdnet_plan(net):
     """Grayscale FFDNet in eval mode as [(weight, bias or None, relu)]: (64,5,3,3) first, 13 x (64,64,3,3) with the BatchNorm folded
-    (engine._fold_bn), (4,64,3,3) last.  Functional: ffdnet_plan_forward does not detach its input.  Usable on the CPU."""
+    (layers.conv_stack), (4,64,3,3) last.  Functional: ffdnet_plan_forward does not detach its input.  Usable on the CPU."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     if not isinstance(net, FFDNet) or net.num_input_channels != 1:
         raise ValueError("ffdnet_plan: a grayscale FFDNet is required")
-    from .engine import _fold_bn
-    mods = list(net.intermediate_dncnn.itermediate_dncnn)
-    layers, i = [], 0
-    while i < len(mods):
-        conv = mods[i]
-        if not isinstance(conv, torch.nn.Conv2d) or not _conv_ok(conv) or conv.bias is not None:
-            raise ValueError(f"ffdnet_plan: module {i} is not a 3x3, stride 1, padding 1 convolution without bias")
-        w, b = conv.weight.detach(), None
-        i += 1
-        if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
-            if mods[i].training:
-                raise ValueError("ffdnet_plan: BatchNorm2d in train mode")
-            w, b = _fold_bn(w, mods[i])
-            w, b = w.detach(), b.detach()
-            i += 1
-        relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
-        i += int(relu)
-        layers.append((w, b, relu))
+    mods = net.intermediate_dncnn.itermediate_dncnn
+    if any(isinstance(m, RealSNConv2d) for m in mods):
+        raise ValueError("ffdnet_plan: RealSNConv2d where FFDNet has a Conv2d")
+    layers, why = conv_stack(mods)
+    if layers is None:
+        raise ValueError(f"ffdnet_plan: {why}")
     shapes = [tuple(w.shape) for w, _, _ in layers]
     if (len(layers) < 3 or shapes[0] != (64, 5, 3, 3) or shapes[-1] != (4, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1])
             or not all(r for _, _, r in layers[:-1]) or layers[-1][2] or layers[0][1] is not None or layers[-1][1] is not None):
@@ -198,34 +171,22 @@ def _sigma_map(sigma, x):
 def ffdnet_plan_forward(layers, x, sigma):
     """(noise, masks) of FFDNet at (x, sigma) in x's dtype, through the input (no detach): masks[i] is the ReLU decision behind layer i."""
     _even(x, "ffdnet_plan_forward")
-    h, masks = torch.cat((_sigma_map(sigma, x), F.pixel_unshuffle(x, 2)), 1), []
-    for w, b, _ in layers[:-1]:
-        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
-        masks.append(h > 0)
-        h = torch.relu(h)
+    h, masks = masked_forward(layers, torch.cat((_sigma_map(sigma, x), F.pixel_unshuffle(x, 2)), 1))
     return F.pixel_shuffle(F.conv2d(h, layers[-1][0].to(x), padding=1), 2), masks
 
 
 def ffdnet_plan_jvp(layers, x, sigma, v, masks=None):
     """J_D(x; sigma) v of FFDNet through its input (sigma a constant: its channel of the first layer carries no tangent).  -> (jvp, masks)"""
     _even(x, "ffdnet_plan_jvp")
-    if masks is None:
-        masks = ffdnet_plan_forward(layers, x, sigma)[1]
-    t = F.conv2d(F.pixel_unshuffle(v, 2), layers[0][0][:, 1:5].to(v), padding=1) * masks[0]
-    for i in range(1, len(layers) - 1):
-        t = F.conv2d(t, layers[i][0].to(v), padding=1) * masks[i]
-    return F.pixel_shuffle(F.conv2d(t, layers[-1][0].to(v), padding=1), 2), masks
+    masks = ffdnet_plan_forward(layers, x, sigma)[1] if masks is None else masks
+    return masked_jvp(layers, masks, v, FFDNET_EDGES), masks
 
 
 def ffdnet_plan_vjp(layers, x, sigma, v, masks=None):
     """J_D(x; sigma)^T v of FFDNet through its input.  -> (vjp, masks)"""
     _even(x, "ffdnet_plan_vjp")
-    if masks is None:
-        masks = ffdnet_plan_forward(layers, x, sigma)[1]
-    g = F.conv2d(F.pixel_unshuffle(v, 2), _transposed(layers[-1][0].to(v)), padding=1) * masks[-1]
-    for i in range(len(layers) - 2, 0, -1):
-        g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1) * masks[i - 1]
-    return F.pixel_shuffle(F.conv2d(g, _transposed(layers[0][0][:, 1:5].to(v)), padding=1), 2), masks
+    masks = ffdnet_plan_forward(layers, x, sigma)[1] if masks is None else masks
+    return masked_vjp(layers, masks, v, FFDNET_EDGES), masks
 
 
 def unpack_masks(words):
@@ -245,122 +206,115 @@ def jacobian_eligibility(net):
     return ok, why
 
 
+# ----------------------------------------------------------------------------- the device: one masked stack
+class _MaskedStack:
+    """The layers of a plan linearised at the fp32 GPU image x, on the HIP kernels.  One forward pass at x (first layer stencil, Winograd
+    F(2x2,3x3) with the folded BN bias) builds the ReLU masks (.masks: relu_mask_pack's words per layer); jvp and vjp are then linear in v:
+    masked layers enqueued on the current stream with no host synchronisation, no pack made twice.  sigma: FFDNet's (1,) or (n,) fp32
+    noise levels on x's device - its plan (ffdnet_plan), read through the 2x2 pixel-unshuffle: csrc/jacobian.hip's masked first layer
+    serves the linearised head and the transposed tail, deqsci_ffdnet_tail_f32 without bias the linearised tail and the transposed head.
+    None: a 1 -> 64 -> ... -> 64 -> 1 stack (host_plan)."""
+
+    def __init__(self, layers, x, sigma=None):
+        x = _hip.f32c(x.detach())
+        f32 = lambda t: t.to(x.device, torch.float32)
+        self.ffdnet = sigma is not None
+        with torch.no_grad():
+            w0, wt = f32(layers[0][0]), f32(layers[-1][0])
+            mid = [f32(w) for w, _, _ in layers[1:-1]]
+            if self.ffdnet:
+                win = w0[:, 1:5]                                    # (channel 0 is sigma's: it carries no tangent)
+                self.head_f = _hip.pack_head_masked_weights(win.contiguous())
+                self.tail_f = _hip.pack_tail_weights(wt)
+                self.tail_t = _hip.pack_head_masked_weights(_transposed(wt))
+                self.head_t = _hip.pack_tail_weights(_transposed(win))
+                h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), sigma)
+            else:
+                self.head_f = _hip.pack_c1_to_64_weights(w0)
+                self.tail_f = _hip.pack_c64_to_1_weights(wt)
+                self.tail_t = _hip.pack_c1_to_64_weights(_transposed(wt))
+                self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
+                h = _hip.conv3x3_c1_to_64(x, self.head_f, relu=True)
+            self.mid_f = [_hip.pack_winograd_weights(w) for w in mid]
+            self.mid_t = [_hip.pack_winograd_weights(_transposed(w)) for w in mid]
+            self.masks = [_hip.relu_mask_pack(h)]
+            for u, (_, b, _) in zip(self.mid_f, layers[1:-1]):
+                h = _hip.conv3x3_c64_winograd(h, u, None if b is None else f32(b).contiguous(), True)
+                self.masks.append(_hip.relu_mask_pack(h))
+
+    def jvp(self, v):
+        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
+        t = first(_hip.f32c(v), self.head_f, self.masks[0])
+        for i, u in enumerate(self.mid_f):
+            t = _hip.conv3x3_c64_winograd_masked(t, u, self.masks[i + 1])
+        return _hip.ffdnet_tail(t, self.tail_f) if self.ffdnet else _hip.conv3x3_c64_to_1(t, self.tail_f)
+
+    def vjp(self, v):
+        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
+        g = first(_hip.f32c(v), self.tail_t, self.masks[-1])
+        for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
+            g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
+        return _hip.ffdnet_tail(g, self.head_t) if self.ffdnet else _hip.conv3x3_c64_to_1(g, self.head_t)
+
+
+def _image(x, who):
+    if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
+        raise _hip.DeqsciHipError(f"{who}: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
+    return tuple(x.shape)
+
+
 class DenoiserJacobian:
-    """v -> J_D(x) v (.jvp) and v -> J_D(x)^T v (.vjp) for a (n,1,H,W) fp32 GPU image x and v of its shape, on the HIP kernels: a
-    diagnostic of the map the iteration applies, so FFDNet (grayscale, eval mode) is differentiated through its input at the noise level
-    sigma, a constant of the linearisation.  One forward pass at x on the fp32 kernels (first layer stencil, Winograd F(2x2,3x3) with the
-    folded BN bias) builds the ReLU masks (.masks, relu_mask_pack's words per layer); every product is then linear in v: masked layers
-    enqueued on the current stream with no host synchronisation.  Conv stacks: .vjp is what DenoiserVJP runs, .jvp the same kernels in
-    forward order with the untransposed weights.  FFDNet: csrc/jacobian.hip's masked first layer serves the linearised head and the
-    transposed tail, deqsci_ffdnet_tail_f32 without bias the linearised tail and the transposed head.  Raises ValueError for a net
+    """v -> J_D(x) v (.jvp) and v -> J_D(x)^T v (.vjp) for a (n,1,H,W) fp32 GPU image x and v of its shape, on the HIP kernels
+    (_MaskedStack; .masks are its ReLU masks): a diagnostic of the map the iteration applies, so FFDNet (grayscale, eval mode) is
+    differentiated through its input at the noise level sigma, a constant of the linearisation.  Raises ValueError for a net
     jacobian_eligibility refuses and for an FFDNet image with an odd side, before any launch."""
 
     def __init__(self, net, x, sigma=None):
         ok, why = jacobian_eligibility(net)
         if not ok:
             raise ValueError(f"DenoiserJacobian: {why}")
-        if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
-            raise _hip.DeqsciHipError(f"DenoiserJacobian: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
-        self.shape = tuple(x.shape)
-        self.ffdnet = why == FFDNET_THROUGH_INPUT
-        if self.ffdnet:
+        self.shape = _image(x, "DenoiserJacobian")
+        if why == FFDNET_THROUGH_INPUT:
             _even(x, "DenoiserJacobian")
             if sigma is None:
                 raise ValueError("DenoiserJacobian: FFDNet is linearised at a noise level: sigma is required")
-        x = _hip.f32c(x.detach())
-        dev = x.device
-        f32 = lambda t: t.to(dev, torch.float32)
-        self.masks = []
-        with torch.no_grad():
-            if self.ffdnet:
-                layers = ffdnet_plan(net)
-                w0, wt = f32(layers[0][0]), f32(layers[-1][0])
-                sg = torch.as_tensor(sigma, dtype=torch.float32, device=dev).reshape(-1)
-                if sg.numel() not in (1, x.shape[0]):
-                    raise ValueError(f"DenoiserJacobian: sigma must have 1 or {x.shape[0]} elements, got {sg.numel()}")
-                self.sigma = sg.contiguous()
-                h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), self.sigma)
-                self.head_f = _hip.pack_head_masked_weights(w0[:, 1:5].contiguous())
-                self.tail_f = _hip.pack_tail_weights(wt)
-                self.tail_t = _hip.pack_head_masked_weights(_transposed(wt))
-                self.head_t = _hip.pack_tail_weights(_transposed(w0[:, 1:5]))
-            else:
-                layers, _ = host_plan(net)
-                w0, wt = f32(layers[0][0]), f32(layers[-1][0])
-                h = _hip.conv3x3_c1_to_64(x, _hip.pack_c1_to_64_weights(w0), relu=True)
-                self.head_f = _hip.pack_c1_to_64_weights(w0)
-                self.tail_f = _hip.pack_c64_to_1_weights(wt)
-                self.tail_t = _hip.pack_c1_to_64_weights(_transposed(wt))
-                self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
-            self.masks.append(_hip.relu_mask_pack(h))
-            for w, b, _ in layers[1:-1]:
-                h = _hip.conv3x3_c64_winograd(h, _hip.pack_winograd_weights(f32(w)), None if b is None else f32(b).contiguous(), True)
-                self.masks.append(_hip.relu_mask_pack(h))
-            del h
-            self.mid_f = [_hip.pack_winograd_weights(f32(w)) for w, _, _ in layers[1:-1]]
-            self.mid_t = [_hip.pack_winograd_weights(_transposed(f32(w))) for w, _, _ in layers[1:-1]]
+            layers = ffdnet_plan(net)
+            sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1).contiguous()
+            if sigma.numel() not in (1, x.shape[0]):
+                raise ValueError(f"DenoiserJacobian: sigma must have 1 or {x.shape[0]} elements, got {sigma.numel()}")
+        else:
+            layers, sigma = host_plan(net)[0], None
+        self._stack = _MaskedStack(layers, x, sigma)
+        self.masks = self._stack.masks
 
     def _v(self, v, what):
         if tuple(v.shape) != self.shape:
             raise _hip.DeqsciHipError(f"DenoiserJacobian.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
-        return _hip.f32c(v)
+        return v
 
     def jvp(self, v):
-        v = self._v(v, "jvp")
-        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
-        t = first(v, self.head_f, self.masks[0])
-        for i, u in enumerate(self.mid_f):
-            t = _hip.conv3x3_c64_winograd_masked(t, u, self.masks[i + 1])
-        return _hip.ffdnet_tail(t, self.tail_f) if self.ffdnet else _hip.conv3x3_c64_to_1(t, self.tail_f)
+        return self._stack.jvp(self._v(v, "jvp"))
 
     def vjp(self, v):
-        v = self._v(v, "vjp")
-        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
-        g = first(v, self.tail_t, self.masks[-1])
-        for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
-            g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
-        return _hip.ffdnet_tail(g, self.head_t) if self.ffdnet else _hip.conv3x3_c64_to_1(g, self.head_t)
+        return self._stack.vjp(self._v(v, "vjp"))
 
 
 class DenoiserVJP:
-    """v -> J_D(x)^T v for a (n,1,H,W) fp32 GPU image x and v of its shape, on the HIP kernels.  One forward pass at x (the existing fp32
-    kernels: 1 -> 64 stencil, Winograd F(2x2,3x3)) builds the ReLU masks; every call is then k-1 masked transposed layers and the 64 -> 1
-    stencil, enqueued on the current stream with no host synchronisation (safe to capture).  sigma: FFDNet's noise level (unused: its
-    input is detached, the product is zero).  Raises ValueError with eligibility()'s reason for a net it cannot differentiate."""
+    """v -> J_D(x)^T v for a (n,1,H,W) fp32 GPU image x and v of its shape: _MaskedStack.vjp, k-1 masked transposed layers and the 64 -> 1
+    stencil per call, enqueued on the current stream with no host synchronisation (safe to capture).  sigma: FFDNet's noise level (unused:
+    its input is detached, the product is zero - no launches, no masks).  Raises ValueError with eligibility()'s reason for a net it
+    cannot differentiate."""
 
     def __init__(self, net, x, sigma=None):
         ok, why = eligibility(net)
         if not ok:
             raise ValueError(f"DenoiserVJP: {why}")
-        if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
-            raise _hip.DeqsciHipError(f"DenoiserVJP: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
-        self.shape = tuple(x.shape)
+        self.shape = _image(x, "DenoiserVJP")
         self.zero = why == _FFDNET_OK
-        self.masks = []
-        if self.zero:
-            return
-        layers, _ = host_plan(net)
-        x = _hip.f32c(x.detach())
-        dev = x.device
-        with torch.no_grad():
-            w0 = layers[0][0].to(dev, torch.float32)
-            h = _hip.conv3x3_c1_to_64(x, _hip.pack_c1_to_64_weights(w0), relu=True)
-            self.masks.append(_hip.relu_mask_pack(h))
-            for w, b, _ in layers[1:-1]:
-                h = _hip.conv3x3_c64_winograd(h, _hip.pack_winograd_weights(w.to(dev, torch.float32)),
-                                              None if b is None else b.to(dev, torch.float32).contiguous(), True)
-                self.masks.append(_hip.relu_mask_pack(h))
-            del h
-            self.tail_t = _hip.pack_c1_to_64_weights(_transposed(layers[-1][0].to(dev, torch.float32)))
-            self.mid_t = [_hip.pack_winograd_weights(_transposed(w.to(dev, torch.float32))) for w, _, _ in layers[1:-1]]
-            self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
+        self._stack = None if self.zero else _MaskedStack(host_plan(net)[0], x)
+        self.masks = [] if self.zero else self._stack.masks
 
     def __call__(self, v):
         if tuple(v.shape) != self.shape:
             raise _hip.DeqsciHipError(f"DenoiserVJP: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
-        if self.zero:
-            return torch.zeros_like(v)
-        g = _hip.conv3x3_c1_to_64_masked(_hip.f32c(v), self.tail_t, self.masks[-1])
-        for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
-            g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
-        return _hip.conv3x3_c64_to_1(g, self.head_t)
+        return torch.zeros_like(v) if self.zero else self._stack.vjp(v)

@@ -84,6 +84,38 @@ def test_denoiser_jacobian_against_host_plans_under_the_devices_masks(kind):
     assert e1 <= 1e-5 and e2 <= 1e-5 and adj <= 1e-5
 
 
+@pytest.mark.parametrize("shape", [(3, 24, 20), (1, 1, 1)])
+@pytest.mark.parametrize("kind", ["SimpleCNN", "DnCNN17_bn"])
+def test_the_hooks_product_is_the_diagnostics_transpose_bit_for_bit(kind, shape):
+    """DenoiserVJP and DenoiserJacobian.vjp are one masked stack: equal masks and equal products, at a shape ragged against the 16x16
+    Winograd tile in both directions with more than one image, and at the smallest shape the masked kernels accept."""
+    from deqsci_amd import vjp
+    from deqsci_amd.networks import DnCNN
+    if kind == "SimpleCNN":
+        net = _pipeline(kind)[0].nonlinear_op
+    else:
+        torch.manual_seed(7)
+        net = DnCNN(1, num_of_layers=17, lip=0.0, no_bn=False, tag="denoiser")
+        for mod in net.dncnn:
+            if isinstance(mod, torch.nn.Conv2d):
+                torch.nn.init.kaiming_normal_(mod.weight, nonlinearity="relu")
+            elif isinstance(mod, torch.nn.BatchNorm2d):
+                mod.weight.data.uniform_(0.7, 1.3)
+                mod.bias.data.normal_(0, 0.05)
+                mod.running_mean.normal_(0, 0.05)
+                mod.running_var.uniform_(0.8, 1.2)
+        net = net.cuda().eval()
+    n, H, W = shape
+    g = torch.Generator().manual_seed(13)
+    x, v = torch.rand(n, 1, H, W, generator=g).cuda(), torch.randn(n, 1, H, W, generator=g).cuda()
+    hook, jd = vjp.DenoiserVJP(net, x), vjp.DenoiserJacobian(net, x)
+    assert len(hook.masks) == len(jd.masks) == (3 if kind == "SimpleCNN" else 16)
+    assert all(torch.equal(a, b) for a, b in zip(hook.masks, jd.masks))
+    got = hook(v)
+    assert got.shape == v.shape and torch.equal(got, jd.vjp(v))
+    assert bool(got.any()) or n == 1                    # (not two zeros: 1440 pixels x 64 units do not all sit behind a closed ReLU)
+
+
 @pytest.mark.parametrize("case", list(CASES))
 def test_map_jacobian_against_the_reference_golden(case):
     gold = np.load(os.path.join(GOLDEN, "jacobian.npz"))

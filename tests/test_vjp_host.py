@@ -112,3 +112,41 @@ def test_deq_implicit_backward_attribute_defaults_and_validation():
     solver.nonlinear_op = DnCNN(1, num_of_layers=5, lip=0.0, no_bn=False, tag="denoiser").train()
     assert deq._device_map(None, None) is None and "BatchNorm2d" in deq.backward_fallback_reason
     assert solver.device_vjp_eligibility()[0] is False
+
+
+@pytest.mark.parametrize("kind", ["SimpleCNN", "RealSN_SimpleCNN", "DnCNN17_bn", "ffdnet"])
+def test_engine_and_plans_walk_the_layers_alike(kind):
+    """The f-call's layers (engine._Denoiser.fast) and the plan the backward and the diagnostics differentiate are one walk
+    (layers.conv_stack): equal weights (the engine's may be channels_last), equal biases or both None, equal ReLU flags."""
+    from deqsci_amd.engine import _Denoiser
+    net = _randomise(FFDNet(1, tag="ffdnet"), 3).eval() if kind == "ffdnet" else _nets()[kind]
+    plan = vjp.ffdnet_plan(net) if kind == "ffdnet" else vjp.host_plan(net)[0]
+    den = _Denoiser(net)
+    assert den.fast is not None and len(den.fast) == len(plan) == {"SimpleCNN": 4, "RealSN_SimpleCNN": 4, "DnCNN17_bn": 17, "ffdnet": 15}[kind]
+    assert any(b is not None for _, b, _ in plan) == (kind in ("DnCNN17_bn", "ffdnet"))
+    for (w, b, relu), (pw, pb, prelu) in zip(den.fast, plan):
+        assert torch.equal(w, pw) and relu == prelu
+        assert (b is None and pb is None) or torch.equal(b, pb)
+        assert not w.requires_grad and (b is None or not b.requires_grad)
+
+
+@pytest.mark.parametrize("what", ["bias", "5x5", "bn_train"])
+def test_engine_leaves_a_stack_the_walk_refuses_to_the_module(what):
+    """A plugin the walk refuses runs its own forward: fast stays None, the route is "module", the f-call is the module's output."""
+    from deqsci_amd.engine import _Denoiser
+    net = _randomise(DnCNN(1, num_of_layers=4, lip=0.0, no_bn=False, tag="denoiser"), 4).eval()
+    if what == "bias":
+        net.dncnn[2] = torch.nn.Conv2d(64, 64, 3, padding=1, bias=True)
+    elif what == "5x5":
+        net.dncnn[2] = torch.nn.Conv2d(64, 64, 5, padding=2, bias=False)
+    else:
+        net.dncnn[3].train()
+    assert not net.training and vjp.host_plan(net)[0] is None
+    den = _Denoiser(net)
+    assert den.fast is None
+    assert den._route(6, 9, 7, "cpu", den.conv64, False) == "module"
+    z1 = torch.randn(2, 3, 9, 7, generator=torch.Generator().manual_seed(5))
+    with torch.no_grad():
+        out, is_noise = den.run(z1, 0)
+        want = net(z1.view(6, 1, 9, 7)).reshape(2, 3, 9, 7)
+    assert is_noise and torch.equal(out, want)
