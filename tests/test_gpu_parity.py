@@ -219,15 +219,26 @@ def _gram_rows(kind, bsz, m, N, gen):
     raise ValueError(kind)
 
 
-@pytest.mark.parametrize("kind", ["correlated", "heavy", "orthogonal", "negative", "tiny", "huge", "few_bits", "zero_row"])
-@pytest.mark.parametrize("bsz,N,m", [(1, 1 << 19, 5), (3, 1 << 17, 5), (2, 20480, 3), (1, (1 << 19) + 28, 8), (2, 105, 5), (1, 2048, 2), (1, 1 << 22, 3), (9, 1 << 15, 5)])
+GRAM_KINDS = ["correlated", "heavy", "orthogonal", "negative", "tiny", "huge", "few_bits", "zero_row"]
+GRAM_SHAPES = [(1, 1 << 19, 5), (3, 1 << 17, 5), (2, 20480, 3), (1, (1 << 19) + 28, 8), (2, 105, 5), (1, 2048, 2), (1, 1 << 22, 3), (9, 1 << 15, 5)]
+# blocks of 3072 elements (bsz N > 2^25): gram_round_kernel without term slots, gram_chain_apply_kernel without prefetch and with up to 1024 terms per
+# chain and block in LDS - 86 blocks (one record window), and 685 blocks (three windows, the last block of 4 elements); four kinds, to keep the time down
+GRAM_BIG_SHAPES = [(128, 262148, 2), (16, 2101252, 2)]
+GRAM_BIG_KINDS = ["correlated", "heavy", "few_bits", "negative"]
+GRAM_CASES = [(k, *s) for s in GRAM_SHAPES for k in GRAM_KINDS] + [(k, *s) for s in GRAM_BIG_SHAPES for k in GRAM_BIG_KINDS]
+
+
+@pytest.mark.parametrize("kind,bsz,N,m", GRAM_CASES, ids=[f"{b}-{n}-{m}-{k}" for k, b, n, m in GRAM_CASES])
 def test_reference_gram_two_pass_form_is_bit_equal_to_the_serial_chains(kind, bsz, N, m):
     """anderson_arith = "reference": the 16 FMA chains per Gram entry (csrc/anderson.hip) as they are written - N / 16 dependent FMAs,
     gram_row_chain16_kernel - and in the two-pass form that ships (gram_round_kernel + gram_chain_apply_kernel: inside a binade of the running sum
     a chain step is S + RN_ulp(p), an integer sum in any order; crossings, ties and oversized terms are walked) give THE SAME BITS, on every kind
     of history: the loop's (correlated, heavy-tailed), sums that wander around zero or run negative, scales near the ends of fp32, operands with
     few bits (ties), an all-zero row; ragged N, N % 4 != 0 (both forms fall back to the serial kernel), m = 8, more blocks than the record window of
-    the apply kernel (N = 2^22: 2048 blocks, eight windows), an odd batch."""
+    the apply kernel (N = 2^22: 2048 blocks, eight windows), an odd batch, blocks of more than 2048 elements (GRAM_BIG_SHAPES)."""
+    if (bsz, N, m) in GRAM_BIG_SHAPES:
+        nchunks = _hip.load().deqsci_anderson_chunks(bsz, N)   # (a retuned chunk_elems must not silently empty these cases)
+        assert nchunks == {262148: 86, 2101252: 685}[N] and -(-(-(-N // nchunks)) // 1024) * 1024 == 3072 and N - (nchunks - 1) * 3072 == {262148: 1028, 2101252: 4}[N]
     gen = torch.Generator(device=DEV).manual_seed(11)
     rows = _gram_rows(kind, bsz, m, N, gen).float().contiguous()
     ws = _hip.AndersonWorkspace(bsz, N, m, DEV)
