@@ -6,6 +6,7 @@ from .operators import A_torch_, At_torch_, initial_point, initial_point_gaptv, 
 from .gaptv import GAP_TV_rec, denoise_tv_chambolle  # noqa: F401
 from .solvers import (EquilibriumProxGradSCI, andersonexp, forward_iteration, DEQFixedPoint,  # noqa: F401
                       EquilibriumADMMSCI, admmexp, DEQFixedPointADMM, initial_point_admm)
+from .broyden import broyden, broyden_fixed_point  # noqa: F401
 from .engine import DEQSCIEngine, sigma_schedule  # noqa: F401
 from .networks import FFDNet, DnCNN  # noqa: F401
 

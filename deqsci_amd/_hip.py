@@ -76,13 +76,16 @@ SIGNATURES = {
     "deqsci_conv3x3_c1_to_64_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_ffdnet_head_masked_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_power_step_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
+    "deqsci_broyden_dots_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _ptr],
+    "deqsci_broyden_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _int, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
 }
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
-                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes")
+                 "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
+                 "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk")
 
 
 class DeqsciHipError(RuntimeError):
@@ -124,6 +127,10 @@ def load():
     lib.deqsci_sqerr_workspace_bytes.argtypes = [_i64, _i64]
     lib.deqsci_power_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_power_workspace_bytes.argtypes = [_i64, _i64]
+    lib.deqsci_broyden_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_broyden_workspace_bytes.argtypes = [_i64, _i64, _int]
+    lib.deqsci_broyden_chunk.restype = _i64
+    lib.deqsci_broyden_chunk.argtypes = []
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -1423,6 +1430,60 @@ def power_step(w, v_prev, v_out, table_row, workspace=None):
         _check(load().deqsci_power_step_f32(_p(w, "w"), _p(v_prev, "v_prev", True), _p(v_out, "v_out"), table_row.data_ptr(), bsz, N,
                                             workspace.data_ptr(), _stream()), "power_step")
     return v_out
+
+
+# ----------------------------------------------------------------------------- Broyden (csrc/broyden.hip)
+BROYDEN_MAX_L = 27
+BROYDEN_TABLE_STRIDE = 84
+# columns of BroydenWorkspace.table: a_j = <dx, U_j>, b_j = <V_j, dg>, c_j = <V_j, gx_new> at A + j, B + j, C + j; |gx_new|^2, d, c_new
+BROYDEN_A, BROYDEN_B, BROYDEN_C, BROYDEN_GG, BROYDEN_D, BROYDEN_CNEW = 0, 27, 54, 81, 82, 83
+
+
+def broyden_chunk():
+    """Elements of a row that one workgroup of the Broyden kernels sums (the first stage of their two-stage sums)."""
+    return int(load().deqsci_broyden_chunk())
+
+
+class BroydenWorkspace:
+    """Caller-owned buffers of the Broyden step kernels: the planar history U, V (bsz, L, N), the float64 table (bsz, 84) and the chunk
+    partials (the library never allocates)."""
+
+    def __init__(self, bsz, N, L, device):
+        if not 1 <= L <= BROYDEN_MAX_L:
+            raise DeqsciHipError(f"Broyden history L={L} must lie in 1..{BROYDEN_MAX_L}")
+        nbytes = int(load().deqsci_broyden_workspace_bytes(bsz, N, L))
+        if nbytes == 0:
+            raise DeqsciHipError(f"Broyden workspace: unsupported sizes bsz={bsz}, N={N}, L={L}")
+        self.bsz, self.N, self.L = bsz, N, L
+        self.U = torch.zeros((bsz, L, N), device=device, dtype=torch.float32)
+        self.V = torch.zeros((bsz, L, N), device=device, dtype=torch.float32)
+        self.table = torch.zeros((bsz, BROYDEN_TABLE_STRIDE), device=device, dtype=torch.float64)
+        self.partials = torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
+
+
+def _broyden_rows(ws, what, **rows):
+    for name, r in rows.items():
+        if r is not None and tuple(r.shape) != (ws.bsz, ws.N):
+            raise DeqsciHipError(f"{what}: {name} {tuple(r.shape)} must be {(ws.bsz, ws.N)}")
+
+
+def broyden_dots(ws, dx, gx_old, gx_new, t):
+    """ws.table[s] <- a_j, b_j, c_j (j < t) and |gx_new_s|^2 in float64 (two launches, no host synchronisation)."""
+    _broyden_rows(ws, "broyden_dots", dx=dx, gx_old=gx_old, gx_new=gx_new)
+    with _dev(ws.U):
+        _check(load().deqsci_broyden_dots_f32(_p(ws.U), _p(ws.V), _p(dx, "dx"), _p(gx_old, "gx_old"), _p(gx_new, "gx_new"), ws.table.data_ptr(),
+                                              ws.partials.data_ptr(), ws.bsz, ws.N, ws.L, int(t), _stream()), "broyden_dots")
+
+
+def broyden_update(ws, dx, gx_old, gx_new, t, slot, update, x=None, x_next=None):
+    """After broyden_dots with the same rows: the rank-one update into row `slot` of ws.U / ws.V, update = gx_new - sum_j c_j U_j and
+    x_next = x + update when given (two launches, no host synchronisation).  update may be dx."""
+    _broyden_rows(ws, "broyden_update", dx=dx, gx_old=gx_old, gx_new=gx_new, update=update, x=x, x_next=x_next)
+    with _dev(ws.U):
+        _check(load().deqsci_broyden_update_f32(_p(ws.U), _p(ws.V), _p(dx, "dx"), _p(gx_old, "gx_old"), _p(gx_new, "gx_new"), _p(x, "x", True),
+                                                _p(x_next, "x_next", True), _p(update, "update"), ws.table.data_ptr(), ws.partials.data_ptr(),
+                                                ws.bsz, ws.N, ws.L, int(t), int(slot), _stream()), "broyden_update")
+    return update
 
 
 # ----------------------------------------------------------------------------- GAP-TV (csrc/tv.hip)

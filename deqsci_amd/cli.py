@@ -17,6 +17,10 @@ residual of every f-call, per clip and measurement.
 `--jacobian [N_ITERS]` (this build's) adds the local Lipschitz constant and spectral radius of f and the Lipschitz constant of the noise
 predictor at every reconstruction (deqsci_amd.jacobian) to each clip line and one 'Total Average' line per quantity after the totals;
 `--jacobian_json FILE` writes the per-measurement values and the iterations' histories.
+`--solver broyden` (this build's) solves the fixed point with Broyden's method (deqsci_amd.broyden, the reference's
+broyd_equilibrium_utils.broyden on the device) instead of Anderson acceleration: `--broyden_threshold` steps at most (default:
+--and_maxiters), stopped when |f(z) - z| over the batch falls below `--broyden_eps`.  It runs on the generic solver path, so
+--snapshots / --trace (the engine's) are refused with it.
 """
 import argparse
 import os
@@ -27,9 +31,10 @@ import torch
 
 from . import checkpoint, distributed
 from .harness import (SCITestDataset, clip_line, evaluate, jacobian_document, png_payloads, print_horizons, print_jacobian_totals,
-                      trace_document, write_png)
+                      solver_line, trace_document, write_png)
 from .networks import DnCNN, FFDNet
 from .operators import A_torch_, At_torch_
+from .broyden import broyden_fixed_point
 from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp
 
 SHIPPED = {'ffdnet': 'ffdnet_gray', 'SimpleCNN': 'cnn', 'RealSN_SimpleCNN': 'rsn_cnn'}
@@ -46,13 +51,19 @@ def build_denoiser(name, n_channels=1):
     raise NotImplementedError('unknown denoiser!')
 
 
-def build_pipeline(denoiser, loadpath=None, and_maxiters=100, and_m=5, and_beta=1.0, device="cuda"):
+def build_pipeline(denoiser, loadpath=None, and_maxiters=100, and_m=5, and_beta=1.0, device="cuda", solver_name="anderson", broyden_threshold=None,
+                   broyden_eps=1e-5):
     net = build_denoiser(denoiser).eval()
     solver = EquilibriumProxGradSCI(A=A_torch_, At=At_torch_, nonlinear_operator=net, eta=0.2, minval=-1, maxval=1)
     if loadpath:
         checkpoint.load_solver(solver, loadpath)
     solver = solver.to(device)
-    deq = DEQFixedPoint(solver, andersonexp, m=and_m, beta=and_beta, lam=1e-2, max_iter=and_maxiters, tol=1e-5)
+    if solver_name == "broyden":
+        deq = DEQFixedPoint(solver, broyden_fixed_point, threshold=and_maxiters if broyden_threshold is None else broyden_threshold, eps=broyden_eps)
+    elif solver_name == "anderson":
+        deq = DEQFixedPoint(solver, andersonexp, m=and_m, beta=and_beta, lam=1e-2, max_iter=and_maxiters, tol=1e-5)
+    else:
+        raise ValueError(f"solver_name must be 'anderson' or 'broyden', got {solver_name!r}")
     return solver, deq
 
 
@@ -119,6 +130,13 @@ def parser():
                    help="(this build) also report, at every reconstruction, the local Lipschitz constant Lip(f) and the spectral radius rho(f) of "
                         "the fixed-point map and the Lipschitz constant Lip(D) of the noise predictor (power iterations of N_ITERS steps, "
                         "default 30): per clip and one 'Total Average' line per quantity")
+    p.add_argument('--solver', default='anderson', choices=['anderson', 'broyden'],
+                   help="(this build) the fixed-point solver: anderson (default) = Anderson acceleration on the engine; broyden = Broyden's method "
+                        "(the reference's broyd_equilibrium_utils.broyden, HIP step kernels) on the generic solver path")
+    p.add_argument('--broyden_threshold', default=None, type=int,
+                   help="(this build) --solver broyden: the largest number of steps (default: --and_maxiters); the history keeps min(threshold, 27) terms")
+    p.add_argument('--broyden_eps', default=1e-5, type=float,
+                   help="(this build) --solver broyden: stop when |f(z) - z| over the batch of a call falls below this")
     p.add_argument('--jacobian_json', default=None, metavar='FILE',
                    help="(this build) write the per-measurement Jacobian values and the histories of their iterations to FILE.  Implies --jacobian")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
@@ -141,7 +159,8 @@ def run(args):
     deq = None
     if args.baseline is None:
         loadpath = args.loadpath or checkpoint.shipped(SHIPPED[args.denoiser])
-        _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev)
+        _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev, solver_name=args.solver,
+                                broyden_threshold=args.broyden_threshold, broyden_eps=args.broyden_eps)
         opts = {}
         if args.conv64 != 'auto':
             opts["conv64"] = args.conv64
@@ -160,6 +179,8 @@ def run(args):
     if rank == 0:
         if deq is not None:
             print('loaded dict!')
+            if args.solver != 'anderson':
+                print(solver_line(deq))
         os.makedirs(args.savepath, exist_ok=True)
     images = {}
     ssim = bool(args.ssim or args.ssim_mode)
@@ -201,7 +222,10 @@ def run(args):
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
+    p = parser()
+    args = p.parse_args(argv)
+    if args.solver == 'broyden' and (args.snapshots is not None or args.trace):
+        p.error("--snapshots / --trace come out of the engine's Anderson / Picard loop: not available with --solver broyden")
     if str(args.inference).lower() in ('false', '0', ''):
         sys.exit("deqsci_amd is the inference hot path only: --inference False (training) is out of scope")
     if args.denoiser not in SHIPPED:

@@ -493,6 +493,12 @@ def print_horizons(results):
             print('---------------------------------', '[and_maxiters %d] Total Average PSNR: %.2f dB' % (K, p), '  SSIM: %.4f' % s)
 
 
+def solver_line(deep_eq_module):
+    """'solver: NAME (settings)' of a DEQFixedPoint: which fixed-point solver its forward runs, with the keyword arguments it passes."""
+    name = getattr(deep_eq_module.solver, "__name__", type(deep_eq_module.solver).__name__)
+    return "solver: %s (%s)" % (name, ", ".join("%s=%s" % kv for kv in sorted(deep_eq_module.kwargs.items())))
+
+
 def clip_line(r, ssim=False):
     """The pieces of a clip's printed line: the reference's, then this build's additions that were asked for."""
     parts = [[r.name], '  PSNR: %.2f dB' % r.mean_psnr]

@@ -388,7 +388,7 @@ class DEQFixedPoint(nn.Module):
         if extras:
             raise NotImplementedError("snapshots / trace exist on the engine's path only, and this call takes the generic solver (use_engine is "
                                       "off, f is not this package's EquilibriumProxGradSCI with A_torch_ / At_torch_, an unknown denoiser tag, "
-                                      "or a solver other than andersonexp / forward_iteration)")
+                                      "or a solver other than andersonexp / forward_iteration, such as broyden_fixed_point)")
         with torch.no_grad():
             z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
             z = self.f(z, x, Phi, Phi_sum)

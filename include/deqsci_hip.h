@@ -436,6 +436,35 @@ size_t deqsci_power_workspace_bytes(int64_t bsz, int64_t N);
 int deqsci_power_step_f32(const float* w, const float* v_prev, float* v_out, double* table_row, int64_t bsz, int64_t N,
                           void* workspace, deqsci_stream_t stream);
 
+/* ---- Broyden's method for g(x) = f(x) - x = 0 (deqsci_amd/broyden.py; the reference's solvers/broyd_equilibrium_utils.py:117-181) ----
+ * The history is two planar buffers U, V (bsz, L, N) fp32 with contiguous rows (the reference's Us, VTs), L <= DEQSCI_BROYDEN_MAX_L;
+ * dx (the update just taken), gx_old, gx_new, x, x_next, update are (bsz, N) dense fp32.  `table` holds
+ * DEQSCI_BROYDEN_TABLE_STRIDE doubles per sample: a_j = <dx, U_j> at [j], b_j = <V_j, dg> at [27 + j], c_j = <V_j, gx_new> at [54 + j]
+ * (j < t; the other entries are left alone), |gx_new|^2 at [81], d = <vT, dg> at [82], c_new = <vT, gx_new> at [83]; dg = gx_new - gx_old
+ * in fp32, never stored.  workspace = deqsci_broyden_workspace_bytes(bsz, N, L) bytes (0 for invalid sizes), no initialisation needed;
+ * deqsci_broyden_chunk() = the elements of a row one workgroup sums.  fp32 pointers 4-byte aligned (float4 accesses where every
+ * pointer is 16-byte aligned and N a multiple of 4; the results do not depend on it), table and workspace 8-byte aligned.
+ * B1+B2 deqsci_broyden_dots_f32: a_j, b_j, c_j for the t filled rows and |gx_new|^2, float64 products and sums in a fixed two-stage
+ *     order -> table.  Two launches.  t = 0 with dx = gx_old = gx_new: just the squared norm.
+ * B3+B4 deqsci_broyden_update_f32 (after B1+B2 with the same arguments): vT = -dx + sum_j a_j V_j -> V[slot] (NaN -> 0),
+ *     w = dx - (sum_j b_j U_j - dg), U[slot] = w / d (fp32 division, NaN -> 0), d and c_new in float64 from vT before its NaNs are
+ *     zeroed -> table, update = gx_new - sum_j c_j U_j over the rows j < max(t, slot + 1) in ascending j with the new row in its place
+ *     (a row it replaces, slot < t, does not contribute), x_next = x + update when x_next is given.  The coefficients are rounded to fp32
+ *     once, the combinations summed in fp32.  slot == t (the history fills) or slot < t == L (it wraps).  update may be dx or gx_new,
+ *     x_next may be x; none of the rows may overlap U or V.  Two launches.
+ * No allocation, no host synchronisation, no atomics: graph-capturable and deterministic, and a sample's results do not depend on the
+ * rest of the batch.  NULL -> -1; bsz <= 0, N <= 0, L < 1, L > 27, t > L, slot >= L, slot > t, slot < t < L -> -2; misaligned -> -3; bsz > 65535,
+ * N > 2^28, aliasing with the history -> -4. */
+#define DEQSCI_BROYDEN_MAX_L 27
+#define DEQSCI_BROYDEN_TABLE_STRIDE 84
+int64_t deqsci_broyden_chunk(void);
+size_t deqsci_broyden_workspace_bytes(int64_t bsz, int64_t N, int L);
+int deqsci_broyden_dots_f32(const float* U, const float* V, const float* dx, const float* gx_old, const float* gx_new, double* table,
+                            void* workspace, int64_t bsz, int64_t N, int L, int t, deqsci_stream_t stream);
+int deqsci_broyden_update_f32(float* U, float* V, const float* dx, const float* gx_old, const float* gx_new, const float* x, float* x_next,
+                              float* update, double* table, void* workspace, int64_t bsz, int64_t N, int L, int t, int slot,
+                              deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
