@@ -7,6 +7,7 @@ from .gaptv import GAP_TV_rec, denoise_tv_chambolle  # noqa: F401
 from .solvers import (EquilibriumProxGradSCI, andersonexp, forward_iteration, DEQFixedPoint,  # noqa: F401
                       EquilibriumADMMSCI, admmexp, DEQFixedPointADMM, initial_point_admm)
 from .broyden import broyden, broyden_fixed_point  # noqa: F401
+from .epsilon2 import epsilon2  # noqa: F401
 from .engine import DEQSCIEngine, sigma_schedule  # noqa: F401
 from .networks import FFDNet, DnCNN  # noqa: F401
 

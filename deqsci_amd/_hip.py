@@ -78,6 +78,8 @@ SIGNATURES = {
     "deqsci_power_step_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr],
     "deqsci_broyden_dots_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _ptr],
     "deqsci_broyden_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _int, _ptr],
+    "deqsci_epsilon2_norms_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr],
+    "deqsci_epsilon2_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -85,7 +87,7 @@ SIGNATURES = {
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
-                 "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk")
+                 "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk")
 
 
 class DeqsciHipError(RuntimeError):
@@ -131,6 +133,10 @@ def load():
     lib.deqsci_broyden_workspace_bytes.argtypes = [_i64, _i64, _int]
     lib.deqsci_broyden_chunk.restype = _i64
     lib.deqsci_broyden_chunk.argtypes = []
+    lib.deqsci_epsilon2_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_epsilon2_workspace_bytes.argtypes = [_i64, _i64]
+    lib.deqsci_epsilon2_chunk.restype = _i64
+    lib.deqsci_epsilon2_chunk.argtypes = []
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -1484,6 +1490,55 @@ def broyden_update(ws, dx, gx_old, gx_new, t, slot, update, x=None, x_next=None)
                                                 _p(x_next, "x_next", True), _p(update, "update"), ws.table.data_ptr(), ws.partials.data_ptr(),
                                                 ws.bsz, ws.N, ws.L, int(t), int(slot), _stream()), "broyden_update")
     return update
+
+
+# ----------------------------------------------------------------------------- the epsilon-algorithm (csrc/epsilon2.hip)
+EPSILON2_TABLE_STRIDE = 5
+# columns of Epsilon2Workspace.table: sum dx^2, sum df^2, sum d2^2 (without lam), sum (x_new - x)^2, sum x_new^2
+EPSILON2_A, EPSILON2_B, EPSILON2_C, EPSILON2_STEP, EPSILON2_NEW = 0, 1, 2, 3, 4
+
+
+def epsilon2_chunk():
+    """Elements of a row that one workgroup of the epsilon2 kernels sums (the first stage of their two-stage sums)."""
+    return int(load().deqsci_epsilon2_chunk())
+
+
+class Epsilon2Workspace:
+    """Caller-owned buffers of the epsilon2 step kernels: the float64 table (bsz, 5) and the chunk partials (the library never
+    allocates)."""
+
+    def __init__(self, bsz, N, device):
+        nbytes = int(load().deqsci_epsilon2_workspace_bytes(bsz, N))
+        if nbytes == 0:
+            raise DeqsciHipError(f"epsilon2 workspace: unsupported sizes bsz={bsz}, N={N}")
+        self.bsz, self.N = bsz, N
+        self.table = torch.zeros((bsz, EPSILON2_TABLE_STRIDE), device=device, dtype=torch.float64)
+        self.partials = torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
+
+
+def _epsilon2_rows(ws, what, **rows):
+    for name, r in rows.items():
+        if tuple(r.shape) != (ws.bsz, ws.N):
+            raise DeqsciHipError(f"{what}: {name} {tuple(r.shape)} must be {(ws.bsz, ws.N)}")
+
+
+def epsilon2_norms(ws, x, f_x, f_fx):
+    """ws.table[s, 0:3] <- the squared norms of dx = f_x - x, df = f_fx - f_x, d2 = df - dx (fp32 differences, float64 sums; two
+    launches, no host synchronisation)."""
+    _epsilon2_rows(ws, "epsilon2_norms", x=x, f_x=f_x, f_fx=f_fx)
+    with _dev(x):
+        _check(load().deqsci_epsilon2_norms_f32(_p(x, "x"), _p(f_x, "f_x"), _p(f_fx, "f_fx"), ws.table.data_ptr(), ws.partials.data_ptr(),
+                                                ws.bsz, ws.N, _stream()), "epsilon2_norms")
+
+
+def epsilon2_update(ws, x, f_x, f_fx, x_new, lam):
+    """After epsilon2_norms with the same rows: x_new = f_x + (df a - dx b) / (c + lam) in fp32 and ws.table[s, 3:5] <- the squared norms
+    of x_new - x and x_new (two launches, no host synchronisation).  x_new may overlap none of the inputs."""
+    _epsilon2_rows(ws, "epsilon2_update", x=x, f_x=f_x, f_fx=f_fx, x_new=x_new)
+    with _dev(x):
+        _check(load().deqsci_epsilon2_update_f32(_p(x, "x"), _p(f_x, "f_x"), _p(f_fx, "f_fx"), _p(x_new, "x_new"), ws.table.data_ptr(),
+                                                 ws.partials.data_ptr(), ws.bsz, ws.N, float(lam), _stream()), "epsilon2_update")
+    return x_new
 
 
 # ----------------------------------------------------------------------------- GAP-TV (csrc/tv.hip)

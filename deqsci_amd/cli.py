@@ -21,6 +21,11 @@ predictor at every reconstruction (deqsci_amd.jacobian) to each clip line and on
 broyd_equilibrium_utils.broyden on the device) instead of Anderson acceleration: `--broyden_threshold` steps at most (default:
 --and_maxiters), stopped when |f(z) - z| over the batch falls below `--broyden_eps`.  It runs on the generic solver path, so
 --snapshots / --trace (the engine's) are refused with it.
+`--solver epsilon2` (this build's) solves it with the vector epsilon-algorithm (deqsci_amd.epsilon2, the reference's epsilon2 on the
+device): --and_maxiters iterations of two f-calls at most, stopped when |x_new - x| / |x_new| over the batch falls below `--eps2_tol`;
+`--eps2_lam` is the regulariser of its denominator.  The generic solver path too: --snapshots / --trace are refused.
+`--solver picard` (this build's) runs the plain iteration z <- f(z) (forward_iteration) on the engine, --and_maxiters iterations at most;
+--snapshots / --trace work with it.
 """
 import argparse
 import os
@@ -35,7 +40,8 @@ from .harness import (SCITestDataset, clip_line, evaluate, jacobian_document, pn
 from .networks import DnCNN, FFDNet
 from .operators import A_torch_, At_torch_
 from .broyden import broyden_fixed_point
-from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp
+from .epsilon2 import epsilon2
+from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp, forward_iteration
 
 SHIPPED = {'ffdnet': 'ffdnet_gray', 'SimpleCNN': 'cnn', 'RealSN_SimpleCNN': 'rsn_cnn'}
 
@@ -52,7 +58,7 @@ def build_denoiser(name, n_channels=1):
 
 
 def build_pipeline(denoiser, loadpath=None, and_maxiters=100, and_m=5, and_beta=1.0, device="cuda", solver_name="anderson", broyden_threshold=None,
-                   broyden_eps=1e-5):
+                   broyden_eps=1e-5, eps2_tol=1e-2, eps2_lam=1e-4):
     net = build_denoiser(denoiser).eval()
     solver = EquilibriumProxGradSCI(A=A_torch_, At=At_torch_, nonlinear_operator=net, eta=0.2, minval=-1, maxval=1)
     if loadpath:
@@ -60,10 +66,14 @@ def build_pipeline(denoiser, loadpath=None, and_maxiters=100, and_m=5, and_beta=
     solver = solver.to(device)
     if solver_name == "broyden":
         deq = DEQFixedPoint(solver, broyden_fixed_point, threshold=and_maxiters if broyden_threshold is None else broyden_threshold, eps=broyden_eps)
+    elif solver_name == "epsilon2":
+        deq = DEQFixedPoint(solver, epsilon2, max_iter=and_maxiters, tol=eps2_tol, lam=eps2_lam)
+    elif solver_name == "picard":
+        deq = DEQFixedPoint(solver, forward_iteration, max_iter=and_maxiters, tol=1e-5)
     elif solver_name == "anderson":
         deq = DEQFixedPoint(solver, andersonexp, m=and_m, beta=and_beta, lam=1e-2, max_iter=and_maxiters, tol=1e-5)
     else:
-        raise ValueError(f"solver_name must be 'anderson' or 'broyden', got {solver_name!r}")
+        raise ValueError(f"solver_name must be 'anderson', 'broyden', 'epsilon2' or 'picard', got {solver_name!r}")
     return solver, deq
 
 
@@ -104,7 +114,7 @@ def parser():
                    help="(this build) how alpha is computed: reference (default) = the reference's own arithmetic - the fp32 Gram of "
                         "new_equilibrium_utils_yaping.py:177-178 in the summation order of its torch.bmm, fp32 LU - which reproduces the reference's "
                         "ensemble statistics on the chaotic FFDNet + Anderson @180 configuration (DESIGN.md section 5); float64 = Gram and solve in "
-                        "float64 (exact; 4 % faster at eight measurements per call, 14 % at one)")
+                        "float64 (exact; 4 %% faster at eight measurements per call, 14 %% at one)")
     p.add_argument('--batch_measurements', nargs='?', const='clip', default=None, choices=['clip', 'all'],
                    help="(this build) clip: a clip's measurements as ONE engine batch instead of the reference's one-by-one schedule (implied by "
                         "more than one --gpu_ids entry, which shards them); all: the measurements of all clips of one frame size as one batch "
@@ -130,13 +140,19 @@ def parser():
                    help="(this build) also report, at every reconstruction, the local Lipschitz constant Lip(f) and the spectral radius rho(f) of "
                         "the fixed-point map and the Lipschitz constant Lip(D) of the noise predictor (power iterations of N_ITERS steps, "
                         "default 30): per clip and one 'Total Average' line per quantity")
-    p.add_argument('--solver', default='anderson', choices=['anderson', 'broyden'],
+    p.add_argument('--solver', default='anderson', choices=['anderson', 'broyden', 'epsilon2', 'picard'],
                    help="(this build) the fixed-point solver: anderson (default) = Anderson acceleration on the engine; broyden = Broyden's method "
-                        "(the reference's broyd_equilibrium_utils.broyden, HIP step kernels) on the generic solver path")
+                        "(the reference's broyd_equilibrium_utils.broyden, HIP step kernels) on the generic solver path; epsilon2 = the vector "
+                        "epsilon-algorithm (the reference's epsilon2, HIP step kernels) on the generic solver path, --and_maxiters iterations of "
+                        "two f-calls at most; picard = the plain iteration z <- f(z) (forward_iteration) on the engine")
     p.add_argument('--broyden_threshold', default=None, type=int,
                    help="(this build) --solver broyden: the largest number of steps (default: --and_maxiters); the history keeps min(threshold, 27) terms")
     p.add_argument('--broyden_eps', default=1e-5, type=float,
                    help="(this build) --solver broyden: stop when |f(z) - z| over the batch of a call falls below this")
+    p.add_argument('--eps2_tol', default=1e-2, type=float,
+                   help="(this build) --solver epsilon2: stop when |x_new - x| / |x_new| over the batch of a call falls below this")
+    p.add_argument('--eps2_lam', default=1e-4, type=float,
+                   help="(this build) --solver epsilon2: the regulariser added to |d2|^2 in the extrapolation's denominator")
     p.add_argument('--jacobian_json', default=None, metavar='FILE',
                    help="(this build) write the per-measurement Jacobian values and the histories of their iterations to FILE.  Implies --jacobian")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
@@ -160,7 +176,7 @@ def run(args):
     if args.baseline is None:
         loadpath = args.loadpath or checkpoint.shipped(SHIPPED[args.denoiser])
         _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev, solver_name=args.solver,
-                                broyden_threshold=args.broyden_threshold, broyden_eps=args.broyden_eps)
+                                broyden_threshold=args.broyden_threshold, broyden_eps=args.broyden_eps, eps2_tol=args.eps2_tol, eps2_lam=args.eps2_lam)
         opts = {}
         if args.conv64 != 'auto':
             opts["conv64"] = args.conv64
@@ -224,8 +240,8 @@ def run(args):
 def main(argv=None):
     p = parser()
     args = p.parse_args(argv)
-    if args.solver == 'broyden' and (args.snapshots is not None or args.trace):
-        p.error("--snapshots / --trace come out of the engine's Anderson / Picard loop: not available with --solver broyden")
+    if args.solver in ('broyden', 'epsilon2') and (args.snapshots is not None or args.trace):
+        p.error(f"--snapshots / --trace come out of the engine's Anderson / Picard loop: not available with --solver {args.solver}")
     if str(args.inference).lower() in ('false', '0', ''):
         sys.exit("deqsci_amd is the inference hot path only: --inference False (training) is out of scope")
     if args.denoiser not in SHIPPED:
@@ -233,7 +249,7 @@ def main(argv=None):
     if args.snapshots is not None:
         from .engine import check_snapshots
         try:
-            check_snapshots(args.snapshots, args.and_maxiters, "anderson")
+            check_snapshots(args.snapshots, args.and_maxiters, "picard" if args.solver == "picard" else "anderson")
         except ValueError as e:
             sys.exit(f"--snapshots: {e}")
     ids = [int(v) for v in str(args.gpu_ids).split(',') if v != '']

@@ -465,6 +465,30 @@ int deqsci_broyden_update_f32(float* U, float* V, const float* dx, const float* 
                               float* update, double* table, void* workspace, int64_t bsz, int64_t N, int L, int t, int slot,
                               deqsci_stream_t stream);
 
+/* ---- The vector epsilon-algorithm, Aitken's delta-squared extrapolation of x, f(x), f(f(x)) (deqsci_amd/epsilon2.py; the reference's
+ * solvers/new_equilibrium_utils_yaping.py:194-211, epsilon2) ----
+ * x, f_x, f_fx, x_new are (bsz, N) dense fp32; dx = f_x - x, df = f_fx - f_x, d2 = df - dx are formed in fp32, never stored.  `table` holds
+ * DEQSCI_EPSILON2_TABLE_STRIDE doubles per sample: sum dx^2 at [0], sum df^2 at [1], sum d2^2 (without lam) at [2], sum (x_new - x)^2 at [3]
+ * (the difference rounded to fp32 first), sum x_new^2 at [4].  workspace = deqsci_epsilon2_workspace_bytes(bsz, N) bytes (0 for invalid
+ * sizes), no initialisation needed; deqsci_epsilon2_chunk() = the elements of a row one workgroup sums.  fp32 pointers 4-byte aligned
+ * (float4 accesses where every pointer is 16-byte aligned and N a multiple of 4; the results do not depend on it), table and workspace
+ * 8-byte aligned.
+ * E1+E2 deqsci_epsilon2_norms_f32: the three sums of squares, float64 products and sums in a fixed two-stage order -> table[s][0..2].
+ *     Two launches.
+ * E3+E2 deqsci_epsilon2_update_f32 (after E1+E2 with the same rows): a = fp32(table[s][0]), b = fp32(table[s][1]),
+ *     c = fp32(table[s][2]) + lam (an fp32 sum), x_new = f_x + (df * a - dx * b) / c elementwise in fp32 with every operation rounded
+ *     on its own, and the two sums of squares of the result -> table[s][3..4].  x_new may overlap none of x, f_x, f_fx (which may be one
+ *     another).  Two launches.
+ * No allocation, no host synchronisation, no atomics: graph-capturable and deterministic, and a sample's results do not depend on the
+ * rest of the batch.  NULL -> -1; bsz <= 0, N <= 0, N > 2^28 -> -2; misaligned -> -3; bsz > 65535, x_new overlapping an input -> -4. */
+#define DEQSCI_EPSILON2_TABLE_STRIDE 5
+int64_t deqsci_epsilon2_chunk(void);
+size_t deqsci_epsilon2_workspace_bytes(int64_t bsz, int64_t N);
+int deqsci_epsilon2_norms_f32(const float* x, const float* f_x, const float* f_fx, double* table, void* workspace, int64_t bsz, int64_t N,
+                              deqsci_stream_t stream);
+int deqsci_epsilon2_update_f32(const float* x, const float* f_x, const float* f_fx, float* x_new, double* table, void* workspace,
+                               int64_t bsz, int64_t N, float lam, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
