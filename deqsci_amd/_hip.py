@@ -1349,10 +1349,26 @@ def ssim_frames(x, y, layout=LAYOUT_HWB, window=11, mode="same", clamp_x=False):
     return out
 
 
+# ----------------------------------------------------------------------------- float64 row sums (csrc/rows.hpp)
+def _partials(nbytes, device, given=None, too_small=None):
+    """The float64 chunk partials of a *_workspace_bytes query (no initialisation needed): allocated, or the caller's `given`, checked."""
+    if given is None:
+        return torch.empty((max(int(nbytes) // 8, 1),), device=device, dtype=torch.float64)
+    if given.dtype != torch.float64 or given.numel() * 8 < nbytes or given.device != device:
+        raise DeqsciHipError(too_small)
+    return given
+
+
+def _same_rows(what, shape, **rows):
+    for name, r in rows.items():
+        if r is not None and tuple(r.shape) != shape:
+            raise DeqsciHipError(f"{what}: {name} {tuple(r.shape)} must be {shape}")
+
+
 # ----------------------------------------------------------------------------- per-f-call squared error (csrc/trace.hip)
 def sqerr_workspace(bsz, N, device):
     """The caller-owned workspace of sqerr_rows for (bsz, N) rows (float64 words; no initialisation needed)."""
-    return torch.empty((max(int(load().deqsci_sqerr_workspace_bytes(bsz, N)) // 8, 1),), device=device, dtype=torch.float64)
+    return _partials(load().deqsci_sqerr_workspace_bytes(bsz, N), device)
 
 
 def sqerr_rows(x, gt, out=None, clamp_x=True, workspace=None):
@@ -1374,10 +1390,8 @@ def sqerr_rows(x, gt, out=None, clamp_x=True, workspace=None):
         raise DeqsciHipError(f"sqerr_rows: out must be {bsz} contiguous float64 values on x's device")
     if bsz == 0 or N == 0:
         return out.zero_()
-    if workspace is None:
-        workspace = sqerr_workspace(bsz, N, x.device)
-    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < load().deqsci_sqerr_workspace_bytes(bsz, N) or workspace.device != x.device:
-        raise DeqsciHipError("sqerr_rows: workspace too small (sqerr_workspace(bsz, N, device))")
+    workspace = _partials(load().deqsci_sqerr_workspace_bytes(bsz, N), x.device, workspace,
+                          "sqerr_rows: workspace too small (sqerr_workspace(bsz, N, device))")
     with _dev(x):
         _check(load().deqsci_sqerr_rows_f32(x.data_ptr(), gt.data_ptr(), out.data_ptr(), bsz, N, x.stride(0) if bsz > 1 else max(x.stride(0), N),
                                             1 if clamp_x else 0, workspace.data_ptr(), _stream()), "sqerr_rows")
@@ -1411,7 +1425,7 @@ def ffdnet_head_masked(x, w_packed, mask, out=None):
 
 def power_workspace(bsz, N, device):
     """The caller-owned workspace of power_step for (bsz, N) rows (float64 words; no initialisation needed)."""
-    return torch.empty((max(int(load().deqsci_power_workspace_bytes(bsz, N)) // 8, 1),), device=device, dtype=torch.float64)
+    return _partials(load().deqsci_power_workspace_bytes(bsz, N), device)
 
 
 def power_step(w, v_prev, v_out, table_row, workspace=None):
@@ -1428,10 +1442,8 @@ def power_step(w, v_prev, v_out, table_row, workspace=None):
     if (not isinstance(table_row, torch.Tensor) or table_row.dtype != torch.float64 or tuple(table_row.shape) != (bsz, 2)
             or not table_row.is_contiguous() or table_row.device != w.device):
         raise DeqsciHipError(f"power_step: table_row must be a contiguous float64 ({bsz},2) tensor on w's device")
-    if workspace is None:
-        workspace = power_workspace(bsz, N, w.device)
-    elif workspace.dtype != torch.float64 or workspace.numel() * 8 < load().deqsci_power_workspace_bytes(bsz, N) or workspace.device != w.device:
-        raise DeqsciHipError("power_step: workspace too small (power_workspace(bsz, N, device))")
+    workspace = _partials(load().deqsci_power_workspace_bytes(bsz, N), w.device, workspace,
+                          "power_step: workspace too small (power_workspace(bsz, N, device))")
     with _dev(w):
         _check(load().deqsci_power_step_f32(_p(w, "w"), _p(v_prev, "v_prev", True), _p(v_out, "v_out"), table_row.data_ptr(), bsz, N,
                                             workspace.data_ptr(), _stream()), "power_step")
@@ -1464,18 +1476,12 @@ class BroydenWorkspace:
         self.U = torch.zeros((bsz, L, N), device=device, dtype=torch.float32)
         self.V = torch.zeros((bsz, L, N), device=device, dtype=torch.float32)
         self.table = torch.zeros((bsz, BROYDEN_TABLE_STRIDE), device=device, dtype=torch.float64)
-        self.partials = torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
-
-
-def _broyden_rows(ws, what, **rows):
-    for name, r in rows.items():
-        if r is not None and tuple(r.shape) != (ws.bsz, ws.N):
-            raise DeqsciHipError(f"{what}: {name} {tuple(r.shape)} must be {(ws.bsz, ws.N)}")
+        self.partials = _partials(nbytes, device)
 
 
 def broyden_dots(ws, dx, gx_old, gx_new, t):
     """ws.table[s] <- a_j, b_j, c_j (j < t) and |gx_new_s|^2 in float64 (two launches, no host synchronisation)."""
-    _broyden_rows(ws, "broyden_dots", dx=dx, gx_old=gx_old, gx_new=gx_new)
+    _same_rows("broyden_dots", (ws.bsz, ws.N), dx=dx, gx_old=gx_old, gx_new=gx_new)
     with _dev(ws.U):
         _check(load().deqsci_broyden_dots_f32(_p(ws.U), _p(ws.V), _p(dx, "dx"), _p(gx_old, "gx_old"), _p(gx_new, "gx_new"), ws.table.data_ptr(),
                                               ws.partials.data_ptr(), ws.bsz, ws.N, ws.L, int(t), _stream()), "broyden_dots")
@@ -1484,7 +1490,7 @@ def broyden_dots(ws, dx, gx_old, gx_new, t):
 def broyden_update(ws, dx, gx_old, gx_new, t, slot, update, x=None, x_next=None):
     """After broyden_dots with the same rows: the rank-one update into row `slot` of ws.U / ws.V, update = gx_new - sum_j c_j U_j and
     x_next = x + update when given (two launches, no host synchronisation).  update may be dx."""
-    _broyden_rows(ws, "broyden_update", dx=dx, gx_old=gx_old, gx_new=gx_new, update=update, x=x, x_next=x_next)
+    _same_rows("broyden_update", (ws.bsz, ws.N), dx=dx, gx_old=gx_old, gx_new=gx_new, update=update, x=x, x_next=x_next)
     with _dev(ws.U):
         _check(load().deqsci_broyden_update_f32(_p(ws.U), _p(ws.V), _p(dx, "dx"), _p(gx_old, "gx_old"), _p(gx_new, "gx_new"), _p(x, "x", True),
                                                 _p(x_next, "x_next", True), _p(update, "update"), ws.table.data_ptr(), ws.partials.data_ptr(),
@@ -1513,19 +1519,13 @@ class Epsilon2Workspace:
             raise DeqsciHipError(f"epsilon2 workspace: unsupported sizes bsz={bsz}, N={N}")
         self.bsz, self.N = bsz, N
         self.table = torch.zeros((bsz, EPSILON2_TABLE_STRIDE), device=device, dtype=torch.float64)
-        self.partials = torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
-
-
-def _epsilon2_rows(ws, what, **rows):
-    for name, r in rows.items():
-        if tuple(r.shape) != (ws.bsz, ws.N):
-            raise DeqsciHipError(f"{what}: {name} {tuple(r.shape)} must be {(ws.bsz, ws.N)}")
+        self.partials = _partials(nbytes, device)
 
 
 def epsilon2_norms(ws, x, f_x, f_fx):
     """ws.table[s, 0:3] <- the squared norms of dx = f_x - x, df = f_fx - f_x, d2 = df - dx (fp32 differences, float64 sums; two
     launches, no host synchronisation)."""
-    _epsilon2_rows(ws, "epsilon2_norms", x=x, f_x=f_x, f_fx=f_fx)
+    _same_rows("epsilon2_norms", (ws.bsz, ws.N), x=x, f_x=f_x, f_fx=f_fx)
     with _dev(x):
         _check(load().deqsci_epsilon2_norms_f32(_p(x, "x"), _p(f_x, "f_x"), _p(f_fx, "f_fx"), ws.table.data_ptr(), ws.partials.data_ptr(),
                                                 ws.bsz, ws.N, _stream()), "epsilon2_norms")
@@ -1534,7 +1534,7 @@ def epsilon2_norms(ws, x, f_x, f_fx):
 def epsilon2_update(ws, x, f_x, f_fx, x_new, lam):
     """After epsilon2_norms with the same rows: x_new = f_x + (df a - dx b) / (c + lam) in fp32 and ws.table[s, 3:5] <- the squared norms
     of x_new - x and x_new (two launches, no host synchronisation).  x_new may overlap none of the inputs."""
-    _epsilon2_rows(ws, "epsilon2_update", x=x, f_x=f_x, f_fx=f_fx, x_new=x_new)
+    _same_rows("epsilon2_update", (ws.bsz, ws.N), x=x, f_x=f_x, f_fx=f_fx, x_new=x_new)
     with _dev(x):
         _check(load().deqsci_epsilon2_update_f32(_p(x, "x"), _p(f_x, "f_x"), _p(f_fx, "f_fx"), _p(x_new, "x_new"), ws.table.data_ptr(),
                                                  ws.partials.data_ptr(), ws.bsz, ws.N, float(lam), _stream()), "epsilon2_update")

@@ -14,69 +14,26 @@
 //
 // The coefficients are rounded to fp32 once; the combinations are summed in fp32 in ascending j (products and sums rounded separately:
 // the library is built with -ffp-contract=off).  A float64 fma of two converted floats is exact in its product, so it IS product + sum.
-// Determinism: no atomics, no counters; element e of a row always belongs to thread ((e / 4) % TB) of chunk e / CHUNK, whether the row
-// is read as float4 (N a multiple of 4 and 16-byte aligned pointers) or element by element, so the sums do not depend on alignment,
-// and nothing depends on the other samples of the batch.  HBM-streaming: per step and sample 4 N (5 t + 13) bytes.
-#include "common.hpp"
+// Determinism: the two-stage order of csrc/rows.hpp (rows are read as float4 where N is a multiple of 4 and the pointers are 16-byte
+// aligned, else element by element: the same sums); nothing depends on the other samples of the batch.  HBM-streaming: per step and sample 4 N (5 t + 13) bytes.
+#include "rows.hpp"
 
 namespace deqsci {
 namespace broyden {
+
+using namespace rows;
 
 constexpr int MAXL = DEQSCI_BROYDEN_MAX_L;
 constexpr int TS = DEQSCI_BROYDEN_TABLE_STRIDE;          // doubles per sample of the table, and per (sample, chunk) of the partials
 constexpr int SLOT_A = 0, SLOT_B = MAXL, SLOT_C = 2 * MAXL, SLOT_GG = 3 * MAXL, SLOT_D = 3 * MAXL + 1, SLOT_CN = 3 * MAXL + 2;
 static_assert(SLOT_CN + 1 == TS, "table layout");
 constexpr int PER_THREAD = 2;                            // float4 per thread and row
-constexpr int64_t CHUNK = (int64_t)TB * 4 * PER_THREAD;  // 2048 elements per workgroup
-constexpr int NW = TB / WAVE;
+typedef Chunk<PER_THREAD> Ch;
+constexpr int64_t CHUNK = Ch::SIZE;                      // 2048 elements per workgroup
 
-// elements e .. e + 3 of a row, zeros beyond N (exact in every product and sum below)
-__device__ __forceinline__ float4 load4(const float* r, int64_t e, int64_t N, bool vec) {
-    if (vec && e + 4 <= N) return ld4(r + e);
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (e < N) v.x = r[e];
-    if (e + 1 < N) v.y = r[e + 1];
-    if (e + 2 < N) v.z = r[e + 2];
-    if (e + 3 < N) v.w = r[e + 3];
-    return v;
-}
-__device__ __forceinline__ void store4(float* r, int64_t e, int64_t N, bool vec, float4 v) {
-    if (vec && e + 4 <= N) { st4(r + e, v); return; }
-    if (e < N) r[e] = v.x;
-    if (e + 1 < N) r[e + 1] = v.y;
-    if (e + 2 < N) r[e + 2] = v.z;
-    if (e + 3 < N) r[e + 3] = v.w;
-}
-__device__ __forceinline__ double dot4(float4 a, float4 b, double acc) {
-    acc = fma((double)a.x, (double)b.x, acc);
-    acc = fma((double)a.y, (double)b.y, acc);
-    acc = fma((double)a.z, (double)b.z, acc);
-    return fma((double)a.w, (double)b.w, acc);
-}
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-// the workgroup's sum in a fixed order: wave butterfly, then the four wave sums in wave order (valid in every thread)
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-    static_assert(NW == 4, "block_sum adds exactly four wave sums");
-    v = wave_all_sum(v);
-    __syncthreads();                                      // the previous reader of wsum is done
-    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-__device__ __forceinline__ float nan_to_zero(float v) { return v != v ? 0.0f : v; }
-__device__ __forceinline__ float4 nan_to_zero(float4 v) {
-    return make_float4(nan_to_zero(v.x), nan_to_zero(v.y), nan_to_zero(v.z), nan_to_zero(v.w));
-}
 // every row of a (bsz, L, N) history starts 16-byte aligned iff the base does and N is a multiple of 4
-__device__ __forceinline__ bool all_vec(int64_t N, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                           reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(f);
-    return (bits & 15u) == 0 && (N & 3) == 0;
-}
+template <typename... P>
+__device__ __forceinline__ bool all_vec(int64_t N, const P*... p) { return aligned16_all(p...) && (N & 3) == 0; }
 
 // ---- B1
 __global__ __launch_bounds__(TB) void dots_partial_kernel(const float* __restrict__ U, const float* __restrict__ V, const float* __restrict__ dx,
@@ -90,14 +47,14 @@ __global__ __launch_bounds__(TB) void dots_partial_kernel(const float* __restric
     const float* dxr = dx + s * N;
     const float* g0r = g0 + s * N;
     const float* g1r = g1 + s * N;
-    const bool vec = all_vec(N, U, V, dx, g0, g1, nullptr);
+    const bool vec = all_vec(N, U, V, dx, g0, g1);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         float4 xv[PER_THREAD], dg[PER_THREAD], gn[PER_THREAD];
         double gg = 0.0;
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = Ch::elem(base, q, tid);
             xv[q] = load4(dxr, e, N, vec);
             gn[q] = load4(g1r, e, N, vec);
             dg[q] = gn[q] - load4(g0r, e, N, vec);
@@ -109,7 +66,7 @@ __global__ __launch_bounds__(TB) void dots_partial_kernel(const float* __restric
             float4 u[PER_THREAD], v[PER_THREAD];
 #pragma unroll
             for (int q = 0; q < PER_THREAD; ++q) {
-                const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+                const int64_t e = Ch::elem(base, q, tid);
                 u[q] = load4(Uj, e, N, vec);
                 v[q] = load4(Vj, e, N, vec);
             }
@@ -168,7 +125,7 @@ __global__ __launch_bounds__(TB) void rank_one_kernel(float* U, float* V, const 
     const float* dxr = dx + s * N;
     const float* g0r = g0 + s * N;
     const float* g1r = g1 + s * N;
-    const bool vec = all_vec(N, U, V, dx, g0, g1, nullptr);
+    const bool vec = all_vec(N, U, V, dx, g0, g1);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         float4 accv[PER_THREAD], accu[PER_THREAD];
@@ -178,7 +135,7 @@ __global__ __launch_bounds__(TB) void rank_one_kernel(float* U, float* V, const 
             const float a = af[j], b = bf[j];
 #pragma unroll
             for (int q = 0; q < PER_THREAD; ++q) {
-                const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+                const int64_t e = Ch::elem(base, q, tid);
                 accv[q] = accv[q] + a * load4(Vs + (int64_t)j * N, e, N, vec);
                 accu[q] = accu[q] + b * load4(Us + (int64_t)j * N, e, N, vec);
             }
@@ -186,7 +143,7 @@ __global__ __launch_bounds__(TB) void rank_one_kernel(float* U, float* V, const 
         double d = 0.0, cn = 0.0;
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = Ch::elem(base, q, tid);
             const float4 xv = load4(dxr, e, N, vec);
             const float4 gn = load4(g1r, e, N, vec);
             const float4 dg = gn - load4(g0r, e, N, vec);
@@ -235,13 +192,13 @@ __global__ __launch_bounds__(TB) void apply_kernel(float* U, const float* g1, co
     const float* xr = x ? x + s * N : nullptr;
     float* xn = x_next ? x_next + s * N : nullptr;
     float* up = update + s * N;
-    const bool vec = all_vec(N, U, g1, x, x_next, update, nullptr);
+    const bool vec = all_vec(N, U, g1, x, x_next, update);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         float4 u[PER_THREAD], acc[PER_THREAD];
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = base + ((int64_t)q * TB + tid) * 4;   // Ch::elem, spelled out
             u[q] = nan_to_zero(load4(Us + (int64_t)slot * N, e, N, vec) / f4(d32));
             store4(Us + (int64_t)slot * N, e, N, vec, u[q]);
             acc[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -250,13 +207,13 @@ __global__ __launch_bounds__(TB) void apply_kernel(float* U, const float* g1, co
             const float cj = cf[j];
 #pragma unroll
             for (int q = 0; q < PER_THREAD; ++q) {
-                const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+                const int64_t e = base + ((int64_t)q * TB + tid) * 4;   // Ch::elem, spelled out
                 acc[q] = acc[q] + cj * (j == slot ? u[q] : load4(Us + (int64_t)j * N, e, N, vec));
             }
         }
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = base + ((int64_t)q * TB + tid) * 4;   // Ch::elem, spelled out
             const float4 upd = load4(g1r, e, N, vec) - acc[q];
             if (xn) store4(xn, e, N, vec, load4(xr, e, N, vec) + upd);
             store4(up, e, N, vec, upd);
@@ -264,17 +221,9 @@ __global__ __launch_bounds__(TB) void apply_kernel(float* U, const float* g1, co
     }
 }
 
-inline bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 inline bool sizes_ok(int64_t bsz, int64_t N, int L) { return bsz > 0 && N > 0 && L >= 1 && L <= MAXL; }
 // (every workgroup of apply_kernel sums its sample's N / CHUNK partial pairs again: 2^28 elements are 2^17 of them, 512 per thread)
 inline bool supported(int64_t bsz, int64_t N) { return bsz <= 65535 && N <= ((int64_t)1 << 28); }
-// [p, p + n) and [q, q + m) floats share an element
-inline bool overlaps(const float* p, int64_t n, const float* q, int64_t m) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return p && q && a < b + (uintptr_t)m * 4 && b < a + (uintptr_t)n * 4;
-}
-inline dim3 grid_for(int64_t n_chunks, int64_t bsz) { return dim3((unsigned)(n_chunks < 65536 ? n_chunks : 65536), (unsigned)bsz); }
 
 }  // namespace broyden
 }  // namespace deqsci
@@ -294,14 +243,14 @@ int deqsci_broyden_dots_f32(const float* U, const float* V, const float* dx, con
                             void* workspace, int64_t bsz, int64_t N, int L, int t, deqsci_stream_t stream) {
     if (!U || !V || !dx || !gx_old || !gx_new || !table || !workspace) return DEQSCI_ERR_NULL;
     if (!broyden::sizes_ok(bsz, N, L) || t < 0 || t > L) return DEQSCI_ERR_SHAPE;
-    if (broyden::misaligned4(U) || broyden::misaligned4(V) || broyden::misaligned4(dx) || broyden::misaligned4(gx_old) ||
-        broyden::misaligned4(gx_new) || broyden::misaligned8(table) || broyden::misaligned8(workspace))
+    if (misaligned(U, 4) || misaligned(V, 4) || misaligned(dx, 4) || misaligned(gx_old, 4) ||
+        misaligned(gx_new, 4) || misaligned(table, 8) || misaligned(workspace, 8))
         return DEQSCI_ERR_ALIGN;
     if (!broyden::supported(bsz, N)) return DEQSCI_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, broyden::CHUNK);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(broyden::dots_partial_kernel, broyden::grid_for(n_chunks, bsz), dim3(TB), 0, st, U, V, dx, gx_old, gx_new, part, N,
+    hipLaunchKernelGGL(broyden::dots_partial_kernel, rows::chunk_grid(n_chunks, bsz), dim3(TB), 0, st, U, V, dx, gx_old, gx_new, part, N,
                        n_chunks, L, t);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(broyden::dots_final_kernel, dim3((unsigned)(3 * t + 1), (unsigned)bsz), dim3(TB), 0, st, (const double*)part, table,
@@ -315,20 +264,20 @@ int deqsci_broyden_update_f32(float* U, float* V, const float* dx, const float* 
     if (!U || !V || !dx || !gx_old || !gx_new || !update || !table || !workspace || (x_next && !x)) return DEQSCI_ERR_NULL;
     if (!broyden::sizes_ok(bsz, N, L) || t < 0 || t > L || slot < 0 || slot >= L || slot > t || (slot < t && t < L))
         return DEQSCI_ERR_SHAPE;                               // slot == t (the history fills) or slot < t == L (it wraps)
-    if (broyden::misaligned4(U) || broyden::misaligned4(V) || broyden::misaligned4(dx) || broyden::misaligned4(gx_old) ||
-        broyden::misaligned4(gx_new) || broyden::misaligned4(x) || broyden::misaligned4(x_next) || broyden::misaligned4(update) ||
-        broyden::misaligned8(table) || broyden::misaligned8(workspace))
+    if (misaligned(U, 4) || misaligned(V, 4) || misaligned(dx, 4) || misaligned(gx_old, 4) ||
+        misaligned(gx_new, 4) || misaligned(x, 4) || misaligned(x_next, 4) || misaligned(update, 4) ||
+        misaligned(table, 8) || misaligned(workspace, 8))
         return DEQSCI_ERR_ALIGN;
     if (!broyden::supported(bsz, N)) return DEQSCI_ERR_UNSUPPORTED;
-    const int64_t hist = bsz * L * N, row = bsz * N;
+    const int64_t hist = bsz * L * N * 4, row = bsz * N * 4;    // bytes
     const float* rows[] = {update, x_next, dx, gx_old, gx_new, x};      // none of them may be (part of) a history row
     for (const float* r : rows)
-        if (broyden::overlaps(r, row, U, hist) || broyden::overlaps(r, row, V, hist)) return DEQSCI_ERR_UNSUPPORTED;
-    if (broyden::overlaps(U, hist, V, hist) || broyden::overlaps(update, row, x_next, row)) return DEQSCI_ERR_UNSUPPORTED;
+        if (overlaps(r, row, U, hist) || overlaps(r, row, V, hist)) return DEQSCI_ERR_UNSUPPORTED;
+    if (overlaps(U, hist, V, hist) || overlaps(update, row, x_next, row)) return DEQSCI_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, broyden::CHUNK);
     double* part = static_cast<double*>(workspace);
-    const dim3 grid = broyden::grid_for(n_chunks, bsz);
+    const dim3 grid = rows::chunk_grid(n_chunks, bsz);
     hipLaunchKernelGGL(broyden::rank_one_kernel, grid, dim3(TB), 0, st, U, V, dx, gx_old, gx_new, (const double*)table, part, N, n_chunks, L, t,
                        slot);
     if (int e = launch_status()) return e;

@@ -164,6 +164,13 @@ __device__ __forceinline__ void sp16_track_block_max(float v, float unscale, flo
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// p is not a multiple of `bytes` (a power of two); a null pointer is aligned
+inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+// the byte ranges [a, a + na) and [b, b + nb) share a byte; a null pointer overlaps nothing
+inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return a && b && pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
+}
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Compute units of the current device (cached per device; a plain attribute query: no allocation, no synchronisation).

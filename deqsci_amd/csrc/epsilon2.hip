@@ -11,76 +11,27 @@
 //                             summed in float64 as in E1 -> part[sample][chunk][0..1]
 //   E2 again                  -> table[sample][3..4]
 //
-// A float64 fma of two converted floats is exact in its product, so it IS product + sum.  Determinism: no atomics, no counters; element e of
-// a row always belongs to thread ((e / 4) % TB) of chunk e / CHUNK, whether the row is read as float4 (N a multiple of 4 and 16-byte aligned
-// pointers) or element by element, so the sums do not depend on alignment, and nothing depends on the other samples of the batch.
+// Determinism: the two-stage order of csrc/rows.hpp (rows are read as float4 where N is a multiple of 4 and the pointers are 16-byte aligned,
+// else element by element: the same sums); nothing depends on the other samples of the batch.
 // HBM-streaming: per iteration and sample 28 N bytes (three rows read, then three read and one written).
-#include "common.hpp"
+#include "rows.hpp"
 
 namespace deqsci {
 namespace epsilon2 {
+
+using namespace rows;
 
 constexpr int TS = DEQSCI_EPSILON2_TABLE_STRIDE;         // doubles per sample of the table
 constexpr int COL_A = 0, COL_B = 1, COL_C = 2, COL_STEP = 3, COL_NEW = 4;
 static_assert(COL_NEW + 1 == TS, "table layout");
 constexpr int PS = 3;                                    // doubles per (sample, chunk) of the partials: E1 fills three, E3 two
 constexpr int PER_THREAD = 2;                            // float4 per thread and row
-constexpr int64_t CHUNK = (int64_t)TB * 4 * PER_THREAD;  // 2048 elements per workgroup
-constexpr int NW = TB / WAVE;
+typedef Chunk<PER_THREAD> Ch;
+constexpr int64_t CHUNK = Ch::SIZE;                      // 2048 elements per workgroup
 
-// elements e .. e + 3 of a row, zeros beyond N (exact in every square summed below)
-__device__ __forceinline__ float4 load4(const float* r, int64_t e, int64_t N, bool vec) {
-    if (vec && e + 4 <= N) return ld4(r + e);
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (e < N) v.x = r[e];
-    if (e + 1 < N) v.y = r[e + 1];
-    if (e + 2 < N) v.z = r[e + 2];
-    if (e + 3 < N) v.w = r[e + 3];
-    return v;
-}
-__device__ __forceinline__ void store4(float* r, int64_t e, int64_t N, bool vec, float4 v) {
-    if (vec && e + 4 <= N) { st4(r + e, v); return; }
-    if (e < N) r[e] = v.x;
-    if (e + 1 < N) r[e + 1] = v.y;
-    if (e + 2 < N) r[e + 2] = v.z;
-    if (e + 3 < N) r[e + 3] = v.w;
-}
-// zeros in the components beyond N (0 / c is not 0 for every c: what lies past the row must not reach a sum)
-__device__ __forceinline__ float4 inside4(float4 v, int64_t e, int64_t N) {
-    return make_float4(e < N ? v.x : 0.0f, e + 1 < N ? v.y : 0.0f, e + 2 < N ? v.z : 0.0f, e + 3 < N ? v.w : 0.0f);
-}
-__device__ __forceinline__ double sq4(float4 a, double acc) {
-    acc = fma((double)a.x, (double)a.x, acc);
-    acc = fma((double)a.y, (double)a.y, acc);
-    acc = fma((double)a.z, (double)a.z, acc);
-    return fma((double)a.w, (double)a.w, acc);
-}
-__device__ __forceinline__ double wave_all_sum(double v) {
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-// K <= PS sums of the workgroup in a fixed order: wave butterflies, then the four wave sums in wave order -> out[0..K-1] (threads 0..K-1)
-template <int K>
-__device__ __forceinline__ void block_sums_to(const double (&v)[K], double (*wsum)[PS], double* out) {
-    static_assert(NW == 4 && K <= PS, "block_sums_to adds exactly four wave sums");
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    double w[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) w[k] = wave_all_sum(v[k]);
-    __syncthreads();                                      // the previous reader of wsum is done
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) wsum[wave][k] = w[k];
-    }
-    __syncthreads();
-    if (tid < K) out[tid] = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
-}
-__device__ __forceinline__ bool all_vec(int64_t N, const void* a, const void* b, const void* c, const void* d) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                           reinterpret_cast<uintptr_t>(d);
-    return (bits & 15u) == 0 && (N & 3) == 0;
-}
+// every row of a (bsz, N) array starts 16-byte aligned iff the base does and N is a multiple of 4
+template <typename... P>
+__device__ __forceinline__ bool all_vec(int64_t N, const P*... p) { return aligned16_all(p...) && (N & 3) == 0; }
 
 // ---- E1
 __global__ __launch_bounds__(TB) void norms_partial_kernel(const float* __restrict__ x, const float* __restrict__ fx, const float* __restrict__ ffx,
@@ -91,13 +42,13 @@ __global__ __launch_bounds__(TB) void norms_partial_kernel(const float* __restri
     const float* xr = x + s * N;
     const float* fr = fx + s * N;
     const float* gr = ffx + s * N;
-    const bool vec = all_vec(N, x, fx, ffx, nullptr);
+    const bool vec = all_vec(N, x, fx, ffx);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         double v[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = Ch::elem(base, q, tid);
             const float4 xv = load4(xr, e, N, vec);
             const float4 fv = load4(fr, e, N, vec);
             const float4 dx = fv - xv;
@@ -139,7 +90,7 @@ __global__ __launch_bounds__(TB) void update_kernel(const float* __restrict__ x,
         double v[2] = {0.0, 0.0};
 #pragma unroll
         for (int q = 0; q < PER_THREAD; ++q) {
-            const int64_t e = base + ((int64_t)q * TB + tid) * 4;
+            const int64_t e = Ch::elem(base, q, tid);
             const float4 xv = load4(xr, e, N, vec);
             const float4 fv = load4(fr, e, N, vec);
             const float4 dx = fv - xv;
@@ -153,17 +104,9 @@ __global__ __launch_bounds__(TB) void update_kernel(const float* __restrict__ x,
     }
 }
 
-inline bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-inline bool misaligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) != 0; }
 // (fold_kernel's threads walk N / CHUNK partials: 2^28 elements are 2^17 of them, 512 per thread)
 inline bool sizes_ok(int64_t bsz, int64_t N) { return bsz > 0 && N > 0 && N <= ((int64_t)1 << 28); }
 inline bool supported(int64_t bsz) { return bsz <= 65535; }
-// [p, p + n) and [q, q + n) floats share an element
-inline bool overlaps(const float* p, const float* q, int64_t n) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)n * 4 && b < a + (uintptr_t)n * 4;
-}
-inline dim3 grid_for(int64_t n_chunks, int64_t bsz) { return dim3((unsigned)(n_chunks < 65536 ? n_chunks : 65536), (unsigned)bsz); }
 
 }  // namespace epsilon2
 }  // namespace deqsci
@@ -183,14 +126,14 @@ int deqsci_epsilon2_norms_f32(const float* x, const float* f_x, const float* f_f
                               deqsci_stream_t stream) {
     if (!x || !f_x || !f_fx || !table || !workspace) return DEQSCI_ERR_NULL;
     if (!epsilon2::sizes_ok(bsz, N)) return DEQSCI_ERR_SHAPE;
-    if (epsilon2::misaligned4(x) || epsilon2::misaligned4(f_x) || epsilon2::misaligned4(f_fx) || epsilon2::misaligned8(table) ||
-        epsilon2::misaligned8(workspace))
+    if (misaligned(x, 4) || misaligned(f_x, 4) || misaligned(f_fx, 4) || misaligned(table, 8) ||
+        misaligned(workspace, 8))
         return DEQSCI_ERR_ALIGN;
     if (!epsilon2::supported(bsz)) return DEQSCI_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, epsilon2::CHUNK);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(epsilon2::norms_partial_kernel, epsilon2::grid_for(n_chunks, bsz), dim3(TB), 0, st, x, f_x, f_fx, part, N, n_chunks);
+    hipLaunchKernelGGL(epsilon2::norms_partial_kernel, rows::chunk_grid(n_chunks, bsz), dim3(TB), 0, st, x, f_x, f_fx, part, N, n_chunks);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(epsilon2::fold_kernel, dim3(3, (unsigned)bsz), dim3(TB), 0, st, (const double*)part, table, n_chunks, epsilon2::COL_A);
     return launch_status();
@@ -200,17 +143,17 @@ int deqsci_epsilon2_update_f32(const float* x, const float* f_x, const float* f_
                                int64_t N, float lam, deqsci_stream_t stream) {
     if (!x || !f_x || !f_fx || !x_new || !table || !workspace) return DEQSCI_ERR_NULL;
     if (!epsilon2::sizes_ok(bsz, N)) return DEQSCI_ERR_SHAPE;
-    if (epsilon2::misaligned4(x) || epsilon2::misaligned4(f_x) || epsilon2::misaligned4(f_fx) || epsilon2::misaligned4(x_new) ||
-        epsilon2::misaligned8(table) || epsilon2::misaligned8(workspace))
+    if (misaligned(x, 4) || misaligned(f_x, 4) || misaligned(f_fx, 4) || misaligned(x_new, 4) ||
+        misaligned(table, 8) || misaligned(workspace, 8))
         return DEQSCI_ERR_ALIGN;
     if (!epsilon2::supported(bsz)) return DEQSCI_ERR_UNSUPPORTED;
-    const int64_t row = bsz * N;
-    if (epsilon2::overlaps(x_new, x, row) || epsilon2::overlaps(x_new, f_x, row) || epsilon2::overlaps(x_new, f_fx, row))
+    const int64_t row = bsz * N * 4;                          // bytes
+    if (overlaps(x_new, row, x, row) || overlaps(x_new, row, f_x, row) || overlaps(x_new, row, f_fx, row))
         return DEQSCI_ERR_UNSUPPORTED;                         // every workgroup reads its inputs through __restrict__ pointers
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, epsilon2::CHUNK);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(epsilon2::update_kernel, epsilon2::grid_for(n_chunks, bsz), dim3(TB), 0, st, x, f_x, f_fx, x_new, (const double*)table, part,
+    hipLaunchKernelGGL(epsilon2::update_kernel, rows::chunk_grid(n_chunks, bsz), dim3(TB), 0, st, x, f_x, f_fx, x_new, (const double*)table, part,
                        N, n_chunks, lam);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(epsilon2::fold_kernel, dim3(2, (unsigned)bsz), dim3(TB), 0, st, (const double*)part, table, n_chunks, epsilon2::COL_STEP);

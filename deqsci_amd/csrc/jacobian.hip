@@ -13,10 +13,10 @@
 //                                  writes its chunk of v_out = w / sqrt(a), and the workgroup of chunk 0 writes (a, b) to the table.
 //                                  a zero or not finite: v_out = 0 and (NaN, NaN) in the table - never a number that looks valid.
 //
-// Determinism: no atomics; element e of a row always belongs to thread ((e / 4) % TB) of chunk e / CHUNK, whether the row is read as
-// float4 or element by element, as in csrc/trace.hip.  fp32 is scale-free and the vectors are renormalised every step, so no range
+// Determinism: J2 sums in the two-stage order of csrc/rows.hpp, reading a row as float4 where the row starts are 16-byte aligned and
+// element by element elsewhere.  fp32 is scale-free and the vectors are renormalised every step, so no range
 // bookkeeping is needed.  HBM-streaming: J2 reads w twice and v_prev once, writes v_out once.
-#include "common.hpp"
+#include "rows.hpp"
 
 namespace deqsci {
 namespace jac {
@@ -87,49 +87,30 @@ __global__ __launch_bounds__(TB) void ffdnet_head_masked_kernel(const float* __r
 }
 
 // ---- J2
-constexpr int PER_THREAD = 4;                            // float4 loads per thread
-constexpr int64_t CHUNK = (int64_t)TB * 4 * PER_THREAD;  // 4096 elements per workgroup
+using namespace rows;
 
-// the workgroup's sum in a fixed order: wave butterfly, then the four wave sums in wave order (valid in every thread)
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-    static_assert(TB / WAVE == 4, "block_sum adds exactly four wave sums");
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    __syncthreads();                                      // the previous reader of wsum is done
-    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
+constexpr int PER_THREAD = 4;                            // float4 per thread and row
+typedef Chunk<PER_THREAD> Ch;
+constexpr int64_t CHUNK = Ch::SIZE;                      // 4096 elements per workgroup
 
 __global__ __launch_bounds__(TB) void power_partial_kernel(const float* __restrict__ w, const float* __restrict__ v_prev,
                                                            double* __restrict__ part, int64_t N, int64_t n_chunks) {
-    __shared__ double wsum[TB / WAVE];
+    __shared__ double wsum[NW];
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.y;
     const float* wr = w + s * N;
     const float* vr = v_prev ? v_prev + s * N : nullptr;
-    const bool vec = ((reinterpret_cast<uintptr_t>(wr) | reinterpret_cast<uintptr_t>(vr)) & 15u) == 0;
+    const bool vec = aligned16_all(wr, vr);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         double a = 0.0, b = 0.0;
 #pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) {
-            const int64_t e = base + ((int64_t)j * TB + tid) * 4;
-            if (vec && e + 4 <= N) {
-                const float4 x = ld4(wr + e);
-                const float4 y = vr ? ld4(vr + e) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                a += (double)x.x * (double)x.x; b += (double)y.x * (double)x.x;
-                a += (double)x.y * (double)x.y; b += (double)y.y * (double)x.y;
-                a += (double)x.z * (double)x.z; b += (double)y.z * (double)x.z;
-                a += (double)x.w * (double)x.w; b += (double)y.w * (double)x.w;
-            } else {
-                for (int q = 0; q < 4; ++q)
-                    if (e + q < N) {
-                        const double x = (double)wr[e + q];
-                        a += x * x;
-                        b += (vr ? (double)vr[e + q] : 0.0) * x;
-                    }
-            }
+        for (int q = 0; q < PER_THREAD; ++q) {
+            const int64_t e = Ch::elem(base, q, tid);
+            const float4 x = load4(wr, e, N, vec);
+            const float4 y = vr ? load4(vr, e, N, vec) : f4(0.0f);
+            a = sq4(x, a);
+            b = dot4(y, x, b);
         }
         a = block_sum(a, wsum);
         b = block_sum(b, wsum);
@@ -143,7 +124,7 @@ __global__ __launch_bounds__(TB) void power_partial_kernel(const float* __restri
 // v_out may be w or v_prev themselves (every element is read and written by the same thread; v_prev was consumed by the first stage)
 __global__ __launch_bounds__(TB) void power_normalise_kernel(const float* w, float* v_out, const double* __restrict__ part,
                                                              double* __restrict__ table_row, int has_prev, int64_t N, int64_t n_chunks) {
-    __shared__ double wsum[TB / WAVE];
+    __shared__ double wsum[NW];
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.y;
     // the sample's chunk pairs, thread t summing chunks t, t + TB, ... in order: the same order in every workgroup of the sample
@@ -163,20 +144,14 @@ __global__ __launch_bounds__(TB) void power_normalise_kernel(const float* w, flo
     const double rs = ok ? 1.0 / sqrt(a) : 0.0;
     const float* wr = w + s * N;
     float* vo = v_out + s * N;
-    const bool vec = ((reinterpret_cast<uintptr_t>(wr) | reinterpret_cast<uintptr_t>(vo)) & 15u) == 0;
+    const bool vec = aligned16_all(wr, vo);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
 #pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) {
-            const int64_t e = base + ((int64_t)j * TB + tid) * 4;
-            if (vec && e + 4 <= N) {
-                const float4 x = ld4(wr + e);
-                st4(vo + e, ok ? make_float4((float)(x.x * rs), (float)(x.y * rs), (float)(x.z * rs), (float)(x.w * rs))
-                               : make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-            } else {
-                for (int q = 0; q < 4; ++q)
-                    if (e + q < N) vo[e + q] = ok ? (float)(wr[e + q] * rs) : 0.0f;
-            }
+        for (int q = 0; q < PER_THREAD; ++q) {
+            const int64_t e = Ch::elem(base, q, tid);
+            const float4 x = load4(wr, e, N, vec);          // the products in float64, rounded to fp32 once
+            store4(vo, e, N, vec, ok ? make_float4((float)(x.x * rs), (float)(x.y * rs), (float)(x.z * rs), (float)(x.w * rs)) : f4(0.0f));
         }
     }
 }
@@ -198,7 +173,7 @@ int deqsci_ffdnet_head_masked_f32(const float* x, const float* w_packed, const u
     if (!x || !w_packed || !mask || !h) return DEQSCI_ERR_NULL;
     if (n <= 0 || H <= 0 || W <= 0) return DEQSCI_ERR_SHAPE;
     if (n > 65535 || H > (1 << 20) || W > (1 << 20)) return DEQSCI_ERR_UNSUPPORTED;
-    if (!aligned16(w_packed) || !aligned16(h) || (reinterpret_cast<uintptr_t>(mask) & 7u) || (reinterpret_cast<uintptr_t>(x) & 3u))
+    if (!aligned16(w_packed) || !aligned16(h) || misaligned(mask, 8) || misaligned(x, 4))
         return DEQSCI_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t* m32 = reinterpret_cast<const uint32_t*>(mask);
@@ -222,13 +197,12 @@ int deqsci_power_step_f32(const float* w, const float* v_prev, float* v_out, dou
     if (!jac::sizes_ok(bsz, N)) return DEQSCI_ERR_SHAPE;
     if (bsz == 0 || N == 0) return 0;
     if (!w || !v_out || !table_row || !workspace) return DEQSCI_ERR_NULL;
-    if ((reinterpret_cast<uintptr_t>(w) & 3u) || (reinterpret_cast<uintptr_t>(v_prev) & 3u) || (reinterpret_cast<uintptr_t>(v_out) & 3u) ||
-        (reinterpret_cast<uintptr_t>(table_row) & 7u) || (reinterpret_cast<uintptr_t>(workspace) & 7u))
+    if (misaligned(w, 4) || misaligned(v_prev, 4) || misaligned(v_out, 4) || misaligned(table_row, 8) || misaligned(workspace, 8))
         return DEQSCI_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, jac::CHUNK);
     double* part = static_cast<double*>(workspace);
-    const dim3 grid((unsigned)(n_chunks < 65536 ? n_chunks : 65536), (unsigned)bsz);
+    const dim3 grid = rows::chunk_grid(n_chunks, bsz);
     hipLaunchKernelGGL(jac::power_partial_kernel, grid, dim3(TB), 0, st, w, v_prev, part, N, n_chunks);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(jac::power_normalise_kernel, grid, dim3(TB), 0, st, w, v_out, (const double*)part, table_row, v_prev ? 1 : 0, N,

@@ -18,7 +18,7 @@
 // Determinism: no atomics; the per-thread, per-wave and per-workgroup summation orders are fixed, so are S2's.
 #include <math.h>
 
-#include "common.hpp"
+#include "rows.hpp"
 
 namespace deqsci {
 namespace ssim {
@@ -134,17 +134,12 @@ __global__ __launch_bounds__(TB) void ssim_tile_kernel(const float* __restrict__
     }
 }
 
-// one wave per (measurement, frame): lane l sums tiles l, l + 64, ... in order, then a fixed xor butterfly
+// one wave per (measurement, frame): its tile sums by rows::wave_fold, divided by the number of map values
 __global__ __launch_bounds__(TB) void ssim_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int64_t MB,
                                                          int64_t n_tiles, double count) {
-    const int lane = threadIdx.x & (WAVE - 1);
     for (int64_t i = (int64_t)blockIdx.x * (TB / WAVE) + threadIdx.x / WAVE; i < MB; i += (int64_t)gridDim.x * (TB / WAVE)) {
-        const double* p = part + i * n_tiles;
-        double s = 0.0;
-        for (int64_t t = lane; t < n_tiles; t += WAVE) s += p[t];
-#pragma unroll
-        for (int o = WAVE / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, WAVE);
-        if (lane == 0) out[i] = s / count;
+        const double s = rows::wave_fold(part + i * n_tiles, n_tiles);
+        if ((threadIdx.x & (WAVE - 1)) == 0) out[i] = s / count;
     }
 }
 
@@ -159,11 +154,6 @@ inline Taps make_taps(int win) {
     }
     for (int k = 0; k < win; ++k) tp.g[k] = tp.g[k] / sum;
     return tp;
-}
-
-inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
 }
 
 inline int64_t tiles_of(int64_t H, int64_t W) { return ceil_div(H, TH) * ceil_div(W, TW); }
@@ -195,14 +185,12 @@ int deqsci_ssim_f32(const float* x, const float* y, double* out, int64_t M, int6
     if (window < 3 || window > ssim::MAXWIN || window % 2 == 0) return DEQSCI_ERR_SHAPE;
     if (valid && (H < window || W < window)) return DEQSCI_ERR_SHAPE;          // empty interior
     if (M == 0 || B == 0) return 0;
-    if ((reinterpret_cast<uintptr_t>(x) & 3u) || (reinterpret_cast<uintptr_t>(y) & 3u) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 7u))
-        return DEQSCI_ERR_ALIGN;
+    if (misaligned(x, 4) || misaligned(y, 4) || misaligned(out, 8) || misaligned(workspace, 8)) return DEQSCI_ERR_ALIGN;
     const int64_t n_in = M * H * W * B * (int64_t)sizeof(float);
     const int64_t n_out = M * B * (int64_t)sizeof(double);
     const int64_t n_ws = deqsci_ssim_workspace_bytes(M, H, W, B, layout);
-    if (ssim::overlaps(out, n_out, x, n_in) || ssim::overlaps(out, n_out, y, n_in) || ssim::overlaps(workspace, n_ws, x, n_in) ||
-        ssim::overlaps(workspace, n_ws, y, n_in) || ssim::overlaps(workspace, n_ws, out, n_out))
+    if (overlaps(out, n_out, x, n_in) || overlaps(out, n_out, y, n_in) || overlaps(workspace, n_ws, x, n_in) ||
+        overlaps(workspace, n_ws, y, n_in) || overlaps(workspace, n_ws, out, n_out))
         return DEQSCI_ERR_UNSUPPORTED;
 
     hipStream_t st = static_cast<hipStream_t>(stream);

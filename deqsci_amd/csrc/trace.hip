@@ -6,73 +6,54 @@
 //   Q2 sqerr_reduce_kernel  one wave per sample: its chunk sums in a fixed order -> out[sample]
 //
 // x is a row of the Anderson history, F_hist[:, slot]: rows x_stride elements apart (m * N there); gt rows are dense (N apart).
-// Determinism: no atomics; element e of a row always belongs to thread ((e / 4) % TB) of chunk e / CHUNK, whether the row is read as
-// float4 (both row bases 16-byte aligned) or element by element (any other row; the tail of N % 4 != 0), so the summation order does
-// not depend on the alignment.  A NaN reaches the sum of its own sample only (the clamp is written with comparisons, which keep NaN).
+// Determinism: the two-stage order of csrc/rows.hpp (a row is read as float4 where both row starts are 16-byte aligned, else element by
+// element: the same sums).  A NaN reaches the sum of its own sample only (the clamp is written with comparisons, which keep NaN).
 // HBM-streaming: 8 bytes per element, read once.
-#include "common.hpp"
+#include "rows.hpp"
 
 namespace deqsci {
 namespace sqerr {
 
-constexpr int PER_THREAD = 4;                          // float4 loads per thread
-constexpr int64_t CHUNK = (int64_t)TB * 4 * PER_THREAD;  // 4096 elements per workgroup
+using namespace rows;
+
+constexpr int PER_THREAD = 4;                            // float4 per thread and row
+typedef Chunk<PER_THREAD> Ch;
+constexpr int64_t CHUNK = Ch::SIZE;                      // 4096 elements per workgroup
 
 __device__ __forceinline__ float clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }   // NaN stays NaN
-
-__device__ __forceinline__ double term(float xv, float gv, int clamp_x) {
-    if (clamp_x) xv = clamp01(xv);
-    const float d = xv - gv;
-    return (double)(d * d);
-}
+__device__ __forceinline__ float4 clamp01(float4 v) { return make_float4(clamp01(v.x), clamp01(v.y), clamp01(v.z), clamp01(v.w)); }
 
 __global__ __launch_bounds__(TB) void sqerr_chunk_kernel(const float* __restrict__ x, const float* __restrict__ gt,
                                                          double* __restrict__ part, int64_t N, int64_t x_stride, int clamp_x,
                                                          int64_t n_chunks) {
-    __shared__ double wsum[TB / WAVE];
+    __shared__ double wsum[NW];
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.y;
     const float* xr = x + s * x_stride;
     const float* gr = gt + s * N;
-    const bool vec = ((reinterpret_cast<uintptr_t>(xr) | reinterpret_cast<uintptr_t>(gr)) & 15u) == 0;
+    const bool vec = aligned16_all(xr, gr);
     for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int64_t base = c * CHUNK;
         double acc = 0.0;
 #pragma unroll
-        for (int j = 0; j < PER_THREAD; ++j) {
-            const int64_t e = base + ((int64_t)j * TB + tid) * 4;
-            if (vec && e + 4 <= N) {
-                const float4 a = ld4(xr + e), b = ld4(gr + e);
-                acc += term(a.x, b.x, clamp_x);
-                acc += term(a.y, b.y, clamp_x);
-                acc += term(a.z, b.z, clamp_x);
-                acc += term(a.w, b.w, clamp_x);
-            } else {
-                for (int q = 0; q < 4; ++q)
-                    if (e + q < N) acc += term(xr[e + q], gr[e + q], clamp_x);
-            }
+        for (int q = 0; q < PER_THREAD; ++q) {
+            const int64_t e = Ch::elem(base, q, tid);
+            const float4 xv = load4(xr, e, N, vec);
+            const float4 d = (clamp_x ? clamp01(xv) : xv) - load4(gr, e, N, vec);
+            const float4 sq = d * d;                       // fp32, as harness.psnr's (beyond N: +0.0)
+            acc = (((acc + (double)sq.x) + (double)sq.y) + (double)sq.z) + (double)sq.w;
         }
-        // workgroup sum in a fixed order: wave butterfly, then the four wave sums in wave order
-#pragma unroll
-        for (int o = WAVE / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, WAVE);
-        __syncthreads();                                   // the previous chunk's reader of wsum is done
-        if ((tid & (WAVE - 1)) == 0) wsum[tid / WAVE] = acc;
-        __syncthreads();
-        if (tid == 0) part[s * n_chunks + c] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+        acc = block_sum(acc, wsum);
+        if (tid == 0) part[s * n_chunks + c] = acc;
     }
 }
 
-// one wave per sample: lane l sums chunks l, l + 64, ... in order, then a fixed xor butterfly
+// one wave per sample: its chunk sums by wave_fold -> out[sample]
 __global__ __launch_bounds__(TB) void sqerr_reduce_kernel(const double* __restrict__ part, double* __restrict__ out, int64_t bsz,
                                                           int64_t n_chunks) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    for (int64_t i = (int64_t)blockIdx.x * (TB / WAVE) + threadIdx.x / WAVE; i < bsz; i += (int64_t)gridDim.x * (TB / WAVE)) {
-        const double* p = part + i * n_chunks;
-        double s = 0.0;
-        for (int64_t t = lane; t < n_chunks; t += WAVE) s += p[t];
-#pragma unroll
-        for (int o = WAVE / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, WAVE);
-        if (lane == 0) out[i] = s;
+    for (int64_t i = (int64_t)blockIdx.x * NW + threadIdx.x / WAVE; i < bsz; i += (int64_t)gridDim.x * NW) {
+        const double s = wave_fold(part + i * n_chunks, n_chunks);
+        if ((threadIdx.x & (WAVE - 1)) == 0) out[i] = s;
     }
 }
 
@@ -98,14 +79,11 @@ int deqsci_sqerr_rows_f32(const float* x, const float* gt, double* out, int64_t 
     if (!sqerr::sizes_ok(bsz, N) || x_stride < N) return DEQSCI_ERR_SHAPE;
     if (bsz == 0 || N == 0) return 0;
     if (!x || !gt || !out || !workspace) return DEQSCI_ERR_NULL;
-    if ((reinterpret_cast<uintptr_t>(x) & 3u) || (reinterpret_cast<uintptr_t>(gt) & 3u) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 7u))
-        return DEQSCI_ERR_ALIGN;
+    if (misaligned(x, 4) || misaligned(gt, 4) || misaligned(out, 8) || misaligned(workspace, 8)) return DEQSCI_ERR_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int64_t n_chunks = ceil_div(N, sqerr::CHUNK);
     double* part = static_cast<double*>(workspace);
-    const dim3 grid((unsigned)(n_chunks < 65536 ? n_chunks : 65536), (unsigned)bsz);
-    hipLaunchKernelGGL(sqerr::sqerr_chunk_kernel, grid, dim3(TB), 0, st, x, gt, part, N, x_stride, clamp_x, n_chunks);
+    hipLaunchKernelGGL(sqerr::sqerr_chunk_kernel, rows::chunk_grid(n_chunks, bsz), dim3(TB), 0, st, x, gt, part, N, x_stride, clamp_x, n_chunks);
     if (int e = launch_status()) return e;
     const int64_t nb = ceil_div(bsz, TB / WAVE);
     hipLaunchKernelGGL(sqerr::sqerr_reduce_kernel, dim3((unsigned)nb), dim3(TB), 0, st, part, out, bsz, n_chunks);

@@ -258,13 +258,6 @@ inline int check(int64_t n, int64_t H, int64_t W, int64_t B) {
     return 0;
 }
 
-inline bool overlaps(const void* a, int64_t na, const void* b, int64_t nb) {
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + (uintptr_t)nb && pb < pa + (uintptr_t)na;
-}
-
-inline bool mis(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 inline unsigned grid_for(int64_t n) {
     const int64_t b = ceil_div(n, TB);
     return (unsigned)(b < 65536 ? (b > 0 ? b : 1) : 65536);
@@ -316,16 +309,16 @@ int deqsci_gaptv_f32(const float* y, const float* phi, const float* phi_sum, flo
     if (maxiter < 0 || !isfinite(step) || !tv::params_ok(weight, eps, n_iter_max, 1.0)) return DEQSCI_ERR_SHAPE;
     if (B > tv::MAX_FRAMES) return DEQSCI_ERR_UNSUPPORTED;
     if (bsz == 0) return 0;
-    if (tv::mis(y, 4) || tv::mis(phi, 4) || tv::mis(phi_sum, 4) || tv::mis(out, 4) || tv::mis(stop, 4) || tv::mis(workspace, 16))
+    if (misaligned(y, 4) || misaligned(phi, 4) || misaligned(phi_sum, 4) || misaligned(out, 4) || misaligned(stop, 4) || misaligned(workspace, 16))
         return DEQSCI_ERR_ALIGN;
     const int64_t HW = H * W, nb = phi_shared ? 1 : bsz;
     const tv::Layout l = tv::layout_of(bsz * B, H, W, bsz);
     const int64_t n_out = bsz * HW * B * 4, n_stop = stop ? bsz * (int64_t)maxiter * B * 4 : 0;
-    if (tv::overlaps(workspace, l.total, y, bsz * HW * 4) || tv::overlaps(workspace, l.total, phi, nb * HW * B * 4) ||
-        tv::overlaps(workspace, l.total, phi_sum, nb * HW * 4) || tv::overlaps(workspace, l.total, out, n_out) ||
-        tv::overlaps(out, n_out, y, bsz * HW * 4) || tv::overlaps(out, n_out, phi, nb * HW * B * 4) ||
-        tv::overlaps(out, n_out, phi_sum, nb * HW * 4) ||
-        (stop && (tv::overlaps(stop, n_stop, workspace, l.total) || tv::overlaps(stop, n_stop, out, n_out))))
+    if (overlaps(workspace, l.total, y, bsz * HW * 4) || overlaps(workspace, l.total, phi, nb * HW * B * 4) ||
+        overlaps(workspace, l.total, phi_sum, nb * HW * 4) || overlaps(workspace, l.total, out, n_out) ||
+        overlaps(out, n_out, y, bsz * HW * 4) || overlaps(out, n_out, phi, nb * HW * B * 4) ||
+        overlaps(out, n_out, phi_sum, nb * HW * 4) ||
+        (stop && (overlaps(stop, n_stop, workspace, l.total) || overlaps(stop, n_stop, out, n_out))))
         return DEQSCI_ERR_UNSUPPORTED;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -355,11 +348,11 @@ int deqsci_tv_chambolle_f32(const float* image, float* out, int64_t n, int64_t H
     if (int e = tv::check(n, H, W, 1)) return e;
     if (!tv::params_ok(weight, eps, n_iter_max, tau)) return DEQSCI_ERR_SHAPE;
     if (n == 0) return 0;
-    if (tv::mis(image, 4) || tv::mis(out, 4) || tv::mis(stop, 4) || tv::mis(workspace, 16)) return DEQSCI_ERR_ALIGN;
+    if (misaligned(image, 4) || misaligned(out, 4) || misaligned(stop, 4) || misaligned(workspace, 16)) return DEQSCI_ERR_ALIGN;
     const tv::Layout l = tv::layout_of(n, H, W, 0);
     const int64_t nb = n * H * W * 4;
-    if (tv::overlaps(workspace, l.total, image, nb) || tv::overlaps(workspace, l.total, out, nb) || tv::overlaps(out, nb, image, nb) ||
-        (stop && (tv::overlaps(stop, n * 4, workspace, l.total) || tv::overlaps(stop, n * 4, out, nb))))
+    if (overlaps(workspace, l.total, image, nb) || overlaps(workspace, l.total, out, nb) || overlaps(out, nb, image, nb) ||
+        (stop && (overlaps(stop, n * 4, workspace, l.total) || overlaps(stop, n * 4, out, nb))))
         return DEQSCI_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);

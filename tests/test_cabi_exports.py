@@ -151,8 +151,8 @@ def test_kernel_sources_carry_no_experiment_switches():
     the measurement).  Every preprocessor conditional of csrc/ tests only the diagnostic build, the cycle-stamp profiling builds and
     WG_NO_CABI."""
     allowed = {"DEQSCI_DIAG", "S16_STAMP", "W16_STAMP", "W44_STAMP", "WG_STAMP", "WG_STAMP_TID", "WG_STAMP_SKIP", "WG_NO_CABI"}
-    csrc = sorted(f for f in os.listdir(os.path.join(ROOT, "deqsci_amd", "csrc")) if f.endswith(".hip") or f == "common.hpp")
-    assert "conv_s16.hip" in csrc and "conv_w16.hip" in csrc and "common.hpp" in csrc
+    csrc = sorted(f for f in os.listdir(os.path.join(ROOT, "deqsci_amd", "csrc")) if f.endswith((".hip", ".hpp")))
+    assert "conv_s16.hip" in csrc and "conv_w16.hip" in csrc and "common.hpp" in csrc and "rows.hpp" in csrc
     offending, seen = [], 0
     for src in csrc:
         for no, line in enumerate(open(os.path.join(ROOT, "deqsci_amd", "csrc", src)), 1):
