@@ -27,6 +27,18 @@ def read_state_dict(path):
         arc = np.load(path)
         sd = {k: torch.from_numpy(arc[k]) for k in arc.files if not k.startswith("__")}
         epoch = int(arc["__epoch__"]) if "__epoch__" in arc.files else None
+        # an archive split over several files (each within the size limit of a committed file: tests/golden/dncnn_noise15.npz): the
+        # first names the others, which lie next to it
+        for name in ([str(n) for n in arc["__parts__"]] if "__parts__" in arc.files else []):
+            part = os.path.join(os.path.dirname(path), name)
+            if os.path.basename(name) != name or not os.path.exists(part):
+                raise FileNotFoundError(f"checkpoint {path!r} names the part {name!r}, which is not next to it")
+            parc = np.load(part)
+            for k in parc.files:
+                if k in sd:
+                    raise KeyError(f"checkpoint part {part!r} repeats the key {k!r}")
+                if not k.startswith("__"):
+                    sd[k] = torch.from_numpy(parc[k])
     else:
         obj = torch.load(path, map_location="cpu", weights_only=False)
         epoch = obj.get("epoch") if isinstance(obj, dict) else None

@@ -44,16 +44,31 @@ from .epsilon2 import epsilon2
 from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp, forward_iteration
 
 SHIPPED = {'ffdnet': 'ffdnet_gray', 'SimpleCNN': 'cnn', 'RealSN_SimpleCNN': 'rsn_cnn'}
+# denoisers the reference's command line names and has weights for, but none trained for SCI: no shipped default, --loadpath names the checkpoint
+NO_DEFAULT = {'DnCNN': "the Provable-PnP DnCNN of 17 layers (a Gaussian denoiser: networks/provable/Pretrained_models/DnCNN_noise{5,15,40}.pth of the "
+                       "reference, or tests/golden/dncnn_noise15.npz of this repository)"}
+
+
+def default_loadpath(denoiser, loadpath=''):
+    """--loadpath as given, else the shipped archive of the denoiser; a denoiser without one (NO_DEFAULT) needs the flag: ValueError."""
+    if loadpath:
+        return loadpath
+    if denoiser in NO_DEFAULT:
+        raise ValueError(f"--denoiser {denoiser} has no shipped weights: pass --loadpath CHECKPOINT ({NO_DEFAULT[denoiser]})")
+    return checkpoint.shipped(SHIPPED[denoiser])
 
 
 def build_denoiser(name, n_channels=1):
-    """Factory of video_sci_proxgrad.py:145-185 restricted to the denoisers with shipped SCI weights."""
+    """Factory of video_sci_proxgrad.py:145-185 restricted to the denoisers with shipped SCI weights, and DnCNN (:172-174: the reference's
+    networks/provable/model/models.py:DnCNN - 17 layers, BatchNorm, the same state-dict keys - whose weights --loadpath names)."""
     if name == 'ffdnet':
         return FFDNet(num_input_channels=n_channels, tag='ffdnet')
     if name == 'SimpleCNN':
         return DnCNN(1, num_of_layers=4, lip=0.0, no_bn=True, tag='denoiser')
     if name == 'RealSN_SimpleCNN':
         return DnCNN(1, num_of_layers=4, lip=1.0, no_bn=True, tag='denoiser')
+    if name == 'DnCNN':
+        return DnCNN(1, num_of_layers=17, lip=0.0, no_bn=False, tag='denoiser')
     raise NotImplementedError('unknown denoiser!')
 
 
@@ -174,7 +189,7 @@ def run(args):
     rank, world, _, dev = distributed.init_from_env("nccl")
     deq = None
     if args.baseline is None:
-        loadpath = args.loadpath or checkpoint.shipped(SHIPPED[args.denoiser])
+        loadpath = default_loadpath(args.denoiser, args.loadpath)
         _, deq = build_pipeline(args.denoiser, loadpath, args.and_maxiters, args.and_m, args.and_beta, device=dev, solver_name=args.solver,
                                 broyden_threshold=args.broyden_threshold, broyden_eps=args.broyden_eps, eps2_tol=args.eps2_tol, eps2_lam=args.eps2_lam)
         opts = {}
@@ -244,8 +259,13 @@ def main(argv=None):
         p.error(f"--snapshots / --trace come out of the engine's Anderson / Picard loop: not available with --solver {args.solver}")
     if str(args.inference).lower() in ('false', '0', ''):
         sys.exit("deqsci_amd is the inference hot path only: --inference False (training) is out of scope")
-    if args.denoiser not in SHIPPED:
+    if args.denoiser not in SHIPPED and args.denoiser not in NO_DEFAULT:
         raise NotImplementedError('unknown denoiser!')
+    if args.baseline is None:
+        try:
+            default_loadpath(args.denoiser, args.loadpath)
+        except ValueError as e:
+            p.error(str(e))
     if args.snapshots is not None:
         from .engine import check_snapshots
         try:

@@ -234,6 +234,10 @@ class _Denoiser:
     # (FFDNet's 13: 138.8 -> 144.8 frames/s); on SimpleCNN's two layers it costs 4 % (180.6 vs 188.7: agent-scope loads re-read the halo
     # overlap from memory instead of the L2, and there is no kernel boundary worth saving between two 100 us launches)
     STACK_MIN_LAYERS = 3
+    # a plain conv + BN + ReLU network (tag 'denoiser') with a long run of 64->64 layers - DnCNN-17's 15 - goes slice by slice like FFDNet:
+    # 1->64 layer -> the run as ONE stack launch -> 64->1 layer (_plain_slices).  Set on the instance by a prepare() that is told the f-call's
+    # batch (n_img=: the engine's own); a bare prepare(n_calls, device) + run() keeps the launch per layer of the kernels' own tests and tools.
+    plain_sliced = False
 
     def _stack_for(self, idx, device, w16=False):
         """The Split16Stack (w16: Wino16Stack) of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a
@@ -279,6 +283,12 @@ class _Denoiser:
             return "layers"
         sp = (self.plain_head_w is not None and self.plain_tail_w is not None and packed
               and _hip.conv64_kernel_for(n, H, W, device, policy) == "s16")
+        run = self._middle_run() if (sp and not cal and self.stack and self.slice_edges and self.plain_sliced) else None
+        if run is not None and len(run) >= self.STACK_MIN_LAYERS and self._has_stack(self._stacks, run):
+            # DnCNN-17: the run of 64->64 layers as one stack launch per slice, as FFDNet's; the Winograd kernel reads the ranges the first
+            # f-call measured on the direct kernels (and its time-out fallback, "w16 per layer" below, needs them too)
+            w16 = self.stack_kernel == "w16" and self.conv64 != "s16" and self.ranges is not None and self._has_stack(self._wstacks, run)
+            return "w16 stack launch" if w16 else "s16 stack launch"
         if sp and not cal and self.stack_kernel == "w16" and self.conv64 != "s16" and self.ranges is not None:
             # the 64->64 layers on the split-fp16 Winograd kernel (csrc/conv_w16.hip: a third fewer matrix-core products), one launch per
             # layer (two layers: no run worth a stack launch), p32 activations from the first layer to the last; the ranges are the ones
@@ -299,7 +309,8 @@ class _Denoiser:
         path = self._route(bsz * B, H, W, device, self.conv64, False)
         if path not in ("w16 stack launch", "s16 stack launch"):
             return None
-        return self._slicing(path, self._middle_run(), bsz * B, H // 2, W // 2, device)[1]
+        f = 2 if self.tag == "ffdnet" else 1                      # (FFDNet's 64->64 layers run at half resolution)
+        return self._slicing(path, self._middle_run(), bsz * B, H // f, W // f, device)[1]
 
     def stack_timed_out(self):
         """(host sync) whether a wait inside a stack launch gave up since the last call: its results are invalid."""
@@ -367,6 +378,10 @@ class _Denoiser:
             self._stack_for(run, device)
             if self.stack_kernel == "w16" and self.tag == "ffdnet" and self.head_w16 is not None and self.tail_w16 is not None:
                 self._stack_for(run, device, w16=True)
+            if self.tag == "denoiser" and n_img is not None and self.plain_head_w is not None and self.plain_tail_w16 is not None:
+                self.plain_sliced = True
+                if self.stack_kernel == "w16" and self.conv64 != "s16":
+                    self._stack_for(run, device, w16=True)
         if self.tag == "ffdnet":
             t = self.sigma_table
             if t is None or t.numel() < n_calls or t.device != torch.device(device):
@@ -423,11 +438,18 @@ class _Denoiser:
             if path == "module":
                 out = self.net(x)
             elif path == "layers":
+                self.last_path = "per layer"
                 out = self._run_stack(x)
+            elif path in ("w16 stack launch", "s16 stack launch"):
+                out = yield from self._plain_slices(x, path)
+                self.last_path = path
             elif path == "w16 per layer":
+                # (behind a stack time-out: the stack launch's kernel and ranges, one launch per layer - its bits)
+                self.last_path = "w16 per layer (behind a stack time-out)" if self.per_layer_w16 else path
                 out = self._w16_per_layer(_hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], p32=True, out_rng=self._slot(1)),
                                           self.plain_tail_w16)
             else:
+                self.last_path = "per layer"
                 out = self._plain_per_layer(x, cal, path == "sp16 per layer")
             return out.reshape(bsz, B, H, W), True
         if self.tag == "conv2d":
@@ -457,6 +479,32 @@ class _Denoiser:
                 self.gate.release()
                 yield "stack"
             st.tail(ys, self.tail_w16, out=out[a:a + m])
+        self.stack_launches += 1
+        return out
+
+    def _plain_slices(self, x, path):
+        """(generator) _ffdnet_slices for a plain network (DnCNN-17) at full resolution: the 1->64 layer writes the slice's input buffer of
+        the path's stack in that stack's layout (p32 / sp16) with the range slots of its images, the run of 64->64 layers is one stack
+        launch, the 64->1 layer reads the buffer the run wrote.  The kernels, weights and ranges of the per-layer paths: their bits."""
+        n, H, W = x.shape[0], x.shape[2], x.shape[3]
+        run = self._middle_run()
+        st, per = self._slicing(path, run, n, H, W, x.device)
+        w16 = path == "w16 stack launch"
+        bufs, hbuf = st.state(min(per, n), H, W), st.head_buffer(min(per, n), H, W)
+        rows = None if self.ranges is None else self.ranges[run[0]:run[-1] + 2]
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        for a in range(0, n, per):
+            m = min(per, n - a)
+            hin = hbuf if m == hbuf.n else st.ACT(hbuf.t[:m], m, H, W)
+            out_rng = None if self.ranges is None else self._slot(1)[a:a + m]
+            hs = _hip.conv3x3_c1_to_64(x[a:a + m], self.plain_head_w, relu=self.fast[0][2], out=hin, p32=w16, sp16=not w16, out_rng=out_rng)
+            if self.gate is not None:
+                self.gate.acquire()
+            ys = st.launch(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
+            if self.gate is not None:
+                self.gate.release()
+                yield "stack"
+            st.tail(ys, self.plain_tail_w16, out=out[a:a + m])
         self.stack_launches += 1
         return out
 
