@@ -963,7 +963,7 @@ class _Stack:
     the tensors it points to (kept alive here), and per launch shape the progress words of the tiles (zeroed once: they count on from
     launch to launch) and the two ping-pong buffers (kept: a captured hipGraph carries their addresses).  Split16Stack and Wino16Stack
     name their kernel's activation class ACT, weights class WEIGHTS, block TILE (rows x columns of output pixels), measurement hook kind
-    HOOK and C entry point ENTRY, and the head, launch and tail functions of that layout (the engine's slice-by-slice f-call)."""
+    HOOK, C entry point ENTRY and launch function (the engine's slice-by-slice f-call; its first and last layer: engine._Edges)."""
     __slots__ = ("table", "n_layers", "keep", "_state")
 
     def __init__(self, layers, device):
@@ -1096,7 +1096,7 @@ class Split16Stack(_Stack):
     """A run of layers of Split16Weights for deqsci_conv3x3_c64_split16_stack (the direct kernel): Sp16 activations."""
     __slots__ = ()
     ACT, WEIGHTS, TILE, HOOK, ENTRY = Sp16, Split16Weights, (16, 32), "s16stack", "deqsci_conv3x3_c64_split16_stack"
-    head, launch, tail = staticmethod(ffdnet_head_split16), staticmethod(conv3x3_c64_split16_stack), staticmethod(tail_split16)
+    launch = staticmethod(conv3x3_c64_split16_stack)
 
 
 # ----------------------------------------------------------------------------- split-fp16 Winograd F(2,3) x direct (csrc/conv_w16.hip)
@@ -1222,7 +1222,7 @@ class Wino16Stack(_Stack):
     pixels."""
     __slots__ = ()
     ACT, WEIGHTS, TILE, HOOK, ENTRY = P32, Wino16Weights, (8, 64), "w16stack", "deqsci_conv3x3_c64_wino16_stack"
-    head, launch, tail = staticmethod(ffdnet_head_p32), staticmethod(conv3x3_c64_wino16_stack), staticmethod(ffdnet_tail_p32)
+    launch = staticmethod(conv3x3_c64_wino16_stack)
 
 
 class Conv64Weights:

@@ -89,6 +89,40 @@ def check_snapshots(snapshots, max_iter, iterator="anderson"):
     return tuple(out)
 
 
+class _Edges:
+    """The first and last layer of a conv + BN + ReLU denoiser as an f-call runs them - what differs between FFDNet (div = 2: its 64->64
+    layers run at half resolution, its first layer takes sigma and the range of the image, its last layer ends in a pixel shuffle) and a
+    plain network (div = 1: SimpleCNN, DnCNN-17, plugins), described once.  head_w / tail_w: the packs of the fp32 stencil kernels
+    (csrc/ffdnet_edges.hip), None where that layer has no HIP kernel; head_w16 / tail_w16: those of the kernels that write / read the
+    Sp16 and P32 layouts of the 64->64 layers (a plain first layer has one pack for all three)."""
+    __slots__ = ("div", "ffdnet", "relu", "head_w", "tail_w", "head_w16", "tail_w16")
+
+    def __init__(self, div=1, relu=True):
+        self.div, self.ffdnet, self.relu = div, div == 2, relu
+        self.head_w = self.tail_w = self.head_w16 = self.tail_w16 = None
+
+    def head(self, x, sigma, act=None, out=None, in_rng=None, out_rng=None, out_exp=_hip.SP16_DEFAULT_EXP, track=None):
+        """The first layer on x (n,1,H,W) as fp32 channels_last (act=None) or in the layout act (_hip.Sp16 / _hip.P32) with the range
+        (out_rng, out_exp); sigma and in_rng (the slots holding max |image|) are FFDNet's, track the slots of a measuring launch."""
+        if not self.ffdnet:
+            return _hip.conv3x3_c1_to_64(x, self.head_w, relu=self.relu, out=out, sp16=act is _hip.Sp16, p32=act is _hip.P32,
+                                         out_rng=out_rng, out_exp=out_exp, track=track)
+        if act is None:
+            return _hip.ffdnet_head(x, self.head_w, sigma)
+        if act is _hip.P32:
+            return _hip.ffdnet_head_p32(x, self.head_w16, sigma, out, in_rng, out_rng=out_rng, out_exp=out_exp)
+        return _hip.ffdnet_head_split16(x, self.head_w16, sigma, out, in_rng, out_rng=out_rng, out_exp=out_exp, track=track)
+
+    def tail(self, h, out=None, in_bias=None):
+        """The last layer (FFDNet: + pixel shuffle) on h in any of the three layouts; in_bias: the bias + ReLU the layer in front of an
+        fp32 h left to this one."""
+        if isinstance(h, _hip.P32):
+            return _hip.ffdnet_tail_p32(h, self.tail_w16, out)
+        if isinstance(h, _hip.Sp16):
+            return _hip.tail_split16(h, self.tail_w16, out)
+        return (_hip.ffdnet_tail if self.ffdnet else _hip.conv3x3_c64_to_1)(h.contiguous(memory_format=torch.channels_last), self.tail_w, out, in_bias)
+
+
 class _Denoiser:
     """Adapter from a reference-style denoiser plugin (nn.Module with .tag) to
     `run(z1_planar, call) -> (tensor (bsz,B,H,W), is_noise)`; dispatch as at
@@ -124,7 +158,6 @@ class _Denoiser:
         self.winograd = winograd
         self.conv64 = conv64                                        # _hip.conv64_kernel_for policy: "fast" | "fast32" | "f22" | "f44" | "s16"
         self.f22_calls = None                                       # f-calls [0, f22_calls) run F(2x2,3x3) whatever the policy (DEQSCIEngine)
-        self._native_out = False
         self._policy = conv64
         self.blk32 = bool(blk32)                                    # blk32 activations between F(4x4,3x3) layers (False: an A/B of the tools)
         # The scales of the split-fp16 layers' activations: "data" = every activation's power-of-two scale follows max |activation| as
@@ -150,6 +183,9 @@ class _Denoiser:
         self._wkey = None
         self._refresh()
 
+    # the edge layers' packs (self.edges), under the names tools and tests read
+    head_w, tail_w, head_w16, tail_w16 = (property(lambda self, k=k: getattr(self.edges, k)) for k in ("head_w", "tail_w", "head_w16", "tail_w16"))
+
     def _weights_key(self):
         return tuple((t.data_ptr(), t._version) for t in list(self.net.parameters()) + list(self.net.buffers()))
 
@@ -164,8 +200,7 @@ class _Denoiser:
         self._wkey = key
         self.fast = None
         self.wino = None
-        self.tail_w = self.head_w = self.tail_w16 = self.head_w16 = None
-        self.plain_head_w = self.plain_tail_w = self.plain_tail_w16 = None
+        self.edges = e = _Edges(2 if isinstance(net, FFDNet) else 1)
         seq = None
         if isinstance(net, FFDNet) and not net.training and net.num_input_channels == 1 and self.fold_bn:
             seq = net.intermediate_dncnn.itermediate_dncnn
@@ -188,34 +223,23 @@ class _Denoiser:
             self.ranges = None
             self._stacks = {}
             self._wstacks = {}
-            if (not isinstance(net, FFDNet) and self.fused_edges and self.channels_last and layers[0][0].is_cuda):
-                # SimpleCNN-style stacks: 1 -> 64 (+ReLU) and 64 -> 1 edge layers as HIP stencils (csrc/ffdnet_edges.hip)
-                if tuple(layers[0][0].shape) == (64, 1, 3, 3) and layers[0][1] is None:
-                    self.plain_head_w = _hip.pack_c1_to_64_weights(layers[0][0])
-                if tuple(layers[-1][0].shape) == (1, 64, 3, 3) and layers[-1][1] is None and not layers[-1][2]:
-                    self.plain_tail_w = _hip.pack_c64_to_1_weights(layers[-1][0])
-                    self.plain_tail_w16 = _hip.TailSplit16Weights(layers[-1][0])
-                if (s16 and self.stack_kernel == "w16" and self.conv64 != "s16"
-                        and self.plain_head_w is not None and self.plain_tail_w16 is not None):
-                    for u in self.wino[1:-1]:                    # (the Winograd pack of the middle layers: here, never inside a capture)
-                        if u is not None:
-                            u.w16
-            if (isinstance(net, FFDNet) and self.fused_edges and self.channels_last and layers[-1][1] is None
-                    and not layers[-1][2] and tuple(layers[-1][0].shape) == (4, 64, 3, 3) and layers[-1][0].is_cuda):
-                # last layer + upsamplefeatures as one HIP stencil kernel (csrc/ffdnet_edges.hip)
-                self.tail_w = _hip.pack_tail_weights(layers[-1][0])
-                self.tail_w16 = _hip.TailSplit16Weights(layers[-1][0])          # the same layer for an sp16 input (MFMA form)
-                if layers[0][1] is None and layers[0][2] and tuple(layers[0][0].shape) == (64, 5, 3, 3):
-                    # concatenate_input_noise_map + first conv + ReLU likewise
-                    self.head_w = _hip.pack_head_weights(layers[0][0])
-                    self.head_w16 = _hip.HeadSplit16Weights(layers[0][0])        # the same layer writing sp16 (f16 matrix-core form)
+            (w0, b0, e.relu), (wl, bl, relu_l) = layers[0], layers[-1]
+            if self.fused_edges and self.channels_last and w0.is_cuda and bl is None and not relu_l and tuple(wl.shape) == (e.div ** 2, 64, 3, 3):
+                # the last layer (FFDNet: + upsamplefeatures) as one HIP stencil kernel (csrc/ffdnet_edges.hip), and for an sp16 / p32 input (MFMA form)
+                e.tail_w = (_hip.pack_tail_weights if e.ffdnet else _hip.pack_c64_to_1_weights)(wl)
+                e.tail_w16 = _hip.TailSplit16Weights(wl)
+            if self.fused_edges and self.channels_last and w0.is_cuda and b0 is None:
+                if e.ffdnet and e.tail_w is not None and e.relu and tuple(w0.shape) == (64, 5, 3, 3):
+                    # concatenate_input_noise_map + first conv + ReLU likewise, and writing sp16 / p32 (f16 matrix-core form)
+                    e.head_w, e.head_w16 = _hip.pack_head_weights(w0), _hip.HeadSplit16Weights(w0)
+                elif not e.ffdnet and tuple(w0.shape) == (64, 1, 3, 3):
+                    e.head_w = e.head_w16 = _hip.pack_c1_to_64_weights(w0)      # (one stencil kernel, three output layouts)
 
     def _run_stack(self, h, skip_last=False, skip_first=False, defer_last_epilogue=False, native_out=False):
         """defer_last_epilogue: leave the bias+ReLU of the last executed layer to the consumer (the fused
         FFDNet tail applies it while staging its input) and return (raw conv output, bias) - only when that
         layer runs on MIOpen; the HIP 64->64 kernels apply bias+ReLU in their own epilogue for free.
         native_out: the consumer reads the split-fp16 kernel's sp16 layout directly (the HIP tails do): do not convert back."""
-        self._native_out = native_out
         if self.channels_last and not isinstance(h, _hip.Sp16):
             h = h.contiguous(memory_format=torch.channels_last)
         fused = self.fused_epilogue and h.is_cuda
@@ -225,17 +249,17 @@ class _Denoiser:
             last = idx[-1]
             w, b, relu = self.fast[last]
             if self.wino[last] is not None and h.is_cuda:
-                return self._run_layers(h, idx, fused), None
+                return self._run_layers(h, idx, fused, native_out), None
             assert b is not None and relu
-            return F.conv2d(self._run_layers(h, idx[:-1], fused), w, None, padding=1), b
-        return self._run_layers(h, idx, fused)
+            return F.conv2d(self._run_layers(h, idx[:-1], fused, native_out), w, None, padding=1), b
+        return self._run_layers(h, idx, fused, native_out)
 
     # a run shorter than this keeps its per-layer launches: the stack launch earns its keep over many layers on a cache-resident slice
     # (FFDNet's 13: 138.8 -> 144.8 frames/s); on SimpleCNN's two layers it costs 4 % (180.6 vs 188.7: agent-scope loads re-read the halo
     # overlap from memory instead of the L2, and there is no kernel boundary worth saving between two 100 us launches)
     STACK_MIN_LAYERS = 3
     # a plain conv + BN + ReLU network (tag 'denoiser') with a long run of 64->64 layers - DnCNN-17's 15 - goes slice by slice like FFDNet:
-    # 1->64 layer -> the run as ONE stack launch -> 64->1 layer (_plain_slices).  Set on the instance by a prepare() that is told the f-call's
+    # 1->64 layer -> the run as ONE stack launch -> 64->1 layer (_sliced).  Set on the instance by a prepare() that is told the f-call's
     # batch (n_img=: the engine's own); a bare prepare(n_calls, device) + run() keeps the launch per layer of the kernels' own tests and tools.
     plain_sliced = False
 
@@ -265,42 +289,33 @@ class _Denoiser:
         they are NOW: tests and tools set them between calls, and the engine turns `stack` off and `per_layer_w16` on behind a time-out."""
         if self.fast is None or self.tag not in ("ffdnet", "denoiser"):
             return "module"
-        cuda = torch.device(device).type == "cuda"
-        packed = all(u is not None for u in self.wino[1:-1])
-        if self.tag == "ffdnet":
-            # a run of 64->64 layers on the split-fp16 kernel: the head writes its sp16 layout, the tail reads it - no conversion pass
-            sp = (cuda and self.head_w is not None and self.tail_w is not None and packed
-                  and _hip.conv64_kernel_for(n, H // 2, W // 2, device, policy) == "s16")
-            run = self._middle_run()
-            if (sp and not cal and self.stack and self.slice_edges and run is not None and len(run) >= self.STACK_MIN_LAYERS
-                    and self._has_stack(self._stacks, run)):
-                return "w16 stack launch" if self.stack_kernel == "w16" and self._has_stack(self._wstacks, run) else "s16 stack launch"
-            if (sp and not cal and not self.stack and self.per_layer_w16 and self.stack_kernel == "w16" and self.ranges is not None
-                    and self._has_stack(self._wstacks, run)):
-                return "w16 per layer"
-            return "sp16 per layer" if sp else "per layer"
-        if not (cuda and (self.plain_head_w is not None or self.plain_tail_w is not None)):
+        e, cuda = self.edges, torch.device(device).type == "cuda"
+        if not e.ffdnet and not (cuda and (e.head_w is not None or e.tail_w is not None)):
             return "layers"
-        sp = (self.plain_head_w is not None and self.plain_tail_w is not None and packed
-              and _hip.conv64_kernel_for(n, H, W, device, policy) == "s16")
-        run = self._middle_run() if (sp and not cal and self.stack and self.slice_edges and self.plain_sliced) else None
-        if run is not None and len(run) >= self.STACK_MIN_LAYERS and self._has_stack(self._stacks, run):
-            # DnCNN-17: the run of 64->64 layers as one stack launch per slice, as FFDNet's; the Winograd kernel reads the ranges the first
-            # f-call measured on the direct kernels (and its time-out fallback, "w16 per layer" below, needs them too)
-            w16 = self.stack_kernel == "w16" and self.conv64 != "s16" and self.ranges is not None and self._has_stack(self._wstacks, run)
-            return "w16 stack launch" if w16 else "s16 stack launch"
-        if sp and not cal and self.stack_kernel == "w16" and self.conv64 != "s16" and self.ranges is not None:
-            # the 64->64 layers on the split-fp16 Winograd kernel (csrc/conv_w16.hip: a third fewer matrix-core products), one launch per
-            # layer (two layers: no run worth a stack launch), p32 activations from the first layer to the last; the ranges are the ones
-            # the first f-call measured on the direct kernels.  conv64="s16" means the direct kernel (ADVICE r5).  (A long DnCNN-style run
-            # - a user plugin; test_plugin_stack_dncnn17_follows_the_data_scale - takes this path too: per-layer Winograd launches, a third
-            # fewer matrix-core products than its one direct stack launch.)
+        run = self._middle_run()
+        # a run of 64->64 layers on the split-fp16 kernel: the head writes its sp16 layout, the tail reads it - no conversion pass
+        # (_middle_run has looked at the packs already where it names a run)
+        sp = (cuda and e.head_w is not None and e.tail_w is not None and (run is not None or all(u is not None for u in self.wino[1:-1]))
+              and _hip.conv64_kernel_for(n, H // e.div, W // e.div, device, policy) == "s16")
+        # the Winograd kernel of a plain network reads the ranges the first f-call measured on the direct kernels (and its time-out
+        # fallback, "w16 per layer" below, needs them too); conv64="s16" means the direct kernel there (ADVICE r5)
+        w16 = self.stack_kernel == "w16" and (e.ffdnet or (self.conv64 != "s16" and self.ranges is not None))
+        if (sp and not cal and self.stack and self.slice_edges and (e.ffdnet or self.plain_sliced) and run is not None
+                and len(run) >= self.STACK_MIN_LAYERS and self._has_stack(self._stacks, run)):
+            # FFDNet, DnCNN-17: first layer -> the run of 64->64 layers as one stack launch -> last layer, slice by slice
+            return "w16 stack launch" if w16 and self._has_stack(self._wstacks, run) else "s16 stack launch"
+        # FFDNet behind a stack time-out: the stack launch's kernel and ranges, one launch per layer.  A plain network: the 64->64 layers
+        # on the split-fp16 Winograd kernel (csrc/conv_w16.hip: a third fewer matrix-core products) whenever they do not go out as a stack
+        # launch - SimpleCNN's two (no run worth one), a long DnCNN-style run of a user plugin or of a bare prepare()
+        # (test_plugin_stack_dncnn17_follows_the_data_scale), and behind a time-out
+        if (sp and not cal and w16 and self.ranges is not None
+                and (not e.ffdnet or (not self.stack and self.per_layer_w16 and self._has_stack(self._wstacks, run)))):
             return "w16 per layer"
         return "sp16 per layer" if sp else "per layer"
 
-    def _slicing(self, path, run, n, H, W, device):
+    def _slicing(self, path, n, H, W, device):
         """(stack, images per stack launch) of an f-call on a "... stack launch" path, n images of H x W at the 64->64 layers."""
-        st = (self._wstacks if path == "w16 stack launch" else self._stacks)[run[0]]
+        st = (self._wstacks if path == "w16 stack launch" else self._stacks)[1]       # (_middle_run: layers 1 .. len(fast) - 2)
         return st, self.stack_per_launch or _hip.split16_stack_per_launch(n, H, W, cus=_hip._cus(device), tile=st.TILE)
 
     def stack_slice(self, bsz, B, H, W, device):
@@ -309,15 +324,15 @@ class _Denoiser:
         path = self._route(bsz * B, H, W, device, self.conv64, False)
         if path not in ("w16 stack launch", "s16 stack launch"):
             return None
-        f = 2 if self.tag == "ffdnet" else 1                      # (FFDNet's 64->64 layers run at half resolution)
-        return self._slicing(path, self._middle_run(), bsz * B, H // f, W // f, device)[1]
+        f = self.edges.div                                         # (FFDNet's 64->64 layers run at half resolution)
+        return self._slicing(path, bsz * B, H // f, W // f, device)[1]
 
     def stack_timed_out(self):
         """(host sync) whether a wait inside a stack launch gave up since the last call: its results are invalid."""
         return any([st.timed_out() for st in list(self._stacks.values()) + list(self._wstacks.values())])    # (every stack: the words are rearmed)
 
-    def _run_layers(self, h, idx, fused):
-        if (self.stack and isinstance(h, _hip.Sp16) and len(idx) >= self.STACK_MIN_LAYERS and self._native_out and not self._calibrating
+    def _run_layers(self, h, idx, fused, native_out):
+        if (self.stack and isinstance(h, _hip.Sp16) and len(idx) >= self.STACK_MIN_LAYERS and native_out and not self._calibrating
                 and self._has_stack(self._stacks, idx) and (h.rng is None) == (self.ranges is None)):
             # the whole run in one launch (per slice of the batch): sp16 in, sp16 out, ranges of the run = slots idx[0] .. idx[-1] + 1
             self.stack_launches += 1
@@ -339,7 +354,7 @@ class _Denoiser:
                             _hip.absmax(h, self._slot(i))
                             self._measured = True
                         h = _hip.to_split16(h, rng=self._slot(i))
-                    sp_out = chain or (nxt is None and self._native_out)
+                    sp_out = chain or (nxt is None and native_out)
                     if sp_out and self._calibrating:               # measure max |output| of this layer, then write it with that range
                         _hip.conv3x3_c64_split16(h, self.wino[i].s16, b, relu, track=self._slot(i + 1))
                         self._measured = True
@@ -376,11 +391,12 @@ class _Denoiser:
         run = self._middle_run() if (self.stack and torch.device(device).type == "cuda") else None
         if run is not None and len(run) >= self.STACK_MIN_LAYERS and self.wino[run[0]].s16.packed.is_cuda:
             self._stack_for(run, device)
-            if self.stack_kernel == "w16" and self.tag == "ffdnet" and self.head_w16 is not None and self.tail_w16 is not None:
-                self._stack_for(run, device, w16=True)
-            if self.tag == "denoiser" and n_img is not None and self.plain_head_w is not None and self.plain_tail_w16 is not None:
-                self.plain_sliced = True
-                if self.stack_kernel == "w16" and self.conv64 != "s16":
+            e = self.edges
+            # the sliced f-call needs both edge layers in the stack's layout; a plain network takes it once prepare() knows the batch
+            if e.head_w16 is not None and e.tail_w16 is not None and (e.ffdnet or n_img is not None):
+                if not e.ffdnet:
+                    self.plain_sliced = True
+                if self.stack_kernel == "w16" and (e.ffdnet or self.conv64 != "s16"):
                     self._stack_for(run, device, w16=True)
         if self.tag == "ffdnet":
             t = self.sigma_table
@@ -419,136 +435,84 @@ class _Denoiser:
         a grouped reconstruction switches to its other half (DEQSCIEngine._reconstruct_grouped) - and returns (output, is_noise)."""
         bsz, B, H, W = z1.shape
         path = self._route(bsz * B, H, W, x.device, self._policy, cal)
-        if self.tag == "ffdnet":
-            sg = self.sigma_table[call:call + 1]
+        if self.tag in ("ffdnet", "denoiser"):
+            sg = self.sigma_table[call:call + 1] if self.tag == "ffdnet" else None      # (a plain network takes no sigma)
             if path == "module":
-                out = self.net(x, sg.expand(bsz * B))
-            elif path in ("w16 stack launch", "s16 stack launch"):
-                out = yield from self._ffdnet_slices(x, sg, path)
-                self.last_path = path
-            elif path == "w16 per layer":
-                # behind a stack time-out: the same kernel, the same ranges, one launch per layer - the stack launch's bits
-                out = self._w16_per_layer(_hip.ffdnet_head_p32(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1)), self.tail_w16)
-                self.last_path = "w16 per layer (behind a stack time-out)"
-            else:
-                self.last_path = "per layer"
-                out = self._ffdnet_per_layer(x, sg, cal, path == "sp16 per layer")
-            return out.reshape(bsz, B, H, W), True
-        if self.tag == "denoiser":
-            if path == "module":
-                out = self.net(x)
+                out = self.net(x) if sg is None else self.net(x, sg.expand(bsz * B))
             elif path == "layers":
                 self.last_path = "per layer"
                 out = self._run_stack(x)
             elif path in ("w16 stack launch", "s16 stack launch"):
-                out = yield from self._plain_slices(x, path)
+                out = yield from self._sliced(x, sg, path)
                 self.last_path = path
             elif path == "w16 per layer":
                 # (behind a stack time-out: the stack launch's kernel and ranges, one launch per layer - its bits)
                 self.last_path = "w16 per layer (behind a stack time-out)" if self.per_layer_w16 else path
-                out = self._w16_per_layer(_hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], p32=True, out_rng=self._slot(1)),
-                                          self.plain_tail_w16)
+                h = self.edges.head(x, sg, _hip.P32, in_rng=self._slot(0), out_rng=self._slot(1))
+                for i in range(1, len(self.fast) - 1):
+                    h = _hip.conv3x3_c64_wino16(h, self.wino[i].w16, self.fast[i][1], self.fast[i][2], out_rng=self._slot(i + 1))
+                out = self.edges.tail(h)
             else:
                 self.last_path = "per layer"
-                out = self._plain_per_layer(x, cal, path == "sp16 per layer")
+                out = self._per_layer(x, sg, cal, path == "sp16 per layer")
             return out.reshape(bsz, B, H, W), True
         if self.tag == "conv2d":
             return self.net(x).reshape(bsz, B, H, W), False
         x5 = z1.view(bsz, 1, B, H, W)
         return self.net(x5).reshape(bsz, B, H, W), self.tag == "3d_denoiser"
 
-    def _ffdnet_slices(self, x, sg, path):
-        """(generator) FFDNet slice by slice on the kernels of the path's stack: first layer -> the run of 64->64 layers as one stack launch
-        -> last layer, each handing its output to the next through the Infinity Cache (a slice's activation is at most 128 MiB)."""
-        n, H, W = x.shape[0], x.shape[2] // 2, x.shape[3] // 2
-        run = self._middle_run()
-        st, per = self._slicing(path, run, n, H, W, x.device)
+    def _sliced(self, x, sg, path):
+        """(generator) The f-call slice by slice on the kernels of the path's stack: the first layer writes the slice's input buffer in that
+        stack's layout (p32 / sp16) with the range slots of its images, the run of 64->64 layers is one stack launch, the last layer reads
+        the buffer the run wrote - each handing its output to the next through the Infinity Cache (a slice's activation is at most
+        128 MiB).  The kernels, weights and ranges of the per-layer paths: their bits."""
+        e = self.edges
+        n, H, W = x.shape[0], x.shape[2] // e.div, x.shape[3] // e.div
+        st, per = self._slicing(path, n, H, W, x.device)
         bufs, hbuf = st.state(min(per, n), H, W), st.head_buffer(min(per, n), H, W)
-        rows = None if self.ranges is None else self.ranges[run[0]:run[-1] + 2]
+        rows = None if self.ranges is None else self.ranges[1:len(self.fast)]     # (the run's slots: its input's first)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         for a in range(0, n, per):
             m = min(per, n - a)
             hin = hbuf if m == hbuf.n else st.ACT(hbuf.t[:m], m, H, W)
-            in_rng = None if self.ranges is None else self._slot(0)[a:a + m]
-            out_rng = None if self.ranges is None else self._slot(1)[a:a + m]
-            hs = st.head(x[a:a + m], self.head_w16, sg, out=hin, in_rng=in_rng, out_rng=out_rng)
+            in_rng, out_rng = (None, None) if self.ranges is None else (self._slot(0)[a:a + m], self._slot(1)[a:a + m])
+            hs = e.head(x[a:a + m], sg, st.ACT, out=hin, in_rng=in_rng, out_rng=out_rng)
             if self.gate is not None:
                 self.gate.acquire()
             ys = st.launch(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
             if self.gate is not None:
                 self.gate.release()
                 yield "stack"
-            st.tail(ys, self.tail_w16, out=out[a:a + m])
+            e.tail(ys, out=out[a:a + m])
         self.stack_launches += 1
         return out
 
-    def _plain_slices(self, x, path):
-        """(generator) _ffdnet_slices for a plain network (DnCNN-17) at full resolution: the 1->64 layer writes the slice's input buffer of
-        the path's stack in that stack's layout (p32 / sp16) with the range slots of its images, the run of 64->64 layers is one stack
-        launch, the 64->1 layer reads the buffer the run wrote.  The kernels, weights and ranges of the per-layer paths: their bits."""
-        n, H, W = x.shape[0], x.shape[2], x.shape[3]
-        run = self._middle_run()
-        st, per = self._slicing(path, run, n, H, W, x.device)
-        w16 = path == "w16 stack launch"
-        bufs, hbuf = st.state(min(per, n), H, W), st.head_buffer(min(per, n), H, W)
-        rows = None if self.ranges is None else self.ranges[run[0]:run[-1] + 2]
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        for a in range(0, n, per):
-            m = min(per, n - a)
-            hin = hbuf if m == hbuf.n else st.ACT(hbuf.t[:m], m, H, W)
-            out_rng = None if self.ranges is None else self._slot(1)[a:a + m]
-            hs = _hip.conv3x3_c1_to_64(x[a:a + m], self.plain_head_w, relu=self.fast[0][2], out=hin, p32=w16, sp16=not w16, out_rng=out_rng)
-            if self.gate is not None:
-                self.gate.acquire()
-            ys = st.launch(hs, st, rows, per_launch=m, rng_offset=a, out_bufs=bufs, check=False)
-            if self.gate is not None:
-                self.gate.release()
-                yield "stack"
-            st.tail(ys, self.plain_tail_w16, out=out[a:a + m])
-        self.stack_launches += 1
-        return out
-
-    def _w16_per_layer(self, h, tail_w16):
-        """From the first layer's P32 output h: the 64->64 layers as one launch per layer of the Winograd split-fp16 kernel, the last layer."""
-        for i in range(1, len(self.fast) - 1):
-            h = _hip.conv3x3_c64_wino16(h, self.wino[i].w16, self.fast[i][1], self.fast[i][2], out_rng=self._slot(i + 1))
-        return _hip.ffdnet_tail_p32(h, tail_w16)
-
-    def _ffdnet_per_layer(self, x, sg, cal, sp):
-        """FFDNet layer by layer.  sp: the first layer writes sp16 and the last reads it (a calibrating call measures their ranges first)."""
-        n, _, H, W = x.shape
-        if self.head_w is not None and x.is_cuda:
-            if sp:
-                if cal:                                # max |image| (the head adds sigma itself), then max |its own output|
-                    self._measured = True
+    def _per_layer(self, x, sg, cal, sp):
+        """The f-call layer by layer.  sp: the first layer writes sp16 and the last reads it (a calibrating call measures their ranges first)."""
+        e = self.edges
+        first = e.head_w is not None and x.is_cuda
+        if first and sp:
+            if cal:                                    # FFDNet: max |image| (the head adds sigma itself); then max |the head's own output|
+                self._measured = True
+                if e.ffdnet:
                     _hip.absmax(x, self._slot(0))
-                    _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_exp=0, track=self._slot(1))
-                h = _hip.ffdnet_head_split16(x, self.head_w16, sg, in_rng=self._slot(0), out_rng=self._slot(1))
-            else:
-                h = _hip.ffdnet_head(x, self.head_w, sg)
-            first_done = True
-        else:
+                e.head(x, sg, _hip.Sp16, in_rng=self._slot(0), out_exp=0, track=self._slot(1))
+            h = e.head(x, sg, _hip.Sp16, in_rng=self._slot(0), out_rng=self._slot(1))
+        elif first:
+            h = e.head(x, sg)
+        elif e.ffdnet:                                 # no HIP first layer: FFDNet's concatenate in torch; a plain network's stays on _run_stack
+            n, _, H, W = x.shape
             h = torch.cat((sg.expand(n).view(-1, 1, 1, 1).expand(n, 1, H // 2, W // 2), F.pixel_unshuffle(x, 2)), 1)
-            first_done = False
-        if self.tail_w is not None and h.is_cuda:
-            defer = self.fused_epilogue and self.fast[-2][1] is not None and self.fast[-2][2]
-            raw = self._run_stack(h, skip_last=True, skip_first=first_done, defer_last_epilogue=defer, native_out=sp)
+        else:
+            h = x
+        if e.tail_w is not None and h.is_cuda:
+            # FFDNet's fp32 tail takes the bias + ReLU of the layer in front of it; a plain network does not defer them
+            defer = e.ffdnet and self.fused_epilogue and self.fast[-2][1] is not None and self.fast[-2][2]
+            raw = self._run_stack(h, skip_last=True, skip_first=first, defer_last_epilogue=defer, native_out=sp)
             raw, b = raw if defer else (raw, None)
-            return _hip.tail_split16(raw, self.tail_w16) if isinstance(raw, _hip.Sp16) else _hip.ffdnet_tail(raw, self.tail_w, in_bias=b)
-        return F.pixel_shuffle(self._run_stack(h, skip_first=first_done), 2)
-
-    def _plain_per_layer(self, x, cal, sp):
-        """SimpleCNN / DnCNN with HIP edge layers, layer by layer.  sp: as for _ffdnet_per_layer."""
-        first = self.plain_head_w is not None
-        if sp and cal:
-            self._measured = True
-            _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=True, out_exp=0, track=self._slot(1))
-        h = _hip.conv3x3_c1_to_64(x, self.plain_head_w, relu=self.fast[0][2], sp16=sp, out_rng=self._slot(1) if sp else None) if first else x
-        if self.plain_tail_w is not None:
-            h = self._run_stack(h, skip_first=first, skip_last=True, native_out=sp)
-            return (_hip.tail_split16(h, self.plain_tail_w16) if isinstance(h, _hip.Sp16) else
-                    _hip.conv3x3_c64_to_1(h.contiguous(memory_format=torch.channels_last), self.plain_tail_w))
-        return self._run_stack(h, skip_first=first)
+            return e.tail(raw, in_bias=b)
+        h = self._run_stack(h, skip_first=first)       # (no HIP last layer: it runs with the others, FFDNet's pixel shuffle in torch)
+        return F.pixel_shuffle(h, 2) if e.ffdnet else h
 
 
 class _StackTimeout(Exception):

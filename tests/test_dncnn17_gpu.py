@@ -1,5 +1,5 @@
 """DnCNN-17 on the device: the 15 middle layers as ONE conv_w16 stack launch per slice between the HIP 1->64 and 64->1 layers
-(engine._Denoiser._plain_slices), against the same layers launched one by one, a float64 stack, and the reference's own runs
+(engine._Denoiser._sliced), against the same layers launched one by one, a float64 stack, and the reference's own runs
 (tests/golden/dncnn17.npz, make_dncnn_golden.py: traffic measurement 0, the 64 x 64 x 8 crop, 10 and K iterations).
 
 Shapes this small take Winograd F(2x2,3x3) under the default policy (less than a block tile per CU: _hip.conv64_kernel_for), so the

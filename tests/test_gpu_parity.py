@@ -1318,7 +1318,7 @@ def _denoiser_error_vs_float64(net, z1, call=3):
     # (the measuring call runs the direct kernel layer by layer; FFDNet's later calls take the Winograd stack launch - the hook here does
     # not -: the same call to within either's own distance from the float64 network, bit for bit where the run keeps its per-layer launches)
     # (SimpleCNN: the measuring call on the direct kernel, later calls on Winograd launches; a plugin stack keeps the direct kernel)
-    assert set(seen) == ({"s16", "w16"} if den.tag == "denoiser" and den.plain_head_w is not None else {"s16"})
+    assert set(seen) == ({"s16", "w16"} if den.tag == "denoiser" and den.head_w is not None else {"s16"})
     assert torch.equal(got, got2) if "w16" not in seen and den.tag != "ffdnet" else (rel_l2(got.cpu().numpy(), got2.cpu().numpy()) < 2.0 * e(got) and e(got2) < 1.25 * e(got))
     err = {"default": max(e(got), e(got2))}
     den.conv64 = den._policy = "f22"
@@ -1683,7 +1683,7 @@ def test_realsn_simplecnn_vs_reference():
     avg, images = test_solver_sci(deq, test_dataloader=SCITestDataset(orc.DATA_DIR), save_img_path="", verbose=False,
                                   save_image=False, records=records)
     den = deq._engine_for().den
-    assert den.fast is not None and den.plain_head_w is not None and den.plain_tail_w is not None
+    assert den.fast is not None and den.head_w is not None and den.tail_w is not None
     assert [w is not None for w in den.wino] == [False, True, True, False]
     assert [r["id"] for r in records] == [m["id"] for m in meta["measurements"]]
     for r, m in zip(records, meta["measurements"]):

@@ -359,7 +359,7 @@ def test_denoiser_route_table(monkeypatch):
     layers' resolution (half the image's for FFDNet), then the tag, which edge weights and stacks exist, whether the call calibrates, and
     the knobs.  stack_slice asks the same question under the engine's policy, not the call's."""
     from types import SimpleNamespace
-    from deqsci_amd.engine import _Denoiser
+    from deqsci_amd.engine import _Denoiser, _Edges
     asked = []
 
     def route(tag="ffdnet", kind="s16", cal=False, device="cuda", edges=("head", "tail"), stacks=("s16", "w16"), packed=True, **knobs):
@@ -367,8 +367,9 @@ def test_denoiser_route_table(monkeypatch):
         den = object.__new__(_Denoiser)
         den.tag, den.fast = tag, [None] * n_layers
         den.wino = [None] + [object() if packed else None] * (n_layers - 2) + [None]
-        den.head_w = den.plain_head_w = object() if "head" in edges else None
-        den.tail_w = den.plain_tail_w = object() if "tail" in edges else None
+        den.edges = _Edges(2 if tag == "ffdnet" else 1)
+        den.edges.head_w = object() if "head" in edges else None
+        den.edges.tail_w = object() if "tail" in edges else None
         den._stacks = {1: SimpleNamespace(n_layers=n_layers - 2)} if "s16" in stacks else {}
         den._wstacks = {1: SimpleNamespace(n_layers=n_layers - 2)} if "w16" in stacks else {}
         den.ranges = object()
