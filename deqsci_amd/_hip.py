@@ -14,6 +14,7 @@ LAYOUT_HWB = 0   # (bsz,H,W,B)  reference API layout
 LAYOUT_BHW = 1   # (bsz,B,H,W)  planar / denoiser layout
 MAX_M = 8
 PART_STRIDE = MAX_M + 1
+WGRAD_CHAIN = 4096   # DEQSCI_WGRAD_CHAIN: the most products a weight-gradient entry sums in fp32 before the float64 stage
 
 # DEQSCI_HIP_LIB: another build of the SAME library (tools only: the -DDEQSCI_DIAG variant of `make diag`, a stamp build of tools/lib_variants.sh)
 _LIB_PATH = os.environ.get("DEQSCI_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libdeqsci_hip.so")
@@ -80,6 +81,8 @@ SIGNATURES = {
     "deqsci_broyden_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _int, _ptr],
     "deqsci_epsilon2_norms_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr],
     "deqsci_epsilon2_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr],
+    "deqsci_wgrad3x3_c64_c64_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_wgrad3x3_c1_c64_f32": [_ptr, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -87,7 +90,8 @@ SIGNATURES = {
 OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunks",
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
-                 "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk")
+                 "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
+                 "deqsci_wgrad_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -137,6 +141,8 @@ def load():
     lib.deqsci_epsilon2_workspace_bytes.argtypes = [_i64, _i64]
     lib.deqsci_epsilon2_chunk.restype = _i64
     lib.deqsci_epsilon2_chunk.argtypes = []
+    lib.deqsci_wgrad_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_wgrad_workspace_bytes.argtypes = [_i64, _i64, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -506,6 +512,60 @@ def relu_mask_pack(a, out=None):
     with _dev(a):
         _check(load().deqsci_relu_mask_pack_f32(a.data_ptr(), o.data_ptr(), n * H * W, _stream()), "relu_mask_pack")
     return o
+
+
+def wgrad_workspace(n, H, W, device):
+    """The scratch buffer of wgrad_c64_c64 / wgrad_c1_c64 for (n,H,W) images (deqsci_wgrad_workspace_bytes; serves both, uninitialised)."""
+    nbytes = load().deqsci_wgrad_workspace_bytes(n, H, W)
+    if nbytes == 0:
+        raise DeqsciHipError(f"wgrad_workspace: sizes {(n, H, W)} are not served")
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def _wgrad_ws(workspace, n, H, W, ref, what):
+    ws = workspace if workspace is not None else wgrad_workspace(n, H, W, ref.device)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.device != ref.device or not ws.is_contiguous()
+            or ws.numel() * ws.element_size() < load().deqsci_wgrad_workspace_bytes(n, H, W)):
+        raise DeqsciHipError(f"{what}: workspace must be a contiguous tensor of wgrad_workspace{(n, H, W)}'s size on the inputs' device")
+    return ws
+
+
+def _act64(a, what, name):
+    if (not isinstance(a, torch.Tensor) or a.dim() != 4 or a.shape[1] != 64 or not a.is_cuda or a.dtype != torch.float32
+            or not a.is_contiguous(memory_format=torch.channels_last)):
+        raise DeqsciHipError(f"{what}: {name} must be an fp32 channels_last (n,64,H,W) GPU activation")
+    return a
+
+
+def wgrad_c64_c64(x, g, workspace=None):
+    """The weight gradient of a 64 -> 64 conv3x3 (pad 1): dw[co,ci,ky,kx] = sum g[:,co,h,w] x[:,ci,h+ky-1,w+kx-1], x the layer's input and
+    g the gradient behind it, both fp32 channels_last (n,64,H,W) -> (64,64,3,3) (csrc/wgrad.hip W0; deterministic)."""
+    _act64(x, "wgrad_c64_c64", "x"), _act64(g, "wgrad_c64_c64", "g")
+    if x.shape != g.shape or x.device != g.device:
+        raise DeqsciHipError(f"wgrad_c64_c64: x {tuple(x.shape)} and g {tuple(g.shape)} must have one shape and device")
+    n, _, H, W = x.shape
+    ws = _wgrad_ws(workspace, n, H, W, x, "wgrad_c64_c64")
+    dw = torch.empty((64, 64, 3, 3), device=x.device, dtype=torch.float32)
+    with _dev(x):
+        _check(load().deqsci_wgrad3x3_c64_c64_f32(x.data_ptr(), g.data_ptr(), dw.data_ptr(), n, H, W, ws.data_ptr(), _stream()), "wgrad_c64_c64")
+    return dw
+
+
+def wgrad_c1_c64(s, t, flip, workspace=None):
+    """The weight gradient of an edge layer from the planar (n,1,H,W) image s and the channels_last (n,64,H,W) activation t (csrc/wgrad.hip W1):
+    flip = 0 -> (64,1,3,3), dw[c,0,ky,kx] = sum t[:,c,h,w] s[:,0,h+ky-1,w+kx-1] (first layer: s its input, t the gradient behind it);
+    flip = 1 -> (1,64,3,3), dw[0,c,ky,kx] = sum s[:,0,h,w] t[:,c,h+ky-1,w+kx-1] (last layer: s the gradient behind it, t its input)."""
+    _act64(t, "wgrad_c1_c64", "t")
+    n, _, H, W = t.shape
+    if tuple(s.shape) != (n, 1, H, W) or s.device != t.device:
+        raise DeqsciHipError(f"wgrad_c1_c64: s must be the (n,1,H,W) = {(n, 1, H, W)} image on t's device, got {tuple(s.shape)}")
+    if flip not in (0, 1):
+        raise DeqsciHipError(f"wgrad_c1_c64: flip must be 0 or 1, got {flip!r}")
+    ws = _wgrad_ws(workspace, n, H, W, t, "wgrad_c1_c64")
+    dw = torch.empty((1, 64, 3, 3) if flip else (64, 1, 3, 3), device=t.device, dtype=torch.float32)
+    with _dev(t):
+        _check(load().deqsci_wgrad3x3_c1_c64_f32(_p(s, "s"), t.data_ptr(), dw.data_ptr(), int(flip), n, H, W, ws.data_ptr(), _stream()), "wgrad_c1_c64")
+    return dw
 
 
 def _mask_ptr(mask, n, H, W, what):

@@ -8,6 +8,9 @@ The operators are linear in the image / measurement, so every backward is again 
     z1 = z + At((y - A z)/Phi_sum)     grad_z = g - At(A(g)/Phi_sum)  (= the same GAP kernel with y = 0: I - Phi^T D Phi is symmetric)
                                        grad_y = A(g) / Phi_sum
 
+    noise = D(x; W_0 .. W_{k-1})       grad_W_i = csrc/wgrad.hip on the kept activations and the masked gradients, grad_x = J_D(x)^T g
+                                       (deqsci_amd.vjp.DenoiserParamGrads; DEQFixedPoint.parameter_backward = "device")
+
 Masks (Phi, Phi_sum) are data: no gradient is produced for them (the reference never asks for one).
 (bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path.
 """
@@ -61,6 +64,35 @@ class _GapUpdate(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             gy = _hip.sci_forward(g, Phi, LAYOUT_HWB) / Phi_sum
         return gz, gy, None, None
+
+
+class _DenoiserNoise(torch.autograd.Function):
+    """noise = net(x) for a net vjp.param_eligibility accepts, forward and backward on the HIP kernels.  The conv weights are passed as
+    inputs so that autograd routes their gradients; the forward reads them from `net` (the same tensors)."""
+
+    @staticmethod
+    def forward(ctx, net, x, *weights):
+        from . import vjp
+        ctx.pg = vjp.DenoiserParamGrads(net, x)
+        return ctx.pg.noise
+
+    @staticmethod
+    def backward(ctx, gv):
+        pg, ctx.pg = ctx.pg, None
+        if pg is None:
+            raise RuntimeError("denoiser_noise: backward ran already (the kept activations are freed after the first)")
+        try:
+            dws = pg.grads(gv, need=ctx.needs_input_grad[2:])
+            gx = pg.vjp(gv) if ctx.needs_input_grad[1] else None
+        finally:
+            pg.release()
+        return (None, gx) + tuple(dws)
+
+
+def denoiser_noise(net, x):
+    """net(x) with the weight gradients (and the input gradient, where x requires one) formed on the device."""
+    from . import vjp
+    return _DenoiserNoise.apply(net, x, *vjp.conv_weights(net))
 
 
 def taping(*tensors):

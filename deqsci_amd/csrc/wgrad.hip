@@ -1,0 +1,297 @@
+// The denoiser's weight gradients (the taped call z = f(z*) of the training forward: autograd forms (df/dtheta)^T g from it, and for a
+// bias-free conv + ReLU stack that is one weight gradient per 3x3 convolution, from the layer's input and the masked gradient behind it).
+//
+//   W0 wgrad_c64_kernel   dw[co][ci][ky][kx] = sum_p g[p,co] x[p + (ky-1, kx-1), ci] for a 64 -> 64 layer, x and g fp32 channels_last.
+//                         A GEMM with the pixels as K on the exact-fp32 matrix instruction v_mfma_f32_32x32x2_f32: A = g^T (co x pixel),
+//                         B = x shifted by the tap (pixel x ci), two pixels per instruction.  Four waves, wave w owns the 32 x 32 quadrant
+//                         (co half w >> 1, ci half w & 1) of all nine taps: 9 x 16 accumulator registers.  A tile is a run of TW = 32
+//                         pixels of one image row: its g and the three haloed x rows (zero outside the image) are staged in LDS, the next
+//                         tile's are in flight in registers meanwhile.  A tap outside the image is never multiplied (a 0 x NaN would be a
+//                         NaN the sum does not contain): a tap row or column outside the image and a pixel beyond the row's end get a
+//                         zero on BOTH operands.
+//   W1 wgrad_c1_kernel    the two edge layers: dw[c][ky][kx] = sum_p t[p,c] s[p + (ky-1, kx-1)], s a planar scalar image, t channels_last.
+//                         Lane = channel, a wave walks 8 pixels of a tile, the nine s taps come from LDS; nine accumulators per lane.
+//                         The last layer's form sum_p s[p] t[p + d, c] is the same sum with the taps reversed (q = p + d), so the
+//                         second launch writes tap 8 - tap for flip = 1.
+//   wgrad_sum_kernel      the second launch of both: per entry, the workgroups' float64 partials in ascending workgroup order, rounded once.
+//
+// Every workgroup owns a fixed run of consecutive tiles, accumulates in fp32 and adds its accumulators to its float64 partial in the
+// workspace (first flush: a store, so the workspace needs no initialisation) at the latest every DEQSCI_WGRAD_CHAIN pixels and at the end
+// of its run.  No atomics, no workgroup waits for another: bit-for-bit deterministic.
+#include "common.hpp"
+
+namespace deqsci {
+namespace wgrad {
+
+constexpr int TW = 32;                                   // pixels of a tile
+constexpr int XW = TW + 2;                               // with the halo columns
+constexpr int CHAIN = DEQSCI_WGRAD_CHAIN;
+constexpr int FLUSH_TILES = CHAIN / TW;                  // a partial is flushed after this many tiles
+constexpr int W0_MAX_WG = 256, W1_MAX_WG = 512;          // fixed, not the device's: the workspace query has no device
+constexpr int W0_ENTRIES = 9 * 64 * 64, W1_ENTRIES = 9 * 64;
+constexpr int64_t MAX_SIDE = 1 << 20;
+static_assert(CHAIN % TW == 0 && FLUSH_TILES >= 1, "a flush falls on a tile boundary");
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+struct Split {
+    int64_t tiles, per_wg, wgs;
+};
+inline bool sizes_ok(int64_t n, int64_t H, int64_t W) { return n >= 1 && H >= 1 && W >= 1; }
+inline bool supported(int64_t n, int64_t H, int64_t W) {
+    return n <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE && (double)n * (double)H * (double)ceil_div(W, TW) <= (double)INT32_MAX;
+}
+inline Split split(int64_t n, int64_t H, int64_t W, int max_wg) {
+    Split s;
+    s.tiles = n * H * ceil_div(W, TW);
+    s.per_wg = ceil_div(s.tiles, max_wg);
+    s.wgs = ceil_div(s.tiles, s.per_wg);                 // (no idle workgroup: every one has at least one tile)
+    return s;
+}
+
+struct Tile {
+    int64_t row;                                         // img * H + h
+    int h, w0;
+};
+__device__ __forceinline__ Tile tile_at(int64_t t, int H, int tilesW) {
+    Tile r;
+    r.row = t / tilesW;
+    r.w0 = (int)(t - r.row * tilesW) * TW;
+    r.h = (int)(r.row % H);
+    return r;
+}
+
+__global__ __launch_bounds__(TB) void wgrad_c64_kernel(const float* __restrict__ x, const float* __restrict__ g, double* __restrict__ part,
+                                                       int H, int W, int tilesW, int64_t tiles, int64_t per_wg) {
+    __shared__ float gL[TW * 64];
+    __shared__ float xL[3 * XW * 64];
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int cob = (wave >> 1) * 32, cib = (wave & 1) * 32, col = lane & 31, half = lane >> 5;
+    const int64_t t0 = (int64_t)blockIdx.x * per_wg, t1 = t0 + per_wg < tiles ? t0 + per_wg : tiles;
+
+    v16f acc[9];
+    float4 rg[2], rx[7];
+    auto fetch = [&](const Tile& tl) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int idx = tid + i * TB, px = idx >> 4, c4 = idx & 15, w = tl.w0 + px;
+            rg[i] = w < W ? ld4(g + ((tl.row * W + w) * 64 + c4 * 4)) : f4(0.0f);
+        }
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const int idx = tid + i * TB;
+            rx[i] = f4(0.0f);
+            if (idx < 3 * XW * 16) {
+                const int row = idx / (XW * 16), rem = idx - row * (XW * 16), c = rem >> 4, c4 = rem & 15;
+                const int hh = tl.h + row - 1, ww = tl.w0 + c - 1;
+                if (hh >= 0 && hh < H && ww >= 0 && ww < W) rx[i] = ld4(x + (((tl.row + row - 1) * W + ww) * 64 + c4 * 4));
+            }
+        }
+    };
+    auto stage = [&]() {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) st4(gL + (tid + i * TB) * 4, rg[i]);
+#pragma unroll
+        for (int i = 0; i < 7; ++i)
+            if (tid + i * TB < 3 * XW * 16) st4(xL + (tid + i * TB) * 4, rx[i]);
+    };
+    double* const mine = part + (int64_t)blockIdx.x * W0_ENTRIES;
+    auto flush = [&](bool first) {
+        double* base = mine + ((cob + 4 * half) * 64 + cib + col);
+        asm volatile("" : "+v"(base));                                      // (the 144 addresses are formed here, not kept across the tile loop)
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                double* p = base + ((tap * 64 + (r & 3) + 8 * (r >> 2)) * 64);
+                *p = first ? (double)acc[tap][r] : *p + (double)acc[tap][r];
+            }
+            asm volatile("" ::: "memory");                                  // one tap's 16 doubles in flight, not all 144
+        }
+    };
+
+    Tile cur = tile_at(t0, H, tilesW);
+    fetch(cur);
+    const float* const gb = gL + cob + col;
+    const float* const xb = xL + cib + col;
+    for (int64_t c0 = t0; c0 < t1; c0 += FLUSH_TILES) {                     // one partial per FLUSH_TILES tiles: the accumulators live in this loop only
+        const int64_t c1 = c0 + FLUSH_TILES < t1 ? c0 + FLUSH_TILES : t1;
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+        for (int64_t t = c0; t < c1; ++t) {
+            stage();
+            __syncthreads();
+            const Tile now = cur;
+            if (t + 1 < t1) {
+                cur = tile_at(t + 1, H, tilesW);
+                fetch(cur);
+            }
+            const bool rowok[3] = {now.h > 0, true, now.h < H - 1};
+#pragma unroll 4
+            for (int pp = 0; pp < TW / 2; ++pp) {
+                const int px = 2 * pp + half, w = now.w0 + px;
+                // every operand is read unconditionally; what must not be multiplied is zero on both sides by construction: g is staged as
+                // zero beyond the row's end and x as zero outside the image, a tap row / column outside the image zeroes a, and the one real
+                // x value a pixel beyond the row's end could meet (w == W, kx == 0: x[W-1]) is read one column further, where x is zero
+                const float a = gb[px * 64];
+                const float ax[3] = {w == 0 ? 0.0f : a, a, w == W - 1 ? 0.0f : a};
+                const int xc[3] = {px + (w == W ? 1 : 0), px + 1, px + 2};
+                float b[9];
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx) b[ky * 3 + kx] = xb[(ky * XW + xc[kx]) * 64];
+#pragma unroll
+                for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                    for (int kx = 0; kx < 3; ++kx)
+                        acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(rowok[ky] ? ax[kx] : 0.0f, b[ky * 3 + kx], acc[ky * 3 + kx], 0, 0, 0);
+            }
+            __syncthreads();
+        }
+        flush(c0 == t0);
+    }
+}
+
+__global__ __launch_bounds__(TB) void wgrad_c1_kernel(const float* __restrict__ s, const float* __restrict__ t, double* __restrict__ part,
+                                                      int H, int W, int tilesW, int64_t tiles, int64_t per_wg) {
+    __shared__ float sL[3 * XW];
+    __shared__ float red[(TB / WAVE) * 9 * 64];
+    constexpr int PX = TW / (TB / WAVE);                                    // pixels of a tile per wave
+    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int64_t t0 = (int64_t)blockIdx.x * per_wg, t1 = t0 + per_wg < tiles ? t0 + per_wg : tiles;
+    double* const mine = part + (int64_t)blockIdx.x * W1_ENTRIES;
+    float acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.0f;
+
+    auto flush = [&](bool first) {
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            red[(wave * 9 + tap) * 64 + lane] = acc[tap];
+            acc[tap] = 0.0f;
+        }
+        __syncthreads();
+        for (int e = tid; e < W1_ENTRIES; e += TB) {
+            double d = 0.0;
+            for (int wv = 0; wv < TB / WAVE; ++wv) d += (double)red[wv * W1_ENTRIES + e];
+            mine[e] = first ? d : mine[e] + d;
+        }
+        __syncthreads();
+    };
+
+    int since = 0;
+    bool first = true;
+    for (int64_t tt = t0; tt < t1; ++tt) {
+        const Tile tl = tile_at(tt, H, tilesW);
+        __syncthreads();
+        if (tid < 3 * XW) {
+            const int row = tid / XW, c = tid - row * XW, hh = tl.h + row - 1, ww = tl.w0 + c - 1;
+            sL[tid] = (hh >= 0 && hh < H && ww >= 0 && ww < W) ? s[(tl.row + row - 1) * W + ww] : 0.0f;
+        }
+        float tv[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const int w = tl.w0 + wave * PX + j;
+            tv[j] = w < W ? t[(tl.row * W + w) * 64 + lane] : 0.0f;
+        }
+        __syncthreads();
+        const bool rowok[3] = {tl.h > 0, true, tl.h < H - 1};
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const int px = wave * PX + j, w = tl.w0 + px;
+            if (w >= W) continue;                                           // (uniform in the wave)
+            const bool colok[3] = {w > 0, true, w < W - 1};
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx)
+                    if (rowok[ky] && colok[kx]) acc[ky * 3 + kx] = fmaf(tv[j], sL[ky * XW + px + kx], acc[ky * 3 + kx]);
+        }
+        if (++since == FLUSH_TILES) {
+            flush(first);
+            first = false;
+            since = 0;
+        }
+    }
+    if (since > 0) flush(first);
+}
+
+// entry e = tap * per_tap + r  ->  dw[r * 9 + (flip ? 8 - tap : tap)]
+__global__ __launch_bounds__(TB) void wgrad_sum_kernel(const double* __restrict__ part, float* __restrict__ dw, int entries, int per_tap,
+                                                       int wgs, int flip) {
+    const int e = (int)(blockIdx.x * TB + threadIdx.x);
+    if (e >= entries) return;
+    double sum = 0.0;
+#pragma unroll 16
+    for (int b = 0; b < wgs; ++b) sum += part[(int64_t)b * entries + e];
+    const int tap = e / per_tap, r = e - tap * per_tap;
+    dw[r * 9 + (flip ? 8 - tap : tap)] = (float)sum;
+}
+
+inline size_t workspace_bytes(int64_t n, int64_t H, int64_t W) {
+    const int64_t a = split(n, H, W, W0_MAX_WG).wgs * W0_ENTRIES, b = split(n, H, W, W1_MAX_WG).wgs * W1_ENTRIES;
+    return (size_t)(a > b ? a : b) * sizeof(double);
+}
+
+}  // namespace wgrad
+}  // namespace deqsci
+
+using namespace deqsci;
+
+extern "C" {
+
+size_t deqsci_wgrad_workspace_bytes(int64_t n, int64_t H, int64_t W) {
+    if (!wgrad::sizes_ok(n, H, W) || !wgrad::supported(n, H, W)) return 0;
+    return wgrad::workspace_bytes(n, H, W);
+}
+
+int deqsci_wgrad3x3_c64_c64_f32(const float* x, const float* g, float* dw, int64_t n, int64_t H, int64_t W, void* workspace,
+                                deqsci_stream_t stream) {
+    if (!x || !g || !dw || !workspace) return DEQSCI_ERR_NULL;
+    if (!wgrad::sizes_ok(n, H, W)) return DEQSCI_ERR_SHAPE;
+    if (!aligned16(x) || !aligned16(g) || misaligned(dw, 4) || misaligned(workspace, 8)) return DEQSCI_ERR_ALIGN;
+    if (!wgrad::supported(n, H, W)) return DEQSCI_ERR_UNSUPPORTED;
+    const int64_t act = n * H * W * 64 * (int64_t)sizeof(float), out = wgrad::W0_ENTRIES * (int64_t)sizeof(float);
+    const int64_t ws = (int64_t)wgrad::workspace_bytes(n, H, W);
+    if (overlaps(dw, out, x, act) || overlaps(dw, out, g, act) || overlaps(workspace, ws, x, act) || overlaps(workspace, ws, g, act) ||
+        overlaps(workspace, ws, dw, out))
+        return DEQSCI_ERR_UNSUPPORTED;
+    const wgrad::Split sp = wgrad::split(n, H, W, wgrad::W0_MAX_WG);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(wgrad::wgrad_c64_kernel, dim3((unsigned)sp.wgs), dim3(TB), 0, st, x, g, part, (int)H, (int)W,
+                       (int)ceil_div(W, wgrad::TW), sp.tiles, sp.per_wg);
+    int rc = launch_status();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(wgrad::wgrad_sum_kernel, dim3((unsigned)ceil_div(wgrad::W0_ENTRIES, TB)), dim3(TB), 0, st, part, dw,
+                       wgrad::W0_ENTRIES, 64 * 64, (int)sp.wgs, 0);
+    return launch_status();
+}
+
+int deqsci_wgrad3x3_c1_c64_f32(const float* s, const float* t, float* dw, int flip, int64_t n, int64_t H, int64_t W, void* workspace,
+                               deqsci_stream_t stream) {
+    if (!s || !t || !dw || !workspace) return DEQSCI_ERR_NULL;
+    if (!wgrad::sizes_ok(n, H, W)) return DEQSCI_ERR_SHAPE;
+    if (misaligned(s, 4) || misaligned(t, 4) || misaligned(dw, 4) || misaligned(workspace, 8)) return DEQSCI_ERR_ALIGN;
+    if ((flip != 0 && flip != 1) || !wgrad::supported(n, H, W)) return DEQSCI_ERR_UNSUPPORTED;
+    const int64_t img = n * H * W * (int64_t)sizeof(float), act = img * 64, out = wgrad::W1_ENTRIES * (int64_t)sizeof(float);
+    const int64_t ws = (int64_t)wgrad::workspace_bytes(n, H, W);
+    if (overlaps(dw, out, s, img) || overlaps(dw, out, t, act) || overlaps(workspace, ws, s, img) || overlaps(workspace, ws, t, act) ||
+        overlaps(workspace, ws, dw, out))
+        return DEQSCI_ERR_UNSUPPORTED;
+    const wgrad::Split sp = wgrad::split(n, H, W, wgrad::W1_MAX_WG);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(wgrad::wgrad_c1_kernel, dim3((unsigned)sp.wgs), dim3(TB), 0, st, s, t, part, (int)H, (int)W,
+                       (int)ceil_div(W, wgrad::TW), sp.tiles, sp.per_wg);
+    int rc = launch_status();
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(wgrad::wgrad_sum_kernel, dim3((unsigned)ceil_div(wgrad::W1_ENTRIES, TB)), dim3(TB), 0, st, part, dw,
+                       wgrad::W1_ENTRIES, 64, (int)sp.wgs, flip);
+    return launch_status();
+}
+
+}  // extern "C"

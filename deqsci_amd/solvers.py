@@ -84,6 +84,25 @@ class EquilibriumProxGradSCI(nn.Module):
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
+    def device_param_eligibility(self):
+        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility)."""
+        if not (self.A is A_torch_ and self.At is At_torch_):
+            return False, "custom A / At: the device call uses the HIP GAP projection"
+        return _vjp.param_eligibility(self.nonlinear_op)
+
+    def forward_param_device(self, z, y, Phi, Phi_sum):
+        """The taped call f(z) = z1 - D(z1) whose backward forms the denoiser's weight gradients on the HIP kernels: gap_update ->
+        autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called."""
+        ok, why = self.device_param_eligibility()
+        if not ok:
+            raise ValueError(f"forward_param_device: {why}")
+        bsz, w, h, c = z.shape
+        z1 = _ag.gap_update(z, y, Phi, Phi_sum)
+        zp = z1.permute(0, 3, 1, 2).contiguous()
+        self._taped = (zp.detach().view(bsz * c, 1, w, h), None)
+        noise = _ag.denoiser_noise(self.nonlinear_op, zp.view(bsz * c, 1, w, h))
+        return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
+
     def device_vjp_eligibility(self):
         """(ok, reason): whether device_vjp can serve this map (HIP GAP operators and a denoiser deqsci_amd.vjp.eligibility accepts)."""
         if not (self.A is A_torch_ and self.At is At_torch_):
@@ -267,6 +286,13 @@ class DEQFixedPoint(nn.Module):
         self.implicit_backward = "autograd"
         self.last_backward_path = None
         self.backward_fallback_reason = None
+        # how the taped call z = f(z*) forms the denoiser's weight gradients: "autograd" (the torch module on the tape: MIOpen backward) or
+        # "device" (EquilibriumProxGradSCI.forward_param_device: csrc/wgrad.hip, falling back to autograd where vjp.param_eligibility
+        # refuses).  last_parameter_path: the path of the last taped forward; parameter_fallback_reason: why not "device".  Independent of
+        # implicit_backward.
+        self.parameter_backward = "autograd"
+        self.last_parameter_path = None
+        self.parameter_fallback_reason = None
 
     def _engine_for(self):
         f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
@@ -309,6 +335,26 @@ class DEQFixedPoint(nn.Module):
             self.backward_fallback_reason = why
             return None
         return f.device_vjp(Phi, Phi_sum)
+
+    def _taped_call(self, z, x, Phi, Phi_sum):
+        """The taped call z = f(z*) (:268): on the device's weight-gradient path where parameter_backward asks for it and it is served."""
+        if self.parameter_backward not in ("autograd", "device"):
+            raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd' or 'device'")
+        self.parameter_fallback_reason = None
+        self.last_parameter_path = "autograd"
+        if self.parameter_backward == "device":
+            f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
+            if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
+                self.parameter_fallback_reason = "DataParallel over several devices (the taped call runs on replicas)"
+            elif not isinstance(f, EquilibriumProxGradSCI):
+                self.parameter_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
+            else:
+                ok, why = f.device_param_eligibility()
+                if ok:
+                    self.last_parameter_path = "device"
+                    return f.forward_param_device(z, x, Phi, Phi_sum)
+                self.parameter_fallback_reason = why
+        return self.f(z, x, Phi, Phi_sum)
 
     def jacobian_at(self, y, Phi, Phi_sum, z):
         """f's Jacobian at z - the reconstruction the last forward(y, ...) returned - as EquilibriumProxGradSCI.device_jacobian gives it
@@ -355,7 +401,7 @@ class DEQFixedPoint(nn.Module):
                                           "(pass train_flag=False or run under torch.no_grad())")
             with torch.no_grad():
                 z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
-            z = self.f(z, x, Phi, Phi_sum)                                     # re-engage the tape (:268)
+            z = self._taped_call(z, x, Phi, Phi_sum)                           # re-engage the tape (:268)
             z0 = z.clone().detach().requires_grad_()
             f0 = self.f(z0, x, Phi, Phi_sum)                                   # Jacobian-vector products come from this graph
             jmap = self._device_map(Phi, Phi_sum)

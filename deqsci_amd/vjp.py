@@ -21,6 +21,11 @@ The same masked kernels compute J_D(x) v (forward mode) when they are handed the
 (the diagnostics of deqsci_amd/jacobian.py) has both directions, and for FFDNet it differentiates THROUGH the input - the Jacobian of
 the map the iteration applies, sigma a constant of the linearisation - on csrc/jacobian.hip's masked first layer and the existing last
 layer's kernel.  DenoiserVJP and eligibility are the training hook's and do not change.
+
+The weight gradients (dD/dtheta)^T v of a bias-free conv + ReLU stack come from the same walk: the forward keeps each layer's input, the
+transposed masked layers carry v down, and layer i's dW_i is the correlation of its input with the masked gradient behind it
+(csrc/wgrad.hip: W0 for a 64 -> 64 layer, W1 for the two edge layers).  plan_param_grads is the host statement, DenoiserParamGrads the
+device's, param_eligibility says which nets qualify (DEQFixedPoint.parameter_backward = "device").
 """
 import torch
 import torch.nn.functional as F
@@ -137,6 +142,63 @@ def plan_jvp(layers, x, v, masks=None):
     return masked_jvp(layers, masks, v), masks
 
 
+def plan_param_grads(layers, x, v, masks=None):
+    """(dD/dtheta)^T v of the stack `layers` at x, one tensor per conv weight, in x's dtype - the host statement of what
+    DenoiserParamGrads.grads runs, next to plan_vjp: one masked forward keeps each layer's input, the layers are walked backwards with
+    masked_vjp's steps, and dW_i comes from layer i's input and the masked gradient behind it.  masks: those of another forward pass (the
+    device's, unpack_masks) in place of the decisions at x.  Returns ([dW_0 .. dW_{k-1}], masks)."""
+    inputs, used, h = [x], [], x
+    for i, (w, b, relu) in enumerate(layers[:-1]):
+        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
+        m = (masks[i] if masks is not None else h > 0) if relu else None
+        used.append(m)
+        if m is not None:
+            h = h * m
+        inputs.append(h)
+    grads, g = [None] * len(layers), v
+    for i in range(len(layers) - 1, -1, -1):
+        grads[i] = torch.nn.grad.conv2d_weight(inputs[i], layers[i][0].shape, g, padding=1)
+        if i > 0:
+            g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
+            if used[i - 1] is not None:
+                g = g * used[i - 1]
+    return grads, used
+
+
+def param_eligibility(net):
+    """(ok, reason): whether DenoiserParamGrads (and DEQFixedPoint.parameter_backward = "device") can form the weight gradients of `net`:
+    a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0,
+    no_bn=True) of any depth >= 2.  CPU-safe."""
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    if isinstance(net, FFDNet):
+        return False, "FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient"
+    if getattr(net, "tag", None) != "denoiser":
+        return False, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' plugins have device weight gradients"
+    if not isinstance(net, DnCNN):
+        return False, f"not a conv + ReLU stack: {type(net).__name__}"
+    mods = list(net.dncnn)
+    if any(isinstance(m, torch.nn.BatchNorm2d) for m in mods):
+        return False, "BatchNorm2d (its gamma / beta gradients, and the batch statistics in train mode, have no device kernel)"
+    if any(isinstance(m, RealSNConv2d) for m in mods):
+        return False, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
+    layers, why = conv_stack(mods)
+    if layers is None:
+        return False, why
+    shapes = [tuple(w.shape) for w, _, _ in layers]
+    if len(layers) < 2 or shapes[0] != (64, 1, 3, 3) or shapes[-1] != (1, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
+        return False, f"layer shapes {shapes}: the kernels cover 1 -> 64 -> ... -> 64 -> 1"
+    if not all(r for _, _, r in layers[:-1]) or layers[-1][2]:
+        return False, "ReLU pattern other than after every layer but the last"
+    if not all(isinstance(m.weight, torch.nn.Parameter) for m in mods if isinstance(m, torch.nn.Conv2d)):
+        return False, "a conv weight that is not an nn.Parameter"
+    return True, "bias-free conv + ReLU stack"
+
+
+def conv_weights(net):
+    """The conv weights of a net param_eligibility accepts, in layer order: the parameters DenoiserParamGrads.grads answers for."""
+    return [m.weight for m in net.dncnn if isinstance(m, torch.nn.Conv2d)]
+
+
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
 def ffdnet_plan(net):
     """Grayscale FFDNet in eval mode as [(weight, bias or None, relu)]: (64,5,3,3) first, 13 x (64,64,3,3) with the BatchNorm folded
@@ -213,9 +275,10 @@ class _MaskedStack:
     masked layers enqueued on the current stream with no host synchronisation, no pack made twice.  sigma: FFDNet's (1,) or (n,) fp32
     noise levels on x's device - its plan (ffdnet_plan), read through the 2x2 pixel-unshuffle: csrc/jacobian.hip's masked first layer
     serves the linearised head and the transposed tail, deqsci_ffdnet_tail_f32 without bias the linearised tail and the transposed head.
-    None: a 1 -> 64 -> ... -> 64 -> 1 stack (host_plan)."""
+    None: a 1 -> 64 -> ... -> 64 -> 1 stack (host_plan).  keep: hold every post-ReLU activation of the forward pass (.acts[i] = the input
+    of layer i + 1, (k-1) n 64 H W 4 bytes in all) - what the weight gradients are formed from (DenoiserParamGrads)."""
 
-    def __init__(self, layers, x, sigma=None):
+    def __init__(self, layers, x, sigma=None, keep=False):
         x = _hip.f32c(x.detach())
         f32 = lambda t: t.to(x.device, torch.float32)
         self.ffdnet = sigma is not None
@@ -238,9 +301,12 @@ class _MaskedStack:
             self.mid_f = [_hip.pack_winograd_weights(w) for w in mid]
             self.mid_t = [_hip.pack_winograd_weights(_transposed(w)) for w in mid]
             self.masks = [_hip.relu_mask_pack(h)]
+            self.acts = [h] if keep else None
             for u, (_, b, _) in zip(self.mid_f, layers[1:-1]):
                 h = _hip.conv3x3_c64_winograd(h, u, None if b is None else f32(b).contiguous(), True)
                 self.masks.append(_hip.relu_mask_pack(h))
+                if keep:
+                    self.acts.append(h)
 
     def jvp(self, v):
         first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
@@ -318,3 +384,63 @@ class DenoiserVJP:
         if tuple(v.shape) != self.shape:
             raise _hip.DeqsciHipError(f"DenoiserVJP: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
         return torch.zeros_like(v) if self.zero else self._stack.vjp(v)
+
+
+class DenoiserParamGrads:
+    """The denoiser's weight gradients on the device, for a (n,1,H,W) fp32 GPU image x: one forward pass on _MaskedStack's kernels
+    (1 -> 64 stencil, Winograd F(2x2,3x3), relu_mask_pack) that keeps the post-ReLU activations - (k-1) n 64 H W 4 bytes - and the masks;
+    .noise = D(x) from that pass (the 64 -> 1 stencil), .masks, .shape.  .grads(v) -> [dW_0 .. dW_{k-1}] = (dD/dtheta)^T v, one tensor per
+    conv weight (conv_weights(net)): the masked transposed layers of .vjp carry the gradient down, csrc/wgrad.hip's W1 serves the two edge
+    layers and W0 every 64 -> 64 layer.  need: one bool per weight - the walk stops below the lowest layer asked for, the others are None.
+    .vjp(v) is the input product J_D(x)^T v.  .release() drops the activations.  Everything is enqueued on the current stream with no host
+    synchronisation.  Raises ValueError with param_eligibility()'s reason."""
+
+    def __init__(self, net, x):
+        ok, why = param_eligibility(net)
+        if not ok:
+            raise ValueError(f"DenoiserParamGrads: {why}")
+        self.shape = _image(x, "DenoiserParamGrads")
+        self._x = _hip.f32c(x.detach())
+        self._stack = _MaskedStack(host_plan(net)[0], self._x, keep=True)
+        self.masks = self._stack.masks
+        self.noise = _hip.conv3x3_c64_to_1(self._stack.acts[-1], self._stack.tail_f)
+        n, _, H, W = self.shape
+        self._ws = _hip.wgrad_workspace(n, H, W, self._x.device)
+
+    def _v(self, v, what):
+        if tuple(v.shape) != self.shape:
+            raise _hip.DeqsciHipError(f"DenoiserParamGrads.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
+        return _hip.f32c(v)
+
+    def vjp(self, v):
+        return self._stack.vjp(self._v(v, "vjp"))
+
+    def grads(self, v, need=None):
+        st = self._stack
+        if st.acts is None:
+            raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
+        k = len(st.mid_t) + 2
+        need = [True] * k if need is None else [bool(b) for b in need]
+        if len(need) != k:
+            raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {k} conv weights")
+        v = self._v(v, "grads")
+        out = [None] * k
+        if not any(need):
+            return out
+        lowest = need.index(True)
+        if need[k - 1]:
+            out[k - 1] = _hip.wgrad_c1_c64(v, st.acts[-1], 1, self._ws)
+        if lowest == k - 1:
+            return out
+        g = _hip.conv3x3_c1_to_64_masked(v, st.tail_t, st.masks[-1])        # the gradient behind layer k-2, masked by its ReLU
+        for i in range(k - 2, 0, -1):
+            if need[i]:
+                out[i] = _hip.wgrad_c64_c64(st.acts[i - 1], g, self._ws)
+            if i == lowest:
+                return out
+            g = _hip.conv3x3_c64_winograd_masked(g, st.mid_t[i - 1], st.masks[i - 1])
+        out[0] = _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
+        return out
+
+    def release(self):
+        self._stack.acts = None

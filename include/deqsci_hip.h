@@ -489,6 +489,31 @@ int deqsci_epsilon2_norms_f32(const float* x, const float* f_x, const float* f_f
 int deqsci_epsilon2_update_f32(const float* x, const float* f_x, const float* f_fx, float* x_new, double* table, void* workspace,
                                int64_t bsz, int64_t N, float lam, deqsci_stream_t stream);
 
+/* ---- the denoiser's weight gradients (deqsci_amd/vjp.py: DenoiserParamGrads; not on the reconstruction path) ----
+ * The taped call z = f(z*) of the training forward hands autograd (df/dtheta)^T g; for a bias-free conv3x3 + ReLU stack that is one
+ * weight gradient per convolution (torch's cross-correlation, pad 1: a tap outside the image contributes nothing - it is not multiplied,
+ * so a NaN beside the border does not spread - and a row end or an image end never pairs with the next row or image).  All tensors fp32;
+ * 64-channel activations channels_last (n,H,W,64), scalar images planar (n,1,H,W).
+ * W0  dw[co][ci][ky][kx] = sum over img,h,w of g[img,h,w,co] * x[img,h+ky-1,w+kx-1,ci], dense (64,64,3,3): x the layer's input, g the
+ *     gradient behind it (both 16-byte aligned).  Exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32): every product is rounded once
+ *     and summed in an fp32 fma chain.
+ * W1  576 outputs, dense (64,3,3) (= (64,1,3,3) and (1,64,3,3)), s a scalar image, t a 64-channel activation (4-byte aligned):
+ *     flip = 0: dw[c][ky][kx] = sum_p t[p,c] * s[p+(ky-1,kx-1)]   (the first layer: s = the image, t = the gradient behind its ReLU)
+ *     flip = 1: dw[c][ky][kx] = sum_p s[p] * t[p+(ky-1,kx-1),c]   (the last layer: s = the gradient of the noise, t = the last activation)
+ * Both are two launches on `stream`: every workgroup of the first owns a fixed run of pixel tiles, accumulates in fp32 and adds its
+ * accumulators to its float64 partial in the workspace at the latest every DEQSCI_WGRAD_CHAIN pixels (so no entry sums more than
+ * DEQSCI_WGRAD_CHAIN products in fp32); the second sums the workgroups' partials per entry in float64, in ascending workgroup order, and
+ * rounds once.  No atomics, no workgroup waits for another: deterministic bit for bit.  workspace =
+ * deqsci_wgrad_workspace_bytes(n, H, W) bytes (0 for invalid sizes; serves both entries), 8-byte aligned, no initialisation needed.
+ * No allocation, no host synchronisation, graph-capturable.  NULL -> -1; n < 1 or a non-positive side -> -2; misaligned -> -3; dw or
+ * workspace overlapping an input or one another, flip other than 0 / 1, n or a side above 2^20 or n*H*ceil(W/32) >= 2^31 -> -4. */
+#define DEQSCI_WGRAD_CHAIN 4096
+size_t deqsci_wgrad_workspace_bytes(int64_t n, int64_t H, int64_t W);
+int deqsci_wgrad3x3_c64_c64_f32(const float* x, const float* g, float* dw, int64_t n, int64_t H, int64_t W, void* workspace,
+                                deqsci_stream_t stream);
+int deqsci_wgrad3x3_c1_c64_f32(const float* s, const float* t, float* dw, int flip, int64_t n, int64_t H, int64_t W, void* workspace,
+                               deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
