@@ -53,6 +53,14 @@ inline int pick_policy(int64_t bytes, int streaming_policy) {
     return bytes >= STREAM_MIN_BYTES ? streaming_policy : POL_DEFAULT;
 }
 
+// ReLU that keeps NaN: max(NaN, 0) = NaN as in torch.relu (v_maximum3_f32).  fmaxf(v, 0.0f) is maxNum (v_max_f32) and answers 0 for a NaN:
+// a non-finite activation would leave the layer as a clean number.  Every ReLU of the library goes through here, through the same builtin (the matrix-core
+// kernels conv_s16.hip, conv_w16.hip) or through the same instruction (winograd44.hip: relu_nan_asm); max(-0, +0) = +0, which no consumer tells from -0 (relu_mask_pack tests > 0).
+// The range-tracking maxima (sp16_wave_max_bits, the tmax folds of the heads) stay fmaxf ON PURPOSE: a measured range ignores NaN - the
+// exponent it picks only has to suit the finite values, the NaN itself travels in the data.
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+__device__ __forceinline__ float4 relu_nan(float4 v) { return make_float4(relu_nan(v.x), relu_nan(v.y), relu_nan(v.z), relu_nan(v.w)); }
+
 __device__ __forceinline__ float4 f4(float v) { return make_float4(v, v, v, v); }
 __device__ __forceinline__ float4 operator+(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 operator-(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }

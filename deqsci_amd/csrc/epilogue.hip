@@ -19,7 +19,7 @@ __global__ __launch_bounds__(TB) void bias_relu_nchw_kernel(float* __restrict__ 
     float* p = h + plane * HW + i;
     float4 v = ldp<POL>(p);
     v.x += b; v.y += b; v.z += b; v.w += b;
-    if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
+    if (relu) v = relu_nan(v);
     stp<POL>(p, v);
 }
 
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(TB) void bias_relu_nhwc_kernel(float* __restrict__ 
     const float4 b = ld4(bias + (int)((i * 4) % C));
     float4 v = ldp<POL>(h + i * 4);
     v = v + b;
-    if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
+    if (relu) v = relu_nan(v);
     stp<POL>(h + i * 4, v);
 }
 

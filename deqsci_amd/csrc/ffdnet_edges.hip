@@ -94,7 +94,7 @@ __global__ __launch_bounds__(TB) void edge_tail_kernel(const float* __restrict__
             float4 v = stg[i];
             if (bias && soff[i] >= 0) {   // the previous layer's folded-BN bias + ReLU applied on the way in (padding stays 0)
                 const float4 b = ld4(bias + half * TT_CH + (sdst[i] % TT_PS));
-                v.x = fmaxf(v.x + b.x, 0.0f); v.y = fmaxf(v.y + b.y, 0.0f); v.z = fmaxf(v.z + b.z, 0.0f); v.w = fmaxf(v.w + b.w, 0.0f);
+                v = relu_nan(v + b);
             }
             if (sdst[i] >= 0) *reinterpret_cast<float4*>(tile + sdst[i]) = v;
         }
@@ -173,14 +173,14 @@ __global__ __launch_bounds__(TB) void conv_c1_to_64_kernel(const float* __restri
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) acc = fma4(patch[(lr + tap / 3) * H1_PS + lc + tap % 3], wr[tap], acc);
         if (r < H && c < W) {
-            if (relu) { acc.x = fmaxf(acc.x, 0.0f); acc.y = fmaxf(acc.y, 0.0f); acc.z = fmaxf(acc.z, 0.0f); acc.w = fmaxf(acc.w, 0.0f); }
+            if (relu) acc = relu_nan(acc);
             if (OUT_SP16 == 3) {                                // couts 4 cq .. 4 cq + 3: half cq >> 3 of the pixel's word
                 const uint32_t m = mask[2 * ((int64_t)n * H * W + (int64_t)r * W + c) + (cq >> 3)] >> (4 * (cq & 7));
                 acc.x = (m & 1u) ? acc.x : 0.0f; acc.y = (m & 2u) ? acc.y : 0.0f;
                 acc.z = (m & 4u) ? acc.z : 0.0f; acc.w = (m & 8u) ? acc.w : 0.0f;
                 st4(hn + ((int64_t)r * W + c) * 64 + 4 * cq, acc);
             } else if (OUT_SP16) {
-                if (track) tmax = fmaxf(fmaxf(tmax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));   // (uniform branch)
+                if (track) tmax = fmaxf(fmaxf(tmax, fmaxf(fabsf(acc.x), fabsf(acc.y))), fmaxf(fabsf(acc.z), fabsf(acc.w)));   // (uniform branch; a range ignores NaN: common.hpp, relu_nan)
                 if (OUT_SP16 == 2) {                            // plane cq = couts 4 cq .. 4 cq + 3
                     const int64_t nbc = (W + 63) >> 6;
                     st4(h + ((((((int64_t)n * 16 + cq) * H + r) * nbc + (c >> 6)) * 2 + (c & 1)) * 32 + ((c & 63) >> 1)) * 4,
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(TB) void ffdnet_head_kernel(const float* __restrict
             }
         }
         if (r < H && c < W) {
-            const float4 o4 = make_float4(fmaxf(al[0], 0.0f), fmaxf(al[1], 0.0f), fmaxf(ah[0], 0.0f), fmaxf(ah[1], 0.0f));
+            const float4 o4 = relu_nan(make_float4(al[0], al[1], ah[0], ah[1]));
             st4(hn + ((int64_t)r * W + c) * 64 + 4 * cq, o4);
         }
     }
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(TB) void ffdnet_head_mfma_kernel(const float* __res
                 float* o = hn + ((int64_t)r * W + c) * 64 + 4 * kq;    // D: column = position pn, rows 4 kq .. 4 kq + 3 of the cout group
 #pragma unroll
                 for (int cg = 0; cg < 4; ++cg)
-                    st4(o + 16 * cg, make_float4(fmaxf(acc[cg][0], 0.0f), fmaxf(acc[cg][1], 0.0f), fmaxf(acc[cg][2], 0.0f), fmaxf(acc[cg][3], 0.0f)));
+                    st4(o + 16 * cg, relu_nan(make_float4(acc[cg][0], acc[cg][1], acc[cg][2], acc[cg][3])));
             }
         }
     }

@@ -289,8 +289,8 @@ __device__ __forceinline__ void winograd_conv64_body(const float* __restrict__ x
                 if (relu) {
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        o00[h][e] = fmaxf(o00[h][e], 0.0f); o01[h][e] = fmaxf(o01[h][e], 0.0f);
-                        o10[h][e] = fmaxf(o10[h][e], 0.0f); o11[h][e] = fmaxf(o11[h][e], 0.0f);
+                        o00[h][e] = relu_nan(o00[h][e]); o01[h][e] = relu_nan(o01[h][e]);
+                        o10[h][e] = relu_nan(o10[h][e]); o11[h][e] = relu_nan(o11[h][e]);
                     }
                 }
             }

@@ -104,6 +104,17 @@ __device__ __forceinline__ void store_out(f32x4 val, uint32_t vo, i32x4 rsrc, ui
 }
 #undef W44_ST
 
+// relu_nan (common.hpp) on the four couts of a store, as asm: the compiler turns `if (relu) v = maximum(v, 0)` into 128 selects that are
+// alive next to the accumulators, and the MFMA loop then spills one of those (see REGISTERS above); an asm statement stays behind its branch
+__device__ __forceinline__ void relu_nan_asm(f32x4& v) {
+    float a, b, c, d;
+    asm("v_maximum3_f32 %0, %1, 0, 0" : "=v"(a) : "v"(v.x));
+    asm("v_maximum3_f32 %0, %1, 0, 0" : "=v"(b) : "v"(v.y));
+    asm("v_maximum3_f32 %0, %1, 0, 0" : "=v"(c) : "v"(v.z));
+    asm("v_maximum3_f32 %0, %1, 0, 0" : "=v"(d) : "v"(v.w));
+    v = (f32x4){a, b, c, d};
+}
+
 // 1-D input transform of F(4,3): y = B^T x, B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
 __device__ __forceinline__ void bt_lo(const f32x2* x, f32x2& y0, f32x2& y1, f32x2& y2) {
     y0 = fma2(x[2], -5.0f, fma2(x[0], 4.0f, x[4]));
@@ -376,7 +387,7 @@ __global__ __launch_bounds__(TBW, 2) void winograd44_conv64_kernel(const float* 
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {
                         f32x4 val = mine[rr * 2 + c];
-                        if (relu) { val.x = fmaxf(val.x, 0.0f); val.y = fmaxf(val.y, 0.0f); val.z = fmaxf(val.z, 0.0f); val.w = fmaxf(val.w, 0.0f); }
+                        if (relu) relu_nan_asm(val);
                         if (oy + rr < H && ox + 2 * cp + c < W) {
                             // blk32: position 8 ((col+1)&3) + tx of the block.  Non-temporal; (s_nop: the wait states between a 16-byte
                             // store and the next write of its data registers, which the compiler cannot see into the asm to insert)
