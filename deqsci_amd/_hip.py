@@ -83,6 +83,8 @@ SIGNATURES = {
     "deqsci_epsilon2_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr],
     "deqsci_wgrad3x3_c64_c64_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_wgrad3x3_c1_c64_f32": [_ptr, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_wgrad3x3_c64_c64_bn_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_wgrad3x3_shuffle_f32": [_ptr, _ptr, _i64, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -91,7 +93,7 @@ OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunk
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
                  "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
-                 "deqsci_wgrad_workspace_bytes")
+                 "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -143,6 +145,8 @@ def load():
     lib.deqsci_epsilon2_chunk.argtypes = []
     lib.deqsci_wgrad_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_wgrad_workspace_bytes.argtypes = [_i64, _i64, _i64]
+    lib.deqsci_wgrad_bn_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_wgrad_bn_workspace_bytes.argtypes = [_i64, _i64, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -565,6 +569,68 @@ def wgrad_c1_c64(s, t, flip, workspace=None):
     dw = torch.empty((1, 64, 3, 3) if flip else (64, 1, 3, 3), device=t.device, dtype=torch.float32)
     with _dev(t):
         _check(load().deqsci_wgrad3x3_c1_c64_f32(_p(s, "s"), t.data_ptr(), dw.data_ptr(), int(flip), n, H, W, ws.data_ptr(), _stream()), "wgrad_c1_c64")
+    return dw
+
+
+def wgrad_bn_workspace(n, H, W, device):
+    """The scratch buffer of wgrad_c64_c64_bn / wgrad_shuffle for (n,64,H,W) activations (deqsci_wgrad_bn_workspace_bytes; serves both,
+    uninitialised)."""
+    nbytes = load().deqsci_wgrad_bn_workspace_bytes(n, H, W)
+    if nbytes == 0:
+        raise DeqsciHipError(f"wgrad_bn_workspace: sizes {(n, H, W)} are not served")
+    return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+
+
+def _wgrad_bn_ws(workspace, n, H, W, ref, what):
+    ws = workspace if workspace is not None else wgrad_bn_workspace(n, H, W, ref.device)
+    if (not isinstance(ws, torch.Tensor) or not ws.is_cuda or ws.device != ref.device or not ws.is_contiguous()
+            or ws.numel() * ws.element_size() < load().deqsci_wgrad_bn_workspace_bytes(n, H, W)):
+        raise DeqsciHipError(f"{what}: workspace must be a contiguous tensor of wgrad_bn_workspace{(n, H, W)}'s size on the inputs' device")
+    return ws
+
+
+def wgrad_c64_c64_bn(x, g, w, scale, workspace=None):
+    """A 64 -> 64 conv3x3 behind a frozen BatchNorm, y = relu(scale[co] conv(x, w) + shift) (csrc/wgrad_bn.hip W0-BN; deterministic): with
+    R = wgrad_c64_c64(x, g) -> (dw, dsum, ddot) = ((float)(scale[co] R) (64,64,3,3), sum_p g[p,co] (64,), sum_{ci,tap} w R (64,)), formed in
+    float64 from R's entry sums and rounded once.  w (64,64,3,3) and scale (64,) fp32 contiguous on x's device."""
+    _act64(x, "wgrad_c64_c64_bn", "x"), _act64(g, "wgrad_c64_c64_bn", "g")
+    if x.shape != g.shape or x.device != g.device:
+        raise DeqsciHipError(f"wgrad_c64_c64_bn: x {tuple(x.shape)} and g {tuple(g.shape)} must have one shape and device")
+    if tuple(w.shape) != (64, 64, 3, 3) or tuple(scale.shape) != (64,) or w.device != x.device or scale.device != x.device:
+        raise DeqsciHipError(f"wgrad_c64_c64_bn: w must be (64,64,3,3) and scale (64,) on x's device, got {tuple(w.shape)}, {tuple(scale.shape)}")
+    n, _, H, W = x.shape
+    ws = _wgrad_bn_ws(workspace, n, H, W, x, "wgrad_c64_c64_bn")
+    dw = torch.empty((64, 64, 3, 3), device=x.device, dtype=torch.float32)
+    dsum, ddot = torch.empty(64, device=x.device, dtype=torch.float32), torch.empty(64, device=x.device, dtype=torch.float32)
+    with _dev(x):
+        _check(load().deqsci_wgrad3x3_c64_c64_bn_f32(x.data_ptr(), g.data_ptr(), _p(w, "w"), _p(scale, "scale"), dw.data_ptr(), dsum.data_ptr(),
+                                                     ddot.data_ptr(), n, H, W, ws.data_ptr(), _stream()), "wgrad_c64_c64_bn")
+    return dw, dsum, ddot
+
+
+def wgrad_shuffle(img, t, which, sigma=None, workspace=None):
+    """The weight gradient of an FFDNet edge layer, read through the 2x2 pixel-unshuffle u of the planar (n,1,2H,2W) image img; t the
+    channels_last (n,64,H,W) activation (csrc/wgrad_bn.hip W2):
+    which = 0 -> (64,5,3,3): channels 1..4 sum t[:,c,p] u[:,q,p+d] (img the layer's input, t the masked gradient behind it), channel 0
+                 sum sigma[img] t[:,c,p] over the taps inside the image - sigma (1,) or (n,) fp32 on the device;
+    which = 1 -> (4,64,3,3): sum u[:,q,p] t[:,c,p+d] (img the gradient of the noise, t the last activation)."""
+    _act64(t, "wgrad_shuffle", "t")
+    n, _, H, W = t.shape
+    if tuple(img.shape) != (n, 1, 2 * H, 2 * W) or img.device != t.device:
+        raise DeqsciHipError(f"wgrad_shuffle: img must be the (n,1,2H,2W) = {(n, 1, 2 * H, 2 * W)} image on t's device, got {tuple(img.shape)}")
+    if which not in (0, 1):
+        raise DeqsciHipError(f"wgrad_shuffle: which must be 0 or 1, got {which!r}")
+    sp, stride = None, 0
+    if which == 0:
+        if (not isinstance(sigma, torch.Tensor) or sigma.device != t.device or sigma.dtype != torch.float32 or sigma.dim() != 1
+                or sigma.numel() not in (1, n) or (sigma.numel() > 1 and sigma.stride(0) not in (0, 1))):
+            raise DeqsciHipError("wgrad_shuffle: which = 0 needs sigma, a fp32 GPU vector of 1 or n elements")
+        sp, stride = sigma.data_ptr(), (0 if sigma.numel() == 1 else sigma.stride(0))
+    ws = _wgrad_bn_ws(workspace, n, H, W, t, "wgrad_shuffle")
+    dw = torch.empty((4, 64, 3, 3) if which else (64, 5, 3, 3), device=t.device, dtype=torch.float32)
+    with _dev(t):
+        _check(load().deqsci_wgrad3x3_shuffle_f32(_p(img, "img"), sp, stride, t.data_ptr(), dw.data_ptr(), int(which), n, 2 * H, 2 * W,
+                                                  ws.data_ptr(), _stream()), "wgrad_shuffle")
     return dw
 
 

@@ -10,6 +10,8 @@ The operators are linear in the image / measurement, so every backward is again 
 
     noise = D(x; W_0 .. W_{k-1})       grad_W_i = csrc/wgrad.hip on the kept activations and the masked gradients, grad_x = J_D(x)^T g
                                        (deqsci_amd.vjp.DenoiserParamGrads; DEQFixedPoint.parameter_backward = "device")
+    ... with a frozen BatchNorm        grad_W_i = s R, grad_beta = sum gm, grad_gamma = (sum W R - mean grad_beta) / sqrt(var + eps)
+                                       (csrc/wgrad_bn.hip; parameter_backward = "device+bn"; FFDNet: no grad_x, its input is detached)
 
 Masks (Phi, Phi_sum) are data: no gradient is produced for them (the reference never asks for one).
 (bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path.
@@ -67,13 +69,14 @@ class _GapUpdate(torch.autograd.Function):
 
 
 class _DenoiserNoise(torch.autograd.Function):
-    """noise = net(x) for a net vjp.param_eligibility accepts, forward and backward on the HIP kernels.  The conv weights are passed as
-    inputs so that autograd routes their gradients; the forward reads them from `net` (the same tensors)."""
+    """noise = net(x) for a net vjp.param_eligibility accepts, forward and backward on the HIP kernels.  The parameters are passed as
+    inputs so that autograd routes their gradients; the forward reads them from `net` (the same tensors).  sigma: FFDNet's noise levels
+    (data: no gradient); FFDNet detaches its input, so it returns no input gradient either."""
 
     @staticmethod
-    def forward(ctx, net, x, *weights):
+    def forward(ctx, net, x, sigma, frozen_bn, *params):
         from . import vjp
-        ctx.pg = vjp.DenoiserParamGrads(net, x)
+        ctx.pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn)
         return ctx.pg.noise
 
     @staticmethod
@@ -82,17 +85,20 @@ class _DenoiserNoise(torch.autograd.Function):
         if pg is None:
             raise RuntimeError("denoiser_noise: backward ran already (the kept activations are freed after the first)")
         try:
-            dws = pg.grads(gv, need=ctx.needs_input_grad[2:])
-            gx = pg.vjp(gv) if ctx.needs_input_grad[1] else None
+            dws = pg.grads(gv, need=ctx.needs_input_grad[4:])
+            gx = pg.vjp(gv) if ctx.needs_input_grad[1] and not pg.ffdnet else None
         finally:
             pg.release()
-        return (None, gx) + tuple(dws)
+        return (None, gx, None, None) + tuple(dws)
 
 
-def denoiser_noise(net, x):
-    """net(x) with the weight gradients (and the input gradient, where x requires one) formed on the device."""
+def denoiser_noise(net, x, sigma=None, frozen_bn=False):
+    """net(x) - net(x, sigma) for FFDNet - with the weight gradients (and the input gradient, where x requires one and the net does not
+    detach it) formed on the device.  frozen_bn=True: the nets vjp.param_eligibility(net, frozen_bn=True) accepts; the gradients go to
+    vjp.grad_parameters(net), the BatchNorm's gamma and beta among them."""
     from . import vjp
-    return _DenoiserNoise.apply(net, x, *vjp.conv_weights(net))
+    params = vjp.grad_parameters(net) if frozen_bn else vjp.conv_weights(net)
+    return _DenoiserNoise.apply(net, x, sigma, bool(frozen_bn), *params)
 
 
 def taping(*tensors):

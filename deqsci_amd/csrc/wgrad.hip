@@ -17,143 +17,12 @@
 //
 // Every workgroup owns a fixed run of consecutive tiles, accumulates in fp32 and adds its accumulators to its float64 partial in the
 // workspace (first flush: a store, so the workspace needs no initialisation) at the latest every DEQSCI_WGRAD_CHAIN pixels and at the end
-// of its run.  No atomics, no workgroup waits for another: bit-for-bit deterministic.
-#include "common.hpp"
+// of its run.  No atomics, no workgroup waits for another: bit-for-bit deterministic.  (The tiling and W0's kernel live in wgrad.hpp: the
+// frozen-BatchNorm form of csrc/wgrad_bn.hip is the same body with two more outputs.)
+#include "wgrad.hpp"
 
 namespace deqsci {
 namespace wgrad {
-
-constexpr int TW = 32;                                   // pixels of a tile
-constexpr int XW = TW + 2;                               // with the halo columns
-constexpr int CHAIN = DEQSCI_WGRAD_CHAIN;
-constexpr int FLUSH_TILES = CHAIN / TW;                  // a partial is flushed after this many tiles
-constexpr int W0_MAX_WG = 256, W1_MAX_WG = 512;          // fixed, not the device's: the workspace query has no device
-constexpr int W0_ENTRIES = 9 * 64 * 64, W1_ENTRIES = 9 * 64;
-constexpr int64_t MAX_SIDE = 1 << 20;
-static_assert(CHAIN % TW == 0 && FLUSH_TILES >= 1, "a flush falls on a tile boundary");
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-struct Split {
-    int64_t tiles, per_wg, wgs;
-};
-inline bool sizes_ok(int64_t n, int64_t H, int64_t W) { return n >= 1 && H >= 1 && W >= 1; }
-inline bool supported(int64_t n, int64_t H, int64_t W) {
-    return n <= MAX_SIDE && H <= MAX_SIDE && W <= MAX_SIDE && (double)n * (double)H * (double)ceil_div(W, TW) <= (double)INT32_MAX;
-}
-inline Split split(int64_t n, int64_t H, int64_t W, int max_wg) {
-    Split s;
-    s.tiles = n * H * ceil_div(W, TW);
-    s.per_wg = ceil_div(s.tiles, max_wg);
-    s.wgs = ceil_div(s.tiles, s.per_wg);                 // (no idle workgroup: every one has at least one tile)
-    return s;
-}
-
-struct Tile {
-    int64_t row;                                         // img * H + h
-    int h, w0;
-};
-__device__ __forceinline__ Tile tile_at(int64_t t, int H, int tilesW) {
-    Tile r;
-    r.row = t / tilesW;
-    r.w0 = (int)(t - r.row * tilesW) * TW;
-    r.h = (int)(r.row % H);
-    return r;
-}
-
-__global__ __launch_bounds__(TB) void wgrad_c64_kernel(const float* __restrict__ x, const float* __restrict__ g, double* __restrict__ part,
-                                                       int H, int W, int tilesW, int64_t tiles, int64_t per_wg) {
-    __shared__ float gL[TW * 64];
-    __shared__ float xL[3 * XW * 64];
-    const int tid = (int)threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int cob = (wave >> 1) * 32, cib = (wave & 1) * 32, col = lane & 31, half = lane >> 5;
-    const int64_t t0 = (int64_t)blockIdx.x * per_wg, t1 = t0 + per_wg < tiles ? t0 + per_wg : tiles;
-
-    v16f acc[9];
-    float4 rg[2], rx[7];
-    auto fetch = [&](const Tile& tl) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * TB, px = idx >> 4, c4 = idx & 15, w = tl.w0 + px;
-            rg[i] = w < W ? ld4(g + ((tl.row * W + w) * 64 + c4 * 4)) : f4(0.0f);
-        }
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            const int idx = tid + i * TB;
-            rx[i] = f4(0.0f);
-            if (idx < 3 * XW * 16) {
-                const int row = idx / (XW * 16), rem = idx - row * (XW * 16), c = rem >> 4, c4 = rem & 15;
-                const int hh = tl.h + row - 1, ww = tl.w0 + c - 1;
-                if (hh >= 0 && hh < H && ww >= 0 && ww < W) rx[i] = ld4(x + (((tl.row + row - 1) * W + ww) * 64 + c4 * 4));
-            }
-        }
-    };
-    auto stage = [&]() {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) st4(gL + (tid + i * TB) * 4, rg[i]);
-#pragma unroll
-        for (int i = 0; i < 7; ++i)
-            if (tid + i * TB < 3 * XW * 16) st4(xL + (tid + i * TB) * 4, rx[i]);
-    };
-    double* const mine = part + (int64_t)blockIdx.x * W0_ENTRIES;
-    auto flush = [&](bool first) {
-        double* base = mine + ((cob + 4 * half) * 64 + cib + col);
-        asm volatile("" : "+v"(base));                                      // (the 144 addresses are formed here, not kept across the tile loop)
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                double* p = base + ((tap * 64 + (r & 3) + 8 * (r >> 2)) * 64);
-                *p = first ? (double)acc[tap][r] : *p + (double)acc[tap][r];
-            }
-            asm volatile("" ::: "memory");                                  // one tap's 16 doubles in flight, not all 144
-        }
-    };
-
-    Tile cur = tile_at(t0, H, tilesW);
-    fetch(cur);
-    const float* const gb = gL + cob + col;
-    const float* const xb = xL + cib + col;
-    for (int64_t c0 = t0; c0 < t1; c0 += FLUSH_TILES) {                     // one partial per FLUSH_TILES tiles: the accumulators live in this loop only
-        const int64_t c1 = c0 + FLUSH_TILES < t1 ? c0 + FLUSH_TILES : t1;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        for (int64_t t = c0; t < c1; ++t) {
-            stage();
-            __syncthreads();
-            const Tile now = cur;
-            if (t + 1 < t1) {
-                cur = tile_at(t + 1, H, tilesW);
-                fetch(cur);
-            }
-            const bool rowok[3] = {now.h > 0, true, now.h < H - 1};
-#pragma unroll 4
-            for (int pp = 0; pp < TW / 2; ++pp) {
-                const int px = 2 * pp + half, w = now.w0 + px;
-                // every operand is read unconditionally; what must not be multiplied is zero on both sides by construction: g is staged as
-                // zero beyond the row's end and x as zero outside the image, a tap row / column outside the image zeroes a, and the one real
-                // x value a pixel beyond the row's end could meet (w == W, kx == 0: x[W-1]) is read one column further, where x is zero
-                const float a = gb[px * 64];
-                const float ax[3] = {w == 0 ? 0.0f : a, a, w == W - 1 ? 0.0f : a};
-                const int xc[3] = {px + (w == W ? 1 : 0), px + 1, px + 2};
-                float b[9];
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) b[ky * 3 + kx] = xb[(ky * XW + xc[kx]) * 64];
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx)
-                        acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x2f32(rowok[ky] ? ax[kx] : 0.0f, b[ky * 3 + kx], acc[ky * 3 + kx], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-        flush(c0 == t0);
-    }
-}
 
 __global__ __launch_bounds__(TB) void wgrad_c1_kernel(const float* __restrict__ s, const float* __restrict__ t, double* __restrict__ part,
                                                       int H, int W, int tilesW, int64_t tiles, int64_t per_wg) {
@@ -262,7 +131,7 @@ int deqsci_wgrad3x3_c64_c64_f32(const float* x, const float* g, float* dw, int64
     const wgrad::Split sp = wgrad::split(n, H, W, wgrad::W0_MAX_WG);
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(wgrad::wgrad_c64_kernel, dim3((unsigned)sp.wgs), dim3(TB), 0, st, x, g, part, (int)H, (int)W,
+    hipLaunchKernelGGL(wgrad::wgrad_c64_kernel<false>, dim3((unsigned)sp.wgs), dim3(TB), 0, st, x, g, part, (int)H, (int)W,
                        (int)ceil_div(W, wgrad::TW), sp.tiles, sp.per_wg);
     int rc = launch_status();
     if (rc != 0) return rc;

@@ -1,6 +1,8 @@
 """What a "conv stack" is, decided once: a denoiser's module sequence (conv -> optional BatchNorm -> optional ReLU, repeated) as
 [(weight, bias or None, relu)] with eval-mode BatchNorm folded into the convolution.  The engine's f-call (engine._Denoiser), the implicit
-backward and the Jacobian diagnostics (vjp.host_plan, vjp.ffdnet_plan) all run this list.  CPU-safe."""
+backward and the Jacobian diagnostics (vjp.host_plan, vjp.ffdnet_plan) all run this list.  conv_bn_stack is the same walk unfolded -
+[(conv, bn or None, relu)], the modules themselves - for what needs the BatchNorm's own parameters (vjp.grad_parameters and the
+frozen-BatchNorm weight gradients).  CPU-safe."""
 import torch
 
 
@@ -14,13 +16,13 @@ def _conv_ok(conv):
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
 
 
-def conv_stack(mods):
-    """(layers, reason): the module sequence `mods` (net.dncnn, FFDNet's itermediate_dncnn) as [(weight, bias or None, relu)], detached,
-    BatchNorm folded (weight * s, bias = beta - mean * s) - or (None, why not) when it is anything but 3x3, stride-1, pad-1 convolutions
-    without bias, each followed by an optional eval-mode BatchNorm2d and an optional ReLU."""
+def conv_bn_stack(mods):
+    """(stack, reason): the module sequence `mods` as [(conv module, BatchNorm2d module or None, relu)] - or (None, why not), by the rules
+    of conv_stack (which folds this list): 3x3, stride-1, pad-1 convolutions without bias, each followed by an optional eval-mode
+    BatchNorm2d and an optional ReLU."""
     from .networks.simplecnn import RealSNConv2d
     mods = list(mods)
-    layers, i = [], 0
+    stack, i = [], 0
     while i < len(mods):
         conv = mods[i]
         if isinstance(conv, RealSNConv2d):
@@ -34,18 +36,33 @@ def conv_stack(mods):
                 return None, "Conv2d with a bias"
         else:
             return None, f"unknown module {type(conv).__name__} where a convolution was expected"
-        w, b = conv.weight.detach(), None
+        bn = None
         i += 1
         if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
             bn = mods[i]
             if bn.training or not bn.track_running_stats:
                 return None, "BatchNorm2d in train mode (batch statistics: its Jacobian is not a fixed scale)"
-            w, b = (t.detach() for t in _fold_bn(w, bn))
             i += 1
         relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
         if relu:
             i += 1
         elif i < len(mods) and not isinstance(mods[i], (torch.nn.Conv2d, RealSNConv2d)):
             return None, f"unknown module {type(mods[i]).__name__}"
+        stack.append((conv, bn, relu))
+    return stack, None
+
+
+def conv_stack(mods):
+    """(layers, reason): the module sequence `mods` (net.dncnn, FFDNet's itermediate_dncnn) as [(weight, bias or None, relu)], detached,
+    BatchNorm folded (weight * s, bias = beta - mean * s) - or (None, why not) when it is anything but 3x3, stride-1, pad-1 convolutions
+    without bias, each followed by an optional eval-mode BatchNorm2d and an optional ReLU."""
+    stack, why = conv_bn_stack(mods)
+    if stack is None:
+        return None, why
+    layers = []
+    for conv, bn, relu in stack:
+        w, b = conv.weight.detach(), None
+        if bn is not None:
+            w, b = (t.detach() for t in _fold_bn(w, bn))
         layers.append((w, b, relu))
     return layers, None

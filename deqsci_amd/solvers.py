@@ -84,23 +84,37 @@ class EquilibriumProxGradSCI(nn.Module):
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
-    def device_param_eligibility(self):
-        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility)."""
+    def device_param_eligibility(self, frozen_bn=False):
+        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility;
+        frozen_bn=True: also a frozen-BatchNorm stack and tag 'ffdnet', vjp.param_eligibility(net, frozen_bn=True))."""
         if not (self.A is A_torch_ and self.At is At_torch_):
             return False, "custom A / At: the device call uses the HIP GAP projection"
-        return _vjp.param_eligibility(self.nonlinear_op)
+        ok, why = _vjp.param_eligibility(self.nonlinear_op)
+        if ok or not frozen_bn:
+            return ok, why
+        ok, why = _vjp.param_eligibility(self.nonlinear_op, frozen_bn=True)
+        if ok and isinstance(self.nonlinear_op, _vjp._modules()[1]) and getattr(self.nonlinear_op, "tag", None) != "ffdnet":
+            return False, f"FFDNet under nonlinear_op tag {getattr(self.nonlinear_op, 'tag', None)!r}: it gets its noise level under 'ffdnet' only"
+        return ok, why
 
-    def forward_param_device(self, z, y, Phi, Phi_sum):
+    def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False):
         """The taped call f(z) = z1 - D(z1) whose backward forms the denoiser's weight gradients on the HIP kernels: gap_update ->
-        autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called."""
-        ok, why = self.device_param_eligibility()
+        autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called.  frozen_bn=True serves
+        what device_param_eligibility(frozen_bn=True) accepts; FFDNet with _forward_taped's sigma bookkeeping."""
+        ok, why = self.device_param_eligibility(frozen_bn)
         if not ok:
             raise ValueError(f"forward_param_device: {why}")
         bsz, w, h, c = z.shape
+        op = self.nonlinear_op
+        bn = frozen_bn and not _vjp.param_eligibility(op)[0]
         z1 = _ag.gap_update(z, y, Phi, Phi_sum)
         zp = z1.permute(0, 3, 1, 2).contiguous()
         self._taped = (zp.detach().view(bsz * c, 1, w, h), None)
-        noise = _ag.denoiser_noise(self.nonlinear_op, zp.view(bsz * c, 1, w, h))
+        sigma = None
+        if bn and isinstance(op, _vjp._modules()[1]):
+            sigma = self._sigma(y, bsz * c)
+            self._taped = (self._taped[0], sigma)
+        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, bn)
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
     def device_vjp_eligibility(self):
@@ -288,8 +302,9 @@ class DEQFixedPoint(nn.Module):
         self.backward_fallback_reason = None
         # how the taped call z = f(z*) forms the denoiser's weight gradients: "autograd" (the torch module on the tape: MIOpen backward) or
         # "device" (EquilibriumProxGradSCI.forward_param_device: csrc/wgrad.hip, falling back to autograd where vjp.param_eligibility
-        # refuses).  last_parameter_path: the path of the last taped forward; parameter_fallback_reason: why not "device".  Independent of
-        # implicit_backward.
+        # refuses), or "device+bn" (everything "device" serves plus a frozen BatchNorm - conv + BN-eval + ReLU DnCNN, FFDNet: csrc/wgrad_bn.hip,
+        # vjp.param_eligibility(net, frozen_bn=True)).  last_parameter_path: the path of the last taped forward ("device" when served);
+        # parameter_fallback_reason: why not.  Independent of implicit_backward.
         self.parameter_backward = "autograd"
         self.last_parameter_path = None
         self.parameter_fallback_reason = None
@@ -338,21 +353,22 @@ class DEQFixedPoint(nn.Module):
 
     def _taped_call(self, z, x, Phi, Phi_sum):
         """The taped call z = f(z*) (:268): on the device's weight-gradient path where parameter_backward asks for it and it is served."""
-        if self.parameter_backward not in ("autograd", "device"):
-            raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd' or 'device'")
+        if self.parameter_backward not in ("autograd", "device", "device+bn"):
+            raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd', 'device' or 'device+bn'")
         self.parameter_fallback_reason = None
         self.last_parameter_path = "autograd"
-        if self.parameter_backward == "device":
+        if self.parameter_backward != "autograd":
+            frozen_bn = self.parameter_backward == "device+bn"
             f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
             if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
                 self.parameter_fallback_reason = "DataParallel over several devices (the taped call runs on replicas)"
             elif not isinstance(f, EquilibriumProxGradSCI):
                 self.parameter_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
             else:
-                ok, why = f.device_param_eligibility()
+                ok, why = f.device_param_eligibility(frozen_bn)
                 if ok:
                     self.last_parameter_path = "device"
-                    return f.forward_param_device(z, x, Phi, Phi_sum)
+                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn)
                 self.parameter_fallback_reason = why
         return self.f(z, x, Phi, Phi_sum)
 

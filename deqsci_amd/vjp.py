@@ -26,12 +26,22 @@ The weight gradients (dD/dtheta)^T v of a bias-free conv + ReLU stack come from 
 transposed masked layers carry v down, and layer i's dW_i is the correlation of its input with the masked gradient behind it
 (csrc/wgrad.hip: W0 for a 64 -> 64 layer, W1 for the two edge layers).  plan_param_grads is the host statement, DenoiserParamGrads the
 device's, param_eligibility says which nets qualify (DEQFixedPoint.parameter_backward = "device").
+
+With a frozen (eval-mode) BatchNorm behind a conv - FFDNet, a conv + BN + ReLU DnCNN; parameter_backward = "device+bn",
+param_eligibility(net, frozen_bn=True) - the layer is y = relu(s c + t), c = conv(x, W), s = gamma / sqrt(var + eps), t = beta - mean s, and
+with gm the masked gradient behind the ReLU and R = wgrad(x, gm):
+
+    dW = s R        dbeta = sum_p gm        dgamma = (sum_{ci,tap} W R - mean dbeta) / sqrt(var + eps)
+
+(sum_p gm c = sum W R: no stored pre-activation and no division by gamma, exact for gamma = 0 and gamma < 0; csrc/wgrad_bn.hip's W0-BN gives
+the three sums from one pass).  FFDNet's edge layers are read through the 2x2 pixel-(un)shuffle by W2 of the same file, sigma's channel of
+the first weight included.  grad_parameters names the parameters, plan_param_grads_frozen_bn is the host statement.
 """
 import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .layers import conv_stack
+from .layers import conv_bn_stack, conv_stack
 
 _FFDNET_OK = "FFDNet detaches its input: J_D^T = 0"
 
@@ -165,10 +175,69 @@ def plan_param_grads(layers, x, v, masks=None):
     return grads, used
 
 
-def param_eligibility(net):
+_FROZEN_BN_OK, _FROZEN_FFDNET_OK = "bias-free conv [+ frozen BN] + ReLU stack", "FFDNet with its BatchNorm frozen"
+
+
+def _bn_refusal(mods):
+    """Why a BatchNorm2d of `mods` is not a fixed affine map with parameters of its own, or None."""
+    for m in mods:
+        if isinstance(m, torch.nn.BatchNorm2d):
+            if not m.track_running_stats or m.running_mean is None or m.running_var is None:
+                return "BatchNorm2d without running statistics (track_running_stats=False: it normalises by the batch's)"
+            if m.training:
+                return "BatchNorm2d in train mode (batch statistics have no device kernel)"
+            if not m.affine or m.weight is None or m.bias is None:
+                return "BatchNorm2d without affine parameters (affine=False)"
+    return None
+
+
+def _frozen_bn_stack(net):
+    """(stack, ffdnet, reason): layers.conv_bn_stack of a net the frozen-BatchNorm weight gradients serve - [(conv, bn or None, relu)] and
+    whether its edge layers are FFDNet's - or (None, None, why not)."""
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    ffdnet = isinstance(net, FFDNet)
+    if ffdnet:
+        if net.num_input_channels != 1:
+            return None, None, "FFDNet with 3 channels (the HIP kernels cover the grayscale network only)"
+        mods = list(net.intermediate_dncnn.itermediate_dncnn)
+    else:
+        if getattr(net, "tag", None) != "denoiser":
+            return None, None, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' and 'ffdnet' plugins have device weight gradients"
+        if not isinstance(net, DnCNN):
+            return None, None, f"not a conv [+BN] + ReLU stack: {type(net).__name__}"
+        mods = list(net.dncnn)
+    if any(isinstance(m, RealSNConv2d) for m in mods):
+        return None, None, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
+    why = _bn_refusal(mods)
+    if why is not None:
+        return None, None, ("FFDNet: " if ffdnet else "") + why
+    stack, why = conv_bn_stack(mods)
+    if stack is None:
+        return None, None, why
+    shapes = [tuple(c.weight.shape) for c, _, _ in stack]
+    first, last = ((64, 5, 3, 3), (4, 64, 3, 3)) if ffdnet else ((64, 1, 3, 3), (1, 64, 3, 3))
+    if len(stack) < 2 or shapes[0] != first or shapes[-1] != last or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
+        return None, None, f"layer shapes {shapes}: the kernels cover {first[1]} -> 64 -> ... -> 64 -> {last[0]}"
+    if not all(r for _, _, r in stack[:-1]) or stack[-1][2]:
+        return None, None, "ReLU pattern other than after every layer but the last"
+    if stack[0][1] is not None or stack[-1][1] is not None:
+        return None, None, "BatchNorm2d behind the first or the last layer (the edge kernels have no scale)"
+    if not all(isinstance(c.weight, torch.nn.Parameter) for c, _, _ in stack):
+        return None, None, "a conv weight that is not an nn.Parameter"
+    return stack, ffdnet, None
+
+
+def param_eligibility(net, frozen_bn=False):
     """(ok, reason): whether DenoiserParamGrads (and DEQFixedPoint.parameter_backward = "device") can form the weight gradients of `net`:
     a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0,
-    no_bn=True) of any depth >= 2.  CPU-safe."""
+    no_bn=True) of any depth >= 2.  frozen_bn=True (parameter_backward = "device+bn") accepts in addition an eval-mode affine BatchNorm2d
+    with running statistics behind every 64 -> 64 conv - DnCNN(..., no_bn=False).eval() - and the grayscale FFDNet with its BatchNorms in
+    eval mode.  CPU-safe."""
+    if frozen_bn:
+        stack, ffdnet, why = _frozen_bn_stack(net)
+        if stack is None:
+            return False, why
+        return True, _FROZEN_FFDNET_OK if ffdnet else _FROZEN_BN_OK
     DnCNN, FFDNet, RealSNConv2d = _modules()
     if isinstance(net, FFDNet):
         return False, "FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient"
@@ -197,6 +266,78 @@ def param_eligibility(net):
 def conv_weights(net):
     """The conv weights of a net param_eligibility accepts, in layer order: the parameters DenoiserParamGrads.grads answers for."""
     return [m.weight for m in net.dncnn if isinstance(m, torch.nn.Conv2d)]
+
+
+def grad_parameters(net):
+    """The nn.Parameters of a net param_eligibility(net, frozen_bn=True) accepts, in module order - per layer the conv weight, then its
+    BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for."""
+    stack, _, why = _frozen_bn_stack(net)
+    if stack is None:
+        raise ValueError(f"grad_parameters: {why}")
+    out = []
+    for conv, bn, _ in stack:
+        out.append(conv.weight)
+        if bn is not None:
+            out += [bn.weight, bn.bias]
+    return out
+
+
+def _bn_scale(bn, like):
+    """(s, mean, 1 / sqrt(var + eps)) of a frozen BatchNorm in like's dtype and device."""
+    T = lambda p: p.detach().to(like)
+    inv = 1.0 / torch.sqrt(T(bn.running_var) + bn.eps)
+    return T(bn.weight) * inv, T(bn.running_mean), inv
+
+
+def plan_param_grads_frozen_bn(net, x, v, sigma=None, masks=None):
+    """(dD/dtheta)^T v of a net param_eligibility(net, frozen_bn=True) accepts, at x, in x's dtype - the host statement of what
+    DenoiserParamGrads(..., frozen_bn=True).grads runs: one masked forward of the unfolded layers y = relu(s conv(x, W) + t) keeps each
+    layer's input, the walk back carries gm with the folded transposed weights, and per layer R = conv2d_weight(input, gm) gives
+    dW = s R, dbeta = sum gm, dgamma = (sum W R - mean dbeta) / sqrt(var + eps).  FFDNet goes through FFDNET_EDGES at the noise level sigma
+    (1 or n values; sigma's channel of the first weight included) and differentiates nothing through its input.  masks: those of another
+    forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters order, masks)."""
+    stack, ffdnet, why = _frozen_bn_stack(net)
+    if stack is None:
+        raise ValueError(f"plan_param_grads_frozen_bn: {why}")
+    T = lambda p: p.detach().to(x)
+    if ffdnet:
+        _even(x, "plan_param_grads_frozen_bn")
+        if sigma is None:
+            raise ValueError("plan_param_grads_frozen_bn: FFDNet is evaluated at a noise level: sigma is required")
+        read = FFDNET_EDGES[0]
+        h, g = torch.cat((_sigma_map(sigma, x), read(x)), 1), read(v)
+    else:
+        h, g = x, v
+    inputs, used, bns = [h], [], []
+    for i, (conv, bn, relu) in enumerate(stack):
+        bns.append(None if bn is None else _bn_scale(bn, x))
+        if i == len(stack) - 1:
+            break
+        h = F.conv2d(h, T(conv.weight), padding=1)
+        if bn is not None:
+            s, mean, _ = bns[i]
+            h = h * s.view(1, -1, 1, 1) + (T(bn.bias) - mean * s).view(1, -1, 1, 1)
+        m = (masks[i] if masks is not None else h > 0) if relu else None
+        used.append(m)
+        if m is not None:
+            h = h * m
+        inputs.append(h)
+    per_layer = [None] * len(stack)
+    for i in range(len(stack) - 1, -1, -1):
+        W = T(stack[i][0].weight)
+        R = torch.nn.grad.conv2d_weight(inputs[i], W.shape, g, padding=1)
+        if bns[i] is None:
+            per_layer[i], folded = [R], W
+        else:
+            s, mean, inv = bns[i]
+            dbeta = g.sum((0, 2, 3))
+            per_layer[i] = [s.view(-1, 1, 1, 1) * R, ((W * R).sum((1, 2, 3)) - mean * dbeta) * inv, dbeta]
+            folded = W * s.view(-1, 1, 1, 1)
+        if i > 0:
+            g = F.conv2d(g, _transposed(folded), padding=1)
+            if used[i - 1] is not None:
+                g = g * used[i - 1]
+    return [t for layer in per_layer for t in layer], used
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
@@ -393,19 +534,54 @@ class DenoiserParamGrads:
     conv weight (conv_weights(net)): the masked transposed layers of .vjp carry the gradient down, csrc/wgrad.hip's W1 serves the two edge
     layers and W0 every 64 -> 64 layer.  need: one bool per weight - the walk stops below the lowest layer asked for, the others are None.
     .vjp(v) is the input product J_D(x)^T v.  .release() drops the activations.  Everything is enqueued on the current stream with no host
-    synchronisation.  Raises ValueError with param_eligibility()'s reason."""
+    synchronisation.  Raises ValueError with param_eligibility()'s reason.
 
-    def __init__(self, net, x):
-        ok, why = param_eligibility(net)
+    frozen_bn=True: the nets param_eligibility(net, frozen_bn=True) accepts, the BatchNorm folded into the forward and the walk as in
+    _MaskedStack; .grads answers for grad_parameters(net) in its order (per layer dW, then dgamma, dbeta) and `need` has one bool per
+    parameter.  A 64 -> 64 layer with a BatchNorm runs csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass).
+    FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
+    ffdnet_tail's, and .vjp is zero: its input is detached."""
+
+    def __init__(self, net, x, sigma=None, frozen_bn=False):
+        ok, why = param_eligibility(net, frozen_bn=frozen_bn)
         if not ok:
             raise ValueError(f"DenoiserParamGrads: {why}")
         self.shape = _image(x, "DenoiserParamGrads")
         self._x = _hip.f32c(x.detach())
-        self._stack = _MaskedStack(host_plan(net)[0], self._x, keep=True)
-        self.masks = self._stack.masks
-        self.noise = _hip.conv3x3_c64_to_1(self._stack.acts[-1], self._stack.tail_f)
         n, _, H, W = self.shape
-        self._ws = _hip.wgrad_workspace(n, H, W, self._x.device)
+        self.ffdnet = why == _FROZEN_FFDNET_OK
+        self._sigma, self._bn, self._ws_bn = None, None, None
+        if self.ffdnet:
+            _even(x, "DenoiserParamGrads")
+            if sigma is None:
+                raise ValueError("DenoiserParamGrads: FFDNet is evaluated at a noise level: sigma is required")
+            self._sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1)
+            if self._sigma.numel() not in (1, n):
+                raise ValueError(f"DenoiserParamGrads: sigma must have 1 or {n} elements, got {self._sigma.numel()}")
+            if self._sigma.numel() > 1 and self._sigma.stride(0) not in (0, 1):
+                self._sigma = self._sigma.contiguous()
+            self._stack = _MaskedStack(ffdnet_plan(net), self._x, self._sigma, keep=True)
+            self.noise = _hip.ffdnet_tail(self._stack.acts[-1], self._stack.tail_f)
+            H, W = H // 2, W // 2
+        else:
+            self._stack = _MaskedStack(host_plan(net)[0], self._x, keep=True)
+            self.noise = _hip.conv3x3_c64_to_1(self._stack.acts[-1], self._stack.tail_f)
+        self.masks = self._stack.masks
+        plain = True
+        if frozen_bn:
+            stack = _frozen_bn_stack(net)[0]
+            dev = lambda t, dt=torch.float32: t.detach().to(x.device, dt).contiguous()
+            self._bn = []                                                    # per layer None, or (w, s fp32; mean, 1 / sqrt(var + eps) float64)
+            for conv, bn, _ in stack:
+                if bn is None:
+                    self._bn.append(None)
+                else:
+                    inv = 1.0 / torch.sqrt(dev(bn.running_var, torch.float64) + bn.eps)
+                    self._bn.append((dev(conv.weight), (dev(bn.weight, torch.float64) * inv).float(), dev(bn.running_mean, torch.float64), inv))
+            if self.ffdnet or any(b is not None for b in self._bn):
+                self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, self._x.device)
+            plain = not self.ffdnet or any(b is None for b in self._bn[1:-1])
+        self._ws = _hip.wgrad_workspace(n, H, W, self._x.device) if plain else None
 
     def _v(self, v, what):
         if tuple(v.shape) != self.shape:
@@ -413,33 +589,51 @@ class DenoiserParamGrads:
         return _hip.f32c(v)
 
     def vjp(self, v):
-        return self._stack.vjp(self._v(v, "vjp"))
+        v = self._v(v, "vjp")
+        return torch.zeros_like(v) if self.ffdnet else self._stack.vjp(v)
+
+    def _middle(self, i, g):
+        """[dW] of 64 -> 64 layer i, or [dW, dgamma, dbeta] where it has a BatchNorm, from its input and the masked gradient g behind it."""
+        st = self._stack
+        bn = None if self._bn is None else self._bn[i]
+        if bn is None:
+            return [_hip.wgrad_c64_c64(st.acts[i - 1], g, self._ws)]
+        w, s, mean, inv = bn
+        dw, dsum, ddot = _hip.wgrad_c64_c64_bn(st.acts[i - 1], g, w, s, self._ws_bn)
+        return [dw, ((ddot.double() - mean * dsum.double()) * inv).float(), dsum]
 
     def grads(self, v, need=None):
         st = self._stack
         if st.acts is None:
             raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
         k = len(st.mid_t) + 2
-        need = [True] * k if need is None else [bool(b) for b in need]
-        if len(need) != k:
-            raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {k} conv weights")
+        counts = [1] * k if self._bn is None else [1 if b is None else 3 for b in self._bn]      # parameters per layer
+        first = [sum(counts[:i]) for i in range(k)]
+        total = sum(counts)
+        need = [True] * total if need is None else [bool(b) for b in need]
+        if len(need) != total:
+            raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {total} parameters")
         v = self._v(v, "grads")
-        out = [None] * k
+        out = [None] * total
         if not any(need):
             return out
-        lowest = need.index(True)
-        if need[k - 1]:
-            out[k - 1] = _hip.wgrad_c1_c64(v, st.acts[-1], 1, self._ws)
+        wanted = [any(need[first[i]:first[i] + counts[i]]) for i in range(k)]
+        lowest = wanted.index(True)
+        if wanted[k - 1]:
+            out[first[k - 1]] = (_hip.wgrad_shuffle(v, st.acts[-1], 1, None, self._ws_bn) if self.ffdnet
+                                 else _hip.wgrad_c1_c64(v, st.acts[-1], 1, self._ws))
         if lowest == k - 1:
             return out
-        g = _hip.conv3x3_c1_to_64_masked(v, st.tail_t, st.masks[-1])        # the gradient behind layer k-2, masked by its ReLU
+        # the gradient behind layer k-2, masked by its ReLU
+        g = (_hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked)(v, st.tail_t, st.masks[-1])
         for i in range(k - 2, 0, -1):
-            if need[i]:
-                out[i] = _hip.wgrad_c64_c64(st.acts[i - 1], g, self._ws)
+            if wanted[i]:
+                for j, t in enumerate(self._middle(i, g)):
+                    out[first[i] + j] = t if need[first[i] + j] else None
             if i == lowest:
                 return out
             g = _hip.conv3x3_c64_winograd_masked(g, st.mid_t[i - 1], st.masks[i - 1])
-        out[0] = _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
+        out[0] = _hip.wgrad_shuffle(self._x, g, 0, self._sigma, self._ws_bn) if self.ffdnet else _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
         return out
 
     def release(self):

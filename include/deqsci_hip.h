@@ -514,6 +514,28 @@ int deqsci_wgrad3x3_c64_c64_f32(const float* x, const float* g, float* dw, int64
 int deqsci_wgrad3x3_c1_c64_f32(const float* s, const float* t, float* dw, int flip, int64_t n, int64_t H, int64_t W, void* workspace,
                                deqsci_stream_t stream);
 
+/* ---- the same for a denoiser with a frozen (eval-mode) BatchNorm: FFDNet, conv + BN + ReLU DnCNN (csrc/wgrad_bn.hip).  The contract of W0 /
+ * W1 above holds for both: fixed runs of tiles, fp32 accumulators, float64 partials at the latest every DEQSCI_WGRAD_CHAIN pixels, a summing
+ * launch in ascending workgroup order that rounds once, deterministic bit for bit, no allocation, no host synchronisation, graph-capturable;
+ * a tap outside the image and a pixel beyond a row's end are never multiplied.  workspace = deqsci_wgrad_bn_workspace_bytes(n, H, W) bytes for
+ * (n,64,H,W) activations (0 for invalid sizes; serves both entries), 8-byte aligned, no initialisation needed.
+ * W0-BN  a middle layer y = relu(scale[co] * conv(x, w) + shift): with R = W0's dw(x, g),
+ *            dw[co][ci][ky][kx] = (float)(scale[co] * R),  dsum[co] = sum_p g[p,co],  ddot[co] = sum_{ci,ky,kx} w[co][ci][ky][kx] * R
+ *        from W0's entry sums in float64, each rounded once (scale == 1: dw is W0's bit for bit).  x, g as for W0; w dense (64,64,3,3),
+ *        scale, dsum, ddot 64 floats.  dbeta = dsum, dgamma = (ddot - mean * dsum) / sqrt(var + eps).
+ * W2     FFDNet's edge layers, read through the 2x2 pixel-unshuffle u[p, 2i+j] = img[2h+i, 2w+j] of the planar (n,1,H,W) image (H, W the
+ *        FULL-resolution sides; t is (n,64,H/2,W/2) channels_last; the workspace is that of (n, H/2, W/2)):
+ *            which = 0: dw (64,5,3,3), dw[c][1+q][tap] = sum_p t[p,c] * u[p+d, q],  dw[c][0][tap] = sum_p sigma[img] * t[p,c] over the p with
+ *                       p+d inside the half-resolution image (sigma: sigma_stride = 0 one float, = 1 n floats)
+ *            which = 1: dw (4,64,3,3), dw[q][c][tap] = sum_p u[p, q] * t[p+d, c]  (sigma is not read and may be NULL)
+ * NULL -> -1; n < 1, a non-positive or (W2) odd side -> -2; misaligned -> -3; an output or the workspace overlapping an input or one another,
+ * which other than 0 / 1, sigma_stride other than 0 / 1, sizes beyond W0's limits -> -4. */
+size_t deqsci_wgrad_bn_workspace_bytes(int64_t n, int64_t H, int64_t W);
+int deqsci_wgrad3x3_c64_c64_bn_f32(const float* x, const float* g, const float* w, const float* scale, float* dw, float* dsum, float* ddot,
+                                   int64_t n, int64_t H, int64_t W, void* workspace, deqsci_stream_t stream);
+int deqsci_wgrad3x3_shuffle_f32(const float* img, const float* sigma, int64_t sigma_stride, const float* t, float* dw, int which, int64_t n,
+                                int64_t H, int64_t W, void* workspace, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */

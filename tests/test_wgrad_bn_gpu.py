@@ -1,0 +1,443 @@
+"""GPU: the weight gradients of the denoisers with a frozen BatchNorm on the HIP kernels (csrc/wgrad_bn.hip) - W0-BN (a 64 -> 64 layer: dw, the
+sums of g and the dot with the weight) and both forms of W2 (FFDNet's edge layers through the 2x2 pixel-unshuffle) exactly on integer data
+and within the fp32 chain bound on normal data, DenoiserParamGrads(frozen_bn=True) against the float64 host statement under the device's own
+masks, and DEQFixedPoint(parameter_backward="device+bn") against the reference's own training runs (tests/golden/backward_ffdnet.npz,
+backward_dncnn_bn.npz) with its fallbacks.
+
+The shapes are test_wgrad_gpu.py's (half-resolution for W2, whose image has twice each side) and, per kernel, one at which a workgroup holds
+more than WGRAD_CHAIN pixels and flushes its partial more than once (W0-BN runs at most 256 workgroups like W0, W2 at most 512 like W1)."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import GOLDEN, rel_l2
+import test_wgrad_bn_host as host
+import test_wgrad_gpu as base
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    import deqsci_amd
+    from deqsci_amd import _hip, checkpoint, vjp
+    from deqsci_amd import autograd as ag
+    from deqsci_amd.cli import build_pipeline
+    from deqsci_amd.networks import DnCNN
+
+DEV = "cuda"
+W0BN_CAP, W2_CAP = 256, 512
+W0BN_SHAPES = base.SHAPES + [(17, 256, 256)]       # 17 * 256 * 8 tiles / 256 workgroups = 136 tiles = 4352 pixels each > WGRAD_CHAIN
+W2_SHAPES = base.SHAPES + [(33, 256, 256)]         # half resolution: 33 * 256 * 8 tiles / 512 workgroups = 132 tiles = 4224 pixels each
+FFDNET_GRAD_TOL = 5e-4                             # DESIGN f-4: the bound of test_training_backward_vs_reference_golden[ffdnet] on the autograd path
+_cl, _ints, _gamma, _window, TAPS = base._cl, base._ints, base._gamma, base._window, base.TAPS
+
+
+def test_flush_shapes_hold_more_than_a_chain_per_workgroup():
+    lib = _hip.load()
+    for (n, H, W), cap, entries in ((W0BN_SHAPES[-1], W0BN_CAP, 9 * 64 * 64 + 64), (W2_SHAPES[-1], W2_CAP, 5 * 9 * 64)):
+        tiles = n * H * -(-W // 32)
+        assert -(-tiles // cap) * 32 > _hip.WGRAD_CHAIN
+        assert lib.deqsci_wgrad_bn_workspace_bytes(n, H, W) >= cap * entries * 8        # the cap is the kernel's
+
+
+# ----------------------------------------------------------------------------- W0-BN
+def _pow2_scale(gen):
+    """64 scales that are signed powers of two (and one 0): scale * R is exact."""
+    s = torch.ldexp(torch.ones(64, device=DEV), torch.randint(-3, 4, (64,), device=DEV, generator=gen))
+    s = s * (1 - 2 * torch.randint(0, 2, (64,), device=DEV, generator=gen)).float()
+    s[11] = 0.0
+    return s
+
+
+def _ref_w0bn(x, g, w, scale):
+    R = base._ref_w0(x, g)
+    return scale.double().view(64, 1, 1, 1) * R, g.double().sum((0, 2, 3)), (w.double() * R).sum((1, 2, 3)), R
+
+
+@pytest.mark.parametrize("n,H,W", W0BN_SHAPES)
+def test_w0bn_is_exact_on_integer_data(n, H, W):
+    gen = torch.Generator(device=DEV).manual_seed(100 * n + H + W)
+    x, g = _cl(_ints((n, 64, H, W), gen)), _cl(_ints((n, 64, H, W), gen))
+    w, scale = _ints((64, 64, 3, 3), gen), _pow2_scale(gen)
+    dw, dsum, ddot = _hip.wgrad_c64_c64_bn(x, g, w, scale)
+    assert dw.shape == (64, 64, 3, 3) and dsum.shape == ddot.shape == (64,) and dw.dtype == dsum.dtype == ddot.dtype == torch.float32
+    want = _ref_w0bn(x, g, w, scale)
+    assert torch.equal(dw, want[0].float()) and torch.equal(dsum, want[1].float()) and torch.equal(ddot, want[2].float())
+    # scale == 1: the 64 -> 64 kernel's own output, bit for bit
+    assert torch.equal(_hip.wgrad_c64_c64_bn(x, g, w, torch.ones(64, device=DEV))[0], _hip.wgrad_c64_c64(x, g))
+
+
+@pytest.mark.parametrize("n,H,W", W0BN_SHAPES)
+def test_w0bn_rounding_determinism_and_nan(n, H, W):
+    gen = torch.Generator(device=DEV).manual_seed(n + 10 * H + W)
+    x, g = _cl(torch.randn(n, 64, H, W, device=DEV, generator=gen)), _cl(torch.randn(n, 64, H, W, device=DEV, generator=gen))
+    w, scale = torch.randn(64, 64, 3, 3, device=DEV, generator=gen), torch.randn(64, device=DEV, generator=gen)
+    ws = _hip.wgrad_bn_workspace(n, H, W, DEV)
+    ws.fill_(float("nan"))                                     # the workspace needs no initialisation
+    got = _hip.wgrad_c64_c64_bn(x, g, w, scale, ws)
+    want = _ref_w0bn(x, g, w, scale)
+    gam, u = _gamma(n, H, W), 2.0 ** -24
+    S = base._ref_w0(x.abs(), g.abs())
+    # dw = fl(scale * R64): the chain's error scaled, and the final rounding; dsum and ddot alike
+    bounds = (gam * scale.double().abs().view(64, 1, 1, 1) * S + u * want[0].abs(), gam * g.double().abs().sum((0, 2, 3)) + u * want[1].abs(),
+              gam * (w.double().abs() * S).sum((1, 2, 3)) + u * want[2].abs())
+    for name, a, b, bound in zip(("dw", "dsum", "ddot"), got, want, bounds):
+        err = (a.double() - b).abs()
+        print(f"W0-BN {name} {(n, H, W)}: max |err| / bound = {float((err / bound.clamp_min(1e-300)).max()):.3e}")
+        assert bool((err <= bound).all()), name
+    again = _hip.wgrad_c64_c64_bn(x, g, w, scale)
+    assert all(torch.equal(a, b) for a, b in zip(again, got))
+    assert torch.equal(_hip.wgrad_c64_c64_bn(x, g, w, torch.ones(64, device=DEV), ws)[0], _hip.wgrad_c64_c64(x, g))
+    # a NaN reaches exactly the entries whose sum holds one of its products
+    x[n - 1, 5, H - 1, W - 1] = float("nan")
+    g[0, 9, 0, 0] = float("nan")
+    got = _hip.wgrad_c64_c64_bn(x, g, w, scale, ws)
+    want = _ref_w0bn(x, g, w, scale)
+    assert bool(want[3].isnan().any())
+    assert torch.equal(got[0].isnan(), want[3].isnan())
+    assert torch.equal(got[1].isnan(), want[1].isnan()) and got[1].isnan().nonzero().flatten().tolist() == [9]
+    assert torch.equal(got[2].isnan(), want[3].isnan().any(3).any(2).any(1))
+    ok = ~want[3].isnan()
+    assert bool(((got[0].double() - want[0]).abs()[ok] <= bounds[0][ok]).all())
+
+
+# ----------------------------------------------------------------------------- W2
+def _ref_w2(img, t, which, sigma=None):
+    """float64, only the products that exist (a tap outside the half-resolution image is not multiplied)."""
+    u, t = F.pixel_unshuffle(img.double(), 2), t.double()
+    n, _, H, W = t.shape
+    if which == 0:
+        s = sigma.double().reshape(-1)
+        u = torch.cat(((s.expand(n) if s.numel() == 1 else s).view(n, 1, 1, 1).expand(n, 1, H, W), u), 1)
+    out = torch.zeros((4, 64, 3, 3) if which else (64, 5, 3, 3), dtype=torch.float64, device=img.device)
+    for ky, kx in TAPS:
+        win = _window(H, W, ky, kx)
+        if win is not None:
+            (ph, pw), (th, tw) = win
+            if which:                                            # (batched over the rows, then summed: one GEMM with K = n h w would run on few workgroups)
+                out[:, :, ky, kx] = torch.einsum("nqhw,nchw->nhqc", u[:, :, ph, pw], t[:, :, th, tw]).sum((0, 1))
+            else:
+                out[:, :, ky, kx] = torch.einsum("nchw,nkhw->nhck", t[:, :, ph, pw], u[:, :, th, tw]).sum((0, 1))
+    return out
+
+
+@pytest.mark.parametrize("n,H,W", W2_SHAPES)
+def test_w2_is_exact_on_integer_data_in_both_forms(n, H, W):
+    gen = torch.Generator(device=DEV).manual_seed(7 * n + 3 * H + W)
+    img, t = _ints((n, 1, 2 * H, 2 * W), gen), _cl(_ints((n, 64, H, W), gen))
+    sigmas = (_ints((n,), gen), _ints((1,), gen) + 4.0, (_ints((1,), gen) + 4.0).expand(n))          # per image, one for all, one expanded
+    for sigma in sigmas[:3 if n * H * W <= 1 << 16 else 1]:                                          # (how sigma is strided does not depend on the shape)
+        got = _hip.wgrad_shuffle(img, t, 0, sigma)
+        assert got.shape == (64, 5, 3, 3) and got.dtype == torch.float32
+        assert torch.equal(got, _ref_w2(img, t, 0, sigma[:1] if sigma.stride(0) == 0 else sigma).float())
+    got = _hip.wgrad_shuffle(img, t, 1)
+    assert got.shape == (4, 64, 3, 3) and got.dtype == torch.float32
+    assert torch.equal(got, _ref_w2(img, t, 1).float())
+
+
+@pytest.mark.parametrize("n,H,W", W2_SHAPES)
+def test_w2_rounding_determinism_and_nan(n, H, W):
+    gen = torch.Generator(device=DEV).manual_seed(3 * n + H + 10 * W)
+    img, t = torch.randn(n, 1, 2 * H, 2 * W, device=DEV, generator=gen), _cl(torch.randn(n, 64, H, W, device=DEV, generator=gen))
+    sigma = torch.rand(n, device=DEV, generator=gen) + 0.1
+    ws = _hip.wgrad_bn_workspace(n, H, W, DEV)
+    ws.fill_(float("nan"))
+    for which in (0, 1):
+        got = _hip.wgrad_shuffle(img, t, which, sigma, ws)
+        want, S = _ref_w2(img, t, which, sigma), _ref_w2(img.abs(), t.abs(), which, sigma)
+        err = (got.double() - want).abs()
+        print(f"W2 which={which} {(n, H, W)}: max |err| / (gamma S) = {float((err / (_gamma(n, H, W) * S).clamp_min(1e-300)).max()):.3e}")
+        assert bool((err <= _gamma(n, H, W) * S).all()), which
+        assert torch.equal(_hip.wgrad_shuffle(img, t, which, sigma), got)
+    # a NaN at a row's end and one in the last image's corner reach exactly the entries whose sum holds one of their products: not the
+    # taps that would read them from beyond a row's end or from another image's halo
+    img2, t2 = img.clone(), t.clone()
+    img2[0, 0, 0, 2 * W - 1] = float("nan")
+    t2[n - 1, 11, H - 1, 0] = float("nan")
+    for which in (0, 1):
+        got, want = _hip.wgrad_shuffle(img2, t2, which, sigma, ws), _ref_w2(img2, t2, which, sigma)
+        assert bool(want.isnan().any()) and not bool(want.isnan().all()) and torch.equal(got.isnan(), want.isnan()), which
+    # sigma's channel multiplies only where the tap is inside: a NaN sigma of one image stays in channel 0
+    s2 = sigma.clone()
+    s2[0] = float("nan")
+    got, want = _hip.wgrad_shuffle(img, t, 0, s2, ws), _ref_w2(img, t, 0, s2)
+    assert bool(want[:, 0].isnan().any()) and torch.equal(got.isnan(), want.isnan()) and not bool(got[:, 1:].isnan().any())
+
+
+def test_wgrad_bn_bindings_refuse_bad_arguments():
+    x = _cl(torch.zeros(1, 64, 4, 4, device=DEV))
+    w, s = torch.zeros(64, 64, 3, 3, device=DEV), torch.ones(64, device=DEV)
+    with pytest.raises(_hip.DeqsciHipError, match="channels_last"):
+        _hip.wgrad_c64_c64_bn(torch.zeros(1, 64, 4, 4, device=DEV), x, w, s)
+    with pytest.raises(_hip.DeqsciHipError, match="scale"):
+        _hip.wgrad_c64_c64_bn(x, x.clone(), w, torch.ones(32, device=DEV))
+    with pytest.raises(_hip.DeqsciHipError, match="workspace"):
+        _hip.wgrad_c64_c64_bn(x, x.clone(), w, s, torch.empty(16, device=DEV, dtype=torch.float64))
+    with pytest.raises(_hip.DeqsciHipError, match="workspace"):                     # W0's workspace is 64 words per workgroup short
+        _hip.wgrad_c64_c64_bn(x, x.clone(), w, s, _hip.wgrad_workspace(1, 4, 4, DEV))
+    with pytest.raises(_hip.DeqsciHipError, match="which"):
+        _hip.wgrad_shuffle(torch.zeros(1, 1, 8, 8, device=DEV), x, 2)
+    with pytest.raises(_hip.DeqsciHipError, match="image"):
+        _hip.wgrad_shuffle(torch.zeros(1, 1, 8, 10, device=DEV), x, 1)
+    with pytest.raises(_hip.DeqsciHipError, match="sigma"):
+        _hip.wgrad_shuffle(torch.zeros(1, 1, 8, 8, device=DEV), x, 0)
+
+
+# ----------------------------------------------------------------------------- DenoiserParamGrads(frozen_bn=True)
+class _FixedMask(torch.nn.Module):
+    def __init__(self, mask):
+        super().__init__()
+        self.mask = mask
+
+    def forward(self, h):
+        return h * self.mask
+
+
+def _masked_float64(net, masks):
+    """(float64 copy of the module with every ReLU replaced by `h * mask` - the device forward's decisions; its layer sequence, its
+    conv_bn_stack and its grad_parameters)."""
+    m64 = copy.deepcopy(net).double()
+    stack, params = vjp._frozen_bn_stack(m64)[0], vjp.grad_parameters(m64)      # (read before the ReLUs go: the walk knows no _FixedMask)
+    seq, k = (m64.intermediate_dncnn.itermediate_dncnn if hasattr(m64, "intermediate_dncnn") else m64.dncnn), 0
+    for i, mod in enumerate(list(seq)):
+        if isinstance(mod, torch.nn.ReLU):
+            seq[i] = _FixedMask(vjp.unpack_masks(masks[k]).double())
+            k += 1
+    assert k == len(masks)
+    return m64, seq, stack, params
+
+
+def _bounds(m64, seq, stack, call, v64, gam):
+    """Per parameter of grad_parameters(m64), from the float64 masked module: (A, B) with |device - float64| <= 1e-5 A + B expected, where
+    B is the kernels' own error - gam = the fp32 chain bound, applied to the sum of absolute products of each entry: S = wgrad(|input|, |gm|)
+    for R, so |s| gam S for dW = s R, gam sum|gm| for dbeta, and (gam sum_{ci,tap} |W| S + |mean| gam sum|gm|) / sqrt(var + eps) for
+    dgamma = (sum W R - mean dbeta) / sqrt(var + eps) - and A carries the allowance test_wgrad_gpu.py gives the fp32 forward and walk that
+    feed the kernels (1e-5 relative), per SUM: |dW|, |dbeta|, and for dgamma (|sum W R| + |mean dbeta|) / sqrt(var + eps), since the
+    two sums it subtracts each carry that error."""
+    taps = {}
+    hooks = [mod.register_forward_hook(lambda mod, inp, out: taps.__setitem__(mod, (inp[0].detach(), out))) for mod in seq
+             if isinstance(mod, (torch.nn.Conv2d, torch.nn.BatchNorm2d))]
+    y = call(m64)
+    for h in hooks:
+        h.remove()
+    behind = [taps[bn if bn is not None else conv][1] for conv, bn, _ in stack]
+    gms = torch.autograd.grad(y, behind, v64)
+    out = []
+    for (conv, bn, _), gm in zip(stack, gms):
+        W = conv.weight.detach()
+        x_in = taps[conv][0]
+        S = torch.nn.grad.conv2d_weight(x_in.abs(), W.shape, gm.abs(), padding=1)
+        R = torch.nn.grad.conv2d_weight(x_in, W.shape, gm, padding=1)
+        if bn is None:
+            out.append((R.abs(), gam * S))
+            continue
+        s, mean, inv = vjp._bn_scale(bn, W)
+        gsum, gabs = gm.sum((0, 2, 3)), gm.abs().sum((0, 2, 3))
+        out.append(((s.view(-1, 1, 1, 1) * R).abs(), gam * s.abs().view(-1, 1, 1, 1) * S))
+        out.append((((W * R).sum((1, 2, 3)).abs() + (mean * gsum).abs()) * inv, (gam * (W.abs() * S).sum((1, 2, 3)) + mean.abs() * gam * gabs) * inv))
+        out.append((gsum.abs(), gam * gabs))
+    return out
+
+
+def _bn_net(kind):
+    if kind == "ffdnet":
+        return host.seeded_ffdnet(4).to(DEV)
+    return host.seeded_bn_dncnn(5, 6).to(DEV)
+
+
+@pytest.mark.parametrize("kind,n,H,W", [("ffdnet", 2, 12, 20), ("ffdnet", 3, 74, 58), ("dncnn_bn5", 3, 37, 29)])
+def test_denoiser_param_grads_frozen_bn_vs_float64_host_statement(kind, n, H, W):
+    net = _bn_net(kind)
+    gammas = [m.weight for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    assert all(bool((g == 0).any()) and bool((g < 0).any()) for g in gammas)
+    gen = torch.Generator(device=DEV).manual_seed(n + H)
+    x = torch.rand(n, 1, H, W, device=DEV, generator=gen)
+    v = torch.randn(n, 1, H, W, device=DEV, generator=gen)
+    sigma = (torch.rand(n, device=DEV, generator=gen) * 0.2 + 0.02) if kind == "ffdnet" else None
+    with pytest.raises(ValueError):
+        vjp.DenoiserParamGrads(net, x, sigma)                                           # not without the keyword
+    pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn=True)
+    params = vjp.grad_parameters(net)
+    assert pg.shape == (n, 1, H, W) and len(pg.masks) == (14 if kind == "ffdnet" else 4)
+    # .noise is the module's, within fp32 (the BatchNorm folded)
+    with torch.no_grad():
+        n64 = copy.deepcopy(net).double()
+        ref_noise = n64(x.double(), sigma.double()) if kind == "ffdnet" else n64(x.double())
+    assert float((pg.noise.double() - ref_noise).norm() / ref_noise.norm()) < 1e-5
+    got = pg.grads(v)
+    assert len(got) == len(params) and all(a.shape == p.shape and a.dtype == torch.float32 for a, p in zip(got, params))
+    masks = [vjp.unpack_masks(m) for m in pg.masks]
+    want, _ = vjp.plan_param_grads_frozen_bn(copy.deepcopy(net).double(), x.double(), v.double(), None if sigma is None else sigma.double(), masks=masks)
+    # ... which is float64 autograd through the module under those masks
+    m64, seq, stack64, params64 = _masked_float64(net, pg.masks)
+    call = (lambda m: m(x.double(), sigma.double())) if kind == "ffdnet" else (lambda m: m(x.double()))
+    auto = torch.autograd.grad(call(m64), params64, v.double())
+    for a, b in zip(want, auto):
+        assert float((a - b).norm() / b.norm()) <= 1e-10
+    act = (n, H // 2, W // 2) if kind == "ffdnet" else (n, H, W)
+    names = {id(p): name for name, p in net.named_parameters()}
+    for i, (a, b, (A, B), p) in enumerate(zip(got, want, _bounds(m64, seq, stack64, call, v.double(), _gamma(*act)), params)):
+        err, bound = float((a.double() - b).norm()), float((1e-5 * A + B).norm())
+        print(f"{kind} {(n, H, W)} {names[id(p)]}: |err| {err:.3e} (bound {bound:.3e}; rel L2 {err / float(b.norm()):.3e})")
+        assert err <= bound, (i, names[id(p)], err, bound)
+    # the gamma = 0 unit has a gradient of its own (nothing divides by gamma), the input product is zero for FFDNet and DenoiserVJP's otherwise
+    assert float(got[2].abs()[5 if kind == "ffdnet" else 3]) > 0
+    assert torch.equal(pg.vjp(v), vjp.DenoiserVJP(net, x, sigma)(v))
+    if kind == "ffdnet":
+        assert not bool(pg.vjp(v).any())
+    # a subset of the parameters stops the walk early and leaves the others None; the same call again is bit-equal
+    k = len(got)
+    need = [False] * k
+    need[k - 3] = True                                                                 # the last BatchNorm's gamma alone
+    part = pg.grads(v, need=need)
+    assert all(t is None for j, t in enumerate(part) if j != k - 3) and torch.equal(part[k - 3], got[k - 3])
+    assert all(torch.equal(a, b) for a, b in zip(pg.grads(v), got))
+    pg.release()
+    with pytest.raises(RuntimeError, match="released"):
+        pg.grads(v)
+
+
+@pytest.mark.parametrize("kind", ["ffdnet", "dncnn_bn5"])
+def test_denoiser_noise_function_routes_gradients_to_grad_parameters_and_frees(kind):
+    net = _bn_net(kind)
+    gen = torch.Generator(device=DEV).manual_seed(2)
+    x = torch.rand(2, 1, 12, 10, device=DEV, generator=gen, requires_grad=True)
+    v = torch.randn(2, 1, 12, 10, device=DEV, generator=gen)
+    sigma = torch.full((2,), 0.1, device=DEV) if kind == "ffdnet" else None
+    params = vjp.grad_parameters(net)
+    assert len(params) == len(list(net.parameters())) and all(a is b for a, b in zip(params, net.parameters()))
+    params[1].requires_grad_(False)
+    asked = [p for p in params if p.requires_grad]
+    noise = ag.denoiser_noise(net, x, sigma, frozen_bn=True)
+    pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn=True)
+    assert torch.equal(noise, pg.noise)
+    got = torch.autograd.grad(noise, [x] + asked, v, retain_graph=True, allow_unused=True)
+    ref = [t for t, p in zip(pg.grads(v), params) if p.requires_grad]
+    assert len(got) == 1 + len(ref) and all(torch.equal(a, b) for a, b in zip(got[1:], ref))
+    if kind == "ffdnet":
+        assert got[0] is None                                                          # networks/ffdnet.py detaches its input
+    else:
+        assert torch.equal(got[0], pg.vjp(v))
+    with pytest.raises(RuntimeError, match="freed"):
+        torch.autograd.grad(noise, [asked[0]], v)
+
+
+# ----------------------------------------------------------------------------- DEQFixedPoint(parameter_backward="device+bn")
+def _G(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _deq_run(solver, g, parameter, implicit):
+    deq = deqsci_amd.DEQFixedPoint(solver, deqsci_amd.andersonexp, m=5, beta=1.0, lam=1e-2, max_iter=int(g["iters"]) if "iters" in g.files else 12, tol=1e-9)
+    deq.parameter_backward = parameter
+    deq.implicit_backward = implicit
+    calls = []
+    hook = solver.nonlinear_op.register_forward_hook(lambda *a: calls.append(torch.is_grad_enabled()))
+    Phi, y, Ps, gt = _G(g["Phi"]), _G(g["y"]), _G(g["Phi_sum"]), _G(g["gt"])
+    rec = deq(y, Phi, Ps, initial_point=deqsci_amd.initial_point(y, Phi, Ps, gt))
+    hook.remove()
+    loss = F.mse_loss(rec, gt)
+    solver.zero_grad()
+    loss.backward()
+    return deq, rec, loss, sum(calls)
+
+
+def _check_golden_run(g, solver, deq, rec, loss, implicit, grad_tol):
+    assert deq.last_parameter_path == "device" and deq.parameter_fallback_reason is None
+    assert deq.last_backward_path == implicit
+    assert rel_l2(rec.detach().cpu().numpy(), g["rec"]) <= 1e-4
+    assert abs(float(loss.detach()) - float(g["loss"])) < 1e-5 * float(g["loss"])
+    assert abs(deq.forward_res - float(g["forward_res"])) < 1e-2 * float(g["forward_res"])
+    assert abs(deq.backward_res - float(g["backward_res"])) < 1e-2 * float(g["backward_res"])
+    names = [name for name, _ in solver.named_parameters()]
+    assert ["grad." + name for name in names] == [k for k in g.files if k.startswith("grad.")]
+    for name, p in solver.named_parameters():
+        r = rel_l2(p.grad.cpu().numpy(), g["grad." + name])
+        print(f"implicit={implicit} {name}: rel L2 vs the reference {r:.3e}")
+        assert r < grad_tol, name
+
+
+@pytest.mark.parametrize("implicit", ["autograd", "device"])
+def test_device_bn_parameter_backward_vs_reference_golden_ffdnet(implicit):
+    g = np.load(os.path.join(GOLDEN, "backward_ffdnet.npz"))
+    solver, _ = build_pipeline("ffdnet", checkpoint.shipped("ffdnet_gray"), 12)
+    deq, rec, loss, taped_module_calls = _deq_run(solver, g, "device+bn", implicit)
+    assert taped_module_calls == 1, "the torch module ran on the tape for more than f0"
+    _check_golden_run(g, solver, deq, rec, loss, implicit, FFDNET_GRAD_TOL)
+    assert np.array_equal(solver.noise_sigma.cpu().numpy(), g["sigma_after"])       # the sigma state is the autograd path's
+
+
+def _golden_bn_solver(g):
+    net = DnCNN(1, num_of_layers=5, lip=0.0, no_bn=False, tag="denoiser")
+    net.load_state_dict({k[len("state."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("state.")})
+    return deqsci_amd.EquilibriumProxGradSCI(deqsci_amd.A_torch_, deqsci_amd.At_torch_, net.eval().to(DEV), eta=0.2)
+
+
+@pytest.mark.parametrize("implicit", ["autograd", "device"])
+def test_device_bn_parameter_backward_vs_reference_golden_bn_dncnn(implicit):
+    """tests/golden/make_wgrad_bn_golden.py: the reference's own run on its conv + BN + ReLU DnCNN, seeded so that the run is well conditioned
+    (`conditioning`: its gradients move by less than 1e-5 when x0 moves by 1e-7), at the project's parity bar 1e-4.  This net is not
+    detached: the input gradient of the taped call goes through DenoiserParamGrads.vjp."""
+    g = np.load(os.path.join(GOLDEN, "backward_dncnn_bn.npz"))
+    assert float(g["conditioning"].max()) < 1e-5
+    gamma = g["state.dncnn.3.weight"]
+    assert (gamma == 0).any() and (gamma < 0).any()
+    solver = _golden_bn_solver(g)
+    deq, rec, loss, taped_module_calls = _deq_run(solver, g, "device+bn", implicit)
+    assert taped_module_calls == 1, "the torch module ran on the tape for more than f0"
+    _check_golden_run(g, solver, deq, rec, loss, implicit, 1e-4)
+
+
+def test_device_bn_is_what_device_is_for_a_plain_stack():
+    g = np.load(os.path.join(GOLDEN, "backward.npz"))
+    grads = []
+    for parameter in ("device", "device+bn"):
+        solver, _ = build_pipeline("SimpleCNN", checkpoint.shipped("cnn"), 12)
+        deq, _, _, _ = _deq_run(solver, g, parameter, "autograd")
+        assert deq.last_parameter_path == "device" and deq.parameter_fallback_reason is None
+        grads.append([p.grad.clone() for p in solver.parameters()])
+    assert all(torch.equal(a, b) for a, b in zip(*grads))
+
+
+def test_device_still_falls_back_for_ffdnet():
+    g = np.load(os.path.join(GOLDEN, "backward_ffdnet.npz"))
+    solver, _ = build_pipeline("ffdnet", checkpoint.shipped("ffdnet_gray"), 12)
+    deq, _, _, taped_module_calls = _deq_run(solver, g, "device", "autograd")
+    assert deq.last_parameter_path == "autograd" and "FFDNet" in deq.parameter_fallback_reason and taped_module_calls == 2
+    for name, p in solver.named_parameters():
+        assert rel_l2(p.grad.cpu().numpy(), g["grad." + name]) < FFDNET_GRAD_TOL, name
+
+
+def test_device_bn_falls_back_for_train_mode_batchnorm_and_realsn():
+    def run(mode):
+        torch.manual_seed(0)
+        net = DnCNN(1, num_of_layers=5, lip=0.0, no_bn=False, tag="denoiser").to(DEV).train()
+        solver = deqsci_amd.EquilibriumProxGradSCI(deqsci_amd.A_torch_, deqsci_amd.At_torch_, net, eta=0.2)
+        deq = deqsci_amd.DEQFixedPoint(solver, deqsci_amd.andersonexp, m=5, beta=1.0, lam=1e-2, max_iter=6, tol=1e-9)
+        deq.parameter_backward = mode
+        gen = torch.Generator().manual_seed(1)
+        Phi = (torch.rand(1, 16, 16, 4, generator=gen) < 0.5).float().to(DEV)
+        gt = torch.rand(1, 16, 16, 4, generator=gen).to(DEV)
+        y = (gt * Phi).sum(-1)
+        Ps = deqsci_amd.phi_sum(Phi)
+        rec = deq(y, Phi, Ps, initial_point=deqsci_amd.initial_point(y, Phi, Ps, None))
+        F.mse_loss(rec, gt).backward()
+        return deq, [p.grad.clone() for p in solver.parameters()], (y, Phi, Ps)
+    d_dev, g_dev, _ = run("device+bn")
+    d_ref, g_ref, (y, Phi, Ps) = run("autograd")
+    assert d_dev.last_parameter_path == "autograd" and d_ref.last_parameter_path == "autograd"
+    assert "train mode" in d_dev.parameter_fallback_reason and d_ref.parameter_fallback_reason is None
+    for a, b in zip(g_dev, g_ref):
+        assert float((a.double() - b.double()).norm() / b.double().norm()) < 1e-6
+    # RealSN: the taped call itself goes to the module, with the reason recorded
+    solver, deq = build_pipeline("RealSN_SimpleCNN", checkpoint.shipped("rsn_cnn"), 6)
+    deq.parameter_backward = "device+bn"
+    z = deqsci_amd.initial_point(y, Phi, Ps, None)
+    with torch.no_grad():
+        want = solver(z, y, Phi, Ps)
+    got = deq._taped_call(z, y, Phi, Ps)
+    assert deq.last_parameter_path == "autograd" and "RealSNConv2d" in deq.parameter_fallback_reason
+    assert float((got.detach() - want).norm() / want.norm()) < 1e-5
