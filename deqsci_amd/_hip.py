@@ -29,6 +29,9 @@ SIGNATURES = {
     "deqsci_sci_adjoint_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr],
     "deqsci_phi_sum_f32": [_ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr],
     "deqsci_gap_update_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _int, _ptr],
+    "deqsci_gap_update_grad_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr],
+    "deqsci_sci_mask_grad_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _int, _ptr],
+    "deqsci_phi_sum_grad_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr],
     "deqsci_transpose_f32": [_ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr],
     "deqsci_residual_out_f32": [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr],
     "deqsci_residual_store_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _int, _int, _int, _ptr],
@@ -274,6 +277,57 @@ def gap_update(z, phi, y, phisum, layout_in=LAYOUT_HWB, layout_out=None, out=Non
                                             bsz, H, W, B, layout_in, layout_out, _phi_shared(phi, bsz), _stream()),
                "gap_update")
     return z1
+
+
+def gap_update_grad(z, phi, g, y, phisum, need=(True, True, False, False), out=None):
+    """G1, the backward of gap_update in one launch (HWB): (gphi, gs, gz, gy) for g = the gradient of z1, None where `need` is false.
+    gphi has Phi's shape and gs Phi_sum's; a shared mask's hold the sum over the batch.  out: four tensors or None, used where given."""
+    bsz, H, W, B = z.shape
+    if tuple(phi.shape[-3:]) != (H, W, B) or tuple(g.shape) != (bsz, H, W, B) or tuple(y.shape) != (bsz, H, W):
+        raise DeqsciHipError(f"gap_update_grad shapes z {tuple(z.shape)} Phi {tuple(phi.shape)} g {tuple(g.shape)} y {tuple(y.shape)}")
+    shared = _phi_shared(phi, bsz)
+    nm = 1 if shared else bsz
+    if phisum.numel() != nm * H * W:
+        raise DeqsciHipError(f"Phi_sum {tuple(phisum.shape)} does not match Phi {tuple(phi.shape)} (shared={shared})")
+    if not any(need):
+        raise DeqsciHipError("gap_update_grad: no output asked for")
+    shapes = (tuple(phi.shape), tuple(phisum.shape), (bsz, H, W, B), (bsz, H, W))
+    out = out or (None,) * 4
+    outs = [(o if o is not None else torch.empty(s, device=z.device, dtype=torch.float32)) if want else None
+            for want, s, o in zip(need, shapes, out)]
+    with _dev(z):
+        _check(load().deqsci_gap_update_grad_f32(_p(z, "z"), _p(phi, "Phi"), _p(g, "g"), _p(y, "y"), _p(phisum, "Phi_sum"),
+                                                 *[_p(o, allow_none=True) for o in outs], bsz, H, W, B, LAYOUT_HWB, shared, _stream()),
+               "gap_update_grad")
+    return tuple(outs)
+
+
+def sci_mask_grad(a, v, phi_shape, out=None):
+    """G2 (HWB): gphi_b = a v_b in the shape of the mask - (bsz,H,W,B) per measurement; (1,H,W,B) or (H,W,B): summed over the batch."""
+    bsz, H, W, B = v.shape
+    phi_shape = tuple(phi_shape)
+    if tuple(a.shape) != (bsz, H, W) or phi_shape[-3:] != (H, W, B):
+        raise DeqsciHipError(f"sci_mask_grad shapes a {tuple(a.shape)} v {tuple(v.shape)} Phi {phi_shape}")
+    shared = 1 if len(phi_shape) == 3 or (phi_shape[0] == 1 and bsz > 1) else 0
+    if not shared and phi_shape[0] != bsz:
+        raise DeqsciHipError(f"Phi batch {phi_shape[0]} does not match batch {bsz}")
+    gphi = out if out is not None else torch.empty(phi_shape, device=v.device, dtype=torch.float32)
+    with _dev(v):
+        _check(load().deqsci_sci_mask_grad_f32(_p(a, "a"), _p(v, "v"), _p(gphi, "gphi"), bsz, H, W, B, LAYOUT_HWB, shared, _stream()),
+               "sci_mask_grad")
+    return gphi
+
+
+def phi_sum_grad(phi, gs, out=None):
+    """G3 (HWB): the backward of phi_sum - gs spread over the frames, 0 where the sum of the mask is 0 (phi_sum wrote 1 there)."""
+    p4 = phi if phi.dim() == 4 else phi.unsqueeze(0)
+    nb, H, W, B = p4.shape
+    if gs.numel() != nb * H * W:
+        raise DeqsciHipError(f"phi_sum_grad shapes Phi {tuple(phi.shape)} gs {tuple(gs.shape)}")
+    gphi = out if out is not None else torch.empty(tuple(phi.shape), device=phi.device, dtype=torch.float32)
+    with _dev(phi):
+        _check(load().deqsci_phi_sum_grad_f32(_p(p4, "Phi"), _p(gs, "gs"), _p(gphi, "gphi"), nb, H, W, B, LAYOUT_HWB, _stream()), "phi_sum_grad")
+    return gphi
 
 
 def transpose(t, to_layout, out=None):

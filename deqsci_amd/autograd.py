@@ -13,10 +13,20 @@ The operators are linear in the image / measurement, so every backward is again 
     ... with a frozen BatchNorm        grad_W_i = s R, grad_beta = sum gm, grad_gamma = (sum W R - mean grad_beta) / sqrt(var + eps)
                                        (csrc/wgrad_bn.hip; parameter_backward = "device+bn"; FFDNet: no grad_x, its input is detached)
 
-Masks (Phi, Phi_sum) are data: no gradient is produced for them (the reference never asks for one).
+The masks are differentiable too (a learnable coded aperture); their gradients come from csrc/sci_grad.hip, in Phi's own shape - a
+mask shared by the batch, (1,H,W,B) or (H,W,B), gets the sum over the batch:
+
+    y = A(x, Phi)                      grad_Phi_b = grad_y x_b                                       (G2 sci_mask_grad)
+    x = At(y, Phi)                     grad_Phi_b = y grad_x_b                                       (G2)
+    s = phi_sum(Phi)                   grad_Phi_b = grad_s, 0 where sum_b Phi_b = 0 (s is 1 there)   (G3 phi_sum_grad)
+    z1 = gap_update(z, y, Phi, s)      r = (y - A z)/s, t = A(g)/s:  grad_Phi_b = r g_b - t z_b,  grad_s = -t r, and in the same launch
+                                       grad_z = g - t Phi, grad_y = t where asked for               (G1 gap_update_grad)
+
+With no mask gradient asked for, every backward makes the launches it always made.  The backwards are once-differentiable.
 (bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _hip
 from ._hip import LAYOUT_HWB
@@ -25,45 +35,75 @@ from ._hip import LAYOUT_HWB
 class _SCIForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, Phi):
-        Phi = _hip.f32c(Phi)
-        ctx.save_for_backward(Phi)
-        return _hip.sci_forward(_hip.f32c(x), Phi, LAYOUT_HWB)
+        ctx.phi_shape = tuple(Phi.shape)
+        x, Phi = _hip.f32c(x), _hip.f32c(Phi)
+        ctx.save_for_backward(Phi, x if ctx.needs_input_grad[1] else None)
+        return _hip.sci_forward(x, Phi, LAYOUT_HWB)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gy):
-        (Phi,) = ctx.saved_tensors
-        return _hip.sci_adjoint(_hip.f32c(gy), Phi, LAYOUT_HWB), None
+        Phi, x = ctx.saved_tensors
+        gy = _hip.f32c(gy)
+        gx = _hip.sci_adjoint(gy, Phi, LAYOUT_HWB) if ctx.needs_input_grad[0] else None
+        gphi = _hip.sci_mask_grad(gy, x, ctx.phi_shape) if ctx.needs_input_grad[1] else None
+        return gx, gphi
 
 
 class _SCIAdjoint(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, Phi):
-        Phi = _hip.f32c(Phi)
-        ctx.save_for_backward(Phi)
-        return _hip.sci_adjoint(_hip.f32c(y), Phi, LAYOUT_HWB)
+        ctx.phi_shape = tuple(Phi.shape)
+        y, Phi = _hip.f32c(y), _hip.f32c(Phi)
+        ctx.save_for_backward(Phi, y if ctx.needs_input_grad[1] else None)
+        return _hip.sci_adjoint(y, Phi, LAYOUT_HWB)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, gx):
+        Phi, y = ctx.saved_tensors
+        gx = _hip.f32c(gx)
+        gy = _hip.sci_forward(gx, Phi, LAYOUT_HWB) if ctx.needs_input_grad[0] else None
+        gphi = _hip.sci_mask_grad(y, gx, ctx.phi_shape) if ctx.needs_input_grad[1] else None
+        return gy, gphi
+
+
+class _PhiSum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Phi):
+        Phi = _hip.f32c(Phi)
+        ctx.save_for_backward(Phi)
+        return _hip.phi_sum(Phi, LAYOUT_HWB)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gs):
         (Phi,) = ctx.saved_tensors
-        return _hip.sci_forward(_hip.f32c(gx), Phi, LAYOUT_HWB), None
+        return _hip.phi_sum_grad(Phi, _hip.f32c(gs))
 
 
 class _GapUpdate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, y, Phi, Phi_sum):
-        Phi, Phi_sum = _hip.f32c(Phi), _hip.f32c(Phi_sum)
-        ctx.save_for_backward(Phi, Phi_sum)
-        return _hip.gap_update(_hip.f32c(z), Phi, _hip.f32c(y), Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
+        z, y, Phi, Phi_sum = _hip.f32c(z), _hip.f32c(y), _hip.f32c(Phi), _hip.f32c(Phi_sum)
+        mask = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        ctx.save_for_backward(Phi, Phi_sum, z if mask else None, y if mask else None)
+        return _hip.gap_update(z, Phi, y, Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
-        Phi, Phi_sum = ctx.saved_tensors
+        Phi, Phi_sum, z, y = ctx.saved_tensors
         g = _hip.f32c(g)
+        need_z, need_y, need_phi, need_s = ctx.needs_input_grad
+        if need_phi or need_s:                                     # one launch for everything that is asked for
+            gphi, gs, gz, gy = _hip.gap_update_grad(z, Phi, g, y, Phi_sum, need=(need_phi, need_s, need_z, need_y))
+            return gz, gy, gphi, gs
         gz = gy = None
-        if ctx.needs_input_grad[0]:
+        if need_z:
             zero_y = torch.zeros(g.shape[:3], device=g.device, dtype=torch.float32)
             gz = _hip.gap_update(g, Phi, zero_y, Phi_sum, LAYOUT_HWB, LAYOUT_HWB)
-        if ctx.needs_input_grad[1]:
+        if need_y:
             gy = _hip.sci_forward(g, Phi, LAYOUT_HWB) / Phi_sum
         return gz, gy, None, None
 
@@ -116,3 +156,7 @@ def sci_adjoint(y, Phi):
 
 def gap_update(z, y, Phi, Phi_sum):
     return _GapUpdate.apply(z, y, Phi, Phi_sum)
+
+
+def phi_sum(Phi):
+    return _PhiSum.apply(Phi)

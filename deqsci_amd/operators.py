@@ -17,14 +17,14 @@ from . import _hip, autograd as _ag
 
 def A_torch_(x, Phi):
     """Forward model of snapshot compressive imaging: y = sum_b x_b * Phi_b."""
-    if _ag.taping(x):
+    if _ag.taping(x, Phi):
         return _ag.sci_forward(x, Phi)
     return _hip.sci_forward(_hip.f32c(x), _hip.f32c(Phi), _hip.LAYOUT_HWB)
 
 
 def At_torch_(y, Phi):
     """Transpose of the forward model: x_b = y * Phi_b."""
-    if _ag.taping(y):
+    if _ag.taping(y, Phi):
         return _ag.sci_adjoint(y, Phi)
     return _hip.sci_adjoint(_hip.f32c(y), _hip.f32c(Phi), _hip.LAYOUT_HWB)
 
@@ -42,12 +42,16 @@ def initial_point_gaptv(y, Phi, Phi_sum, gt=None):
 
 
 def phi_sum(Phi):
-    """sum over the frame axis with zeros replaced by one."""
+    """sum over the frame axis with zeros replaced by one (differentiable in Phi: no gradient where the sum was replaced)."""
+    if _ag.taping(Phi):
+        return _ag.phi_sum(Phi)
     return _hip.phi_sum(_hip.f32c(Phi), _hip.LAYOUT_HWB)
 
 
 def gap_update(z, y, Phi, Phi_sum):
-    """z + At((y - A(z,Phi)) / Phi_sum, Phi) in one kernel (solvers/equilibrium_solvers_yaping.py:399-400)."""
+    """z + At((y - A(z,Phi)) / Phi_sum, Phi) in one kernel (solvers/equilibrium_solvers_yaping.py:399-400); differentiable in all four."""
+    if _ag.taping(z, y, Phi, Phi_sum):
+        return _ag.gap_update(z, y, Phi, Phi_sum)
     return _hip.gap_update(_hip.f32c(z), _hip.f32c(Phi), _hip.f32c(y), _hip.f32c(Phi_sum), _hip.LAYOUT_HWB)
 
 
@@ -66,11 +70,15 @@ class LinearOperator(torch.nn.Module):
 
 
 class SCIOperator(LinearOperator):
-    """Phi as a LinearOperator: forward = A_torch_(., Phi), adjoint = At_torch_(., Phi)."""
+    """Phi as a LinearOperator: forward = A_torch_(., Phi), adjoint = At_torch_(., Phi).  learnable=True: Phi is an nn.Parameter
+    (a coded aperture to be trained; its gradient comes from csrc/sci_grad.hip), otherwise a buffer."""
 
-    def __init__(self, Phi):
+    def __init__(self, Phi, learnable=False):
         super().__init__()
-        self.register_buffer("Phi", _hip.f32c(Phi))
+        if learnable:
+            self.Phi = torch.nn.Parameter(_hip.f32c(Phi.detach()).clone())
+        else:
+            self.register_buffer("Phi", _hip.f32c(Phi))
 
     def forward(self, x):
         return A_torch_(x, self.Phi)

@@ -175,7 +175,7 @@ class EquilibriumProxGradSCI(nn.Module):
         bsz, w, h, c = z.shape
         op = self.nonlinear_op
         tag = getattr(op, "tag", None)
-        if torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in op.parameters())):
+        if torch.is_grad_enabled() and (_ag.taping(z, y, Phi, Phi_sum) or any(p.requires_grad for p in op.parameters())):
             return self._forward_taped(z, y, Phi, Phi_sum)
         if self.A is A_torch_ and self.At is At_torch_:
             # K3 fused with the permute(0,3,1,2).contiguous() of :415/:419
@@ -277,6 +277,13 @@ def forward_iteration(f, x0, max_iter=50, tol=1e-5):
         if res[-1] < tol:
             break
     return f0, res
+
+
+def _data(*tensors):
+    """The measurement and the masks as data, for the graph J_f^T v is read from: J_f depends on their values only, and a tensor left on
+    that graph would have its gradient formed again in every iteration of the backward solve.  (One that asks for no gradient is passed
+    as it is, the same object.)"""
+    return tuple(t.detach() if isinstance(t, torch.Tensor) and t.requires_grad else t for t in tensors)
 
 
 class DEQFixedPoint(nn.Module):
@@ -404,14 +411,14 @@ class DEQFixedPoint(nn.Module):
         return _jac.power_report(self.jacobian_at(y, Phi, Phi_sum, z), tuple(z.shape), **kw)
 
     def forward(self, x, Phi, Phi_sum, initial_point=None, train_flag=True):
-        """x is the measurement y.  Without a tape (torch.no_grad(), or no parameter of f requiring a gradient) this is the
+        """x is the measurement y.  Without a tape (torch.no_grad(), or neither a parameter of f nor y, Phi, Phi_sum requiring a gradient) this is the
         inference path; with one it is the reference's training forward (:249-281): solve without tape, one taped f call,
         and the implicit-differentiation hook that solves  g = J_f^T g + grad  with the same solver and settings
         (`self.backward_res`).  `train_flag=False` skips the tape even when one could be recorded (the reference has that
         switch commented out, :277-279, and always records)."""
         init_point = torch.zeros_like(x) if initial_point is None else initial_point
         extras = self.snapshots is not None or bool(self.trace) or self.trace_gt is not None
-        if train_flag and torch.is_grad_enabled() and any(p.requires_grad for p in self.f.parameters()):
+        if train_flag and torch.is_grad_enabled() and (_ag.taping(x, Phi, Phi_sum) or any(p.requires_grad for p in self.f.parameters())):
             if extras:
                 raise NotImplementedError("snapshots / trace exist on the engine's inference path only: this is the taped training forward "
                                           "(pass train_flag=False or run under torch.no_grad())")
@@ -419,7 +426,7 @@ class DEQFixedPoint(nn.Module):
                 z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
             z = self._taped_call(z, x, Phi, Phi_sum)                           # re-engage the tape (:268)
             z0 = z.clone().detach().requires_grad_()
-            f0 = self.f(z0, x, Phi, Phi_sum)                                   # Jacobian-vector products come from this graph
+            f0 = self.f(z0, *_data(x, Phi, Phi_sum))                           # Jacobian-vector products come from this graph
             jmap = self._device_map(Phi, Phi_sum)
 
             if jmap is not None:
@@ -471,6 +478,9 @@ class EquilibriumADMMSCI(nn.Module):
         self.minval, self.maxval = minval, maxval
 
     def forward(self, z, u, y, Phi, Phi_sum):
+        if _ag.taping(Phi, Phi_sum):
+            raise NotImplementedError("EquilibriumADMMSCI has no mask gradient: Phi or Phi_sum requires one (detach them, or use "
+                                      "EquilibriumProxGradSCI, whose taped call differentiates the mask)")
         bsz, w, h, c = z.shape
         zu = _hip.f32c(z + u)
         if self.A is A_torch_ and self.At is At_torch_:
@@ -523,6 +533,9 @@ class DEQFixedPointADMM(nn.Module):
 
     def forward(self, x, Phi, Phi_sum, initial_point=None, train_flag=True):
         init_point = [torch.zeros_like(x), torch.zeros_like(x)] if initial_point is None else initial_point
+        if train_flag and _ag.taping(Phi, Phi_sum):
+            raise NotImplementedError("DEQFixedPointADMM has no mask gradient: Phi or Phi_sum requires one (pass train_flag=False, run under "
+                                      "torch.no_grad(), or use DEQFixedPoint with EquilibriumProxGradSCI)")
         with torch.no_grad():
             z, u, self.forward_res = self.solver1(lambda z, u: self.f(z, u, x, Phi, Phi_sum), init_point, **self.kwargs)
         return z

@@ -71,6 +71,30 @@ int deqsci_gap_update_f32(const float* z, const float* phi, const float* y, cons
                           float* z1, int64_t bsz, int64_t H, int64_t W, int64_t B,
                           int layout_in, int layout_out, int phi_shared, deqsci_stream_t stream);
 
+/* ---- mask gradients (csrc/sci_grad.hip): what training a coded aperture needs; not on the reconstruction path ----
+ * HWB only (any other layout: DEQSCI_ERR_UNSUPPORTED); outputs must not overlap inputs.  With phi_shared = 1 a mask gradient has ONE
+ * mask's shape and holds the sum over the batch, taken n = 0 .. bsz-1 in that order by the lane that owns the element (deterministic).
+ *
+ * G1  the backward of K3 in one launch.  g (bsz,H,W,B) is the gradient of z1; with fb = sum_b z_b Phi_b, q = sum_b g_b Phi_b (both
+ *     formed as K3 forms fb), r = (y - fb) / Phi_sum, t = q / Phi_sum, every operation rounded separately:
+ *         gphi_b = r g_b - t z_b     gs = -(t r)     gz_b = g_b - t Phi_b     gy = t
+ *     gphi (nm,H,W,B) and gs (nm,H,W) with nm = 1 for a shared mask, else bsz; gz (bsz,H,W,B) and gy (bsz,H,W) per measurement.
+ *     Each output pointer may be NULL (that output is skipped); all four NULL is DEQSCI_ERR_NULL. */
+int deqsci_gap_update_grad_f32(const float* z, const float* phi, const float* g, const float* y, const float* phisum,
+                               float* gphi, float* gs, float* gz, float* gy,
+                               int64_t bsz, int64_t H, int64_t W, int64_t B,
+                               int layout, int phi_shared, deqsci_stream_t stream);
+
+/* G2  gphi_b = a v_b, a (bsz,H,W), v (bsz,H,W,B): the mask gradient of K1 (a = grad y, v = x) and of K2 (a = y, v = grad x). */
+int deqsci_sci_mask_grad_f32(const float* a, const float* v, float* gphi,
+                             int64_t bsz, int64_t H, int64_t W, int64_t B,
+                             int layout, int phi_shared, deqsci_stream_t stream);
+
+/* G3  the backward of O4: gphi_b = gs where sum_b Phi_b != 0 and 0 where O4 wrote 1 (the sum is formed again in O4's order). */
+int deqsci_phi_sum_grad_f32(const float* phi, const float* gs, float* gphi,
+                            int64_t nb, int64_t H, int64_t W, int64_t B,
+                            int layout, deqsci_stream_t stream);
+
 /* (bsz,H,W,B) <-> (bsz,B,H,W) through an LDS tile; `to_layout` is the layout of `out`. */
 int deqsci_transpose_f32(const float* in, float* out,
                          int64_t bsz, int64_t H, int64_t W, int64_t B,
