@@ -88,6 +88,8 @@ SIGNATURES = {
     "deqsci_wgrad3x3_c1_c64_f32": [_ptr, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_wgrad3x3_c64_c64_bn_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_wgrad3x3_shuffle_f32": [_ptr, _ptr, _i64, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_realsn_power_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _int, _f32, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_realsn_grad_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -96,7 +98,7 @@ OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunk
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
                  "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
-                 "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes")
+                 "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes", "deqsci_realsn_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -150,6 +152,8 @@ def load():
     lib.deqsci_wgrad_workspace_bytes.argtypes = [_i64, _i64, _i64]
     lib.deqsci_wgrad_bn_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_wgrad_bn_workspace_bytes.argtypes = [_i64, _i64, _i64]
+    lib.deqsci_realsn_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_realsn_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -1628,6 +1632,60 @@ def power_step(w, v_prev, v_out, table_row, workspace=None):
         _check(load().deqsci_power_step_f32(_p(w, "w"), _p(v_prev, "v_prev", True), _p(v_out, "v_out"), table_row.data_ptr(), bsz, N,
                                             workspace.data_ptr(), _stream()), "power_step")
     return v_out
+
+
+# ----------------------------------------------------------------------------- RealSN in train mode (csrc/realsn.hip)
+def _realsn_dims(W, u, what):
+    if W.dim() != 4 or tuple(W.shape[2:]) != (3, 3):
+        raise DeqsciHipError(f"{what}: weight must be (C_out, C_in, 3, 3), got {tuple(W.shape)}")
+    cout, cin = int(W.shape[0]), int(W.shape[1])
+    if u.dim() != 4 or u.shape[0] != 1 or u.shape[1] != cout:
+        raise DeqsciHipError(f"{what}: u must be (1, {cout}, h, w), got {tuple(u.shape)}")
+    return cin, cout, int(u.shape[2]), int(u.shape[3])
+
+
+def realsn_workspace(cin, cout, h, w, device):
+    """The caller-owned workspace of realsn_power / realsn_grad for a (cout, cin, 3, 3) weight and an (h, w) map (no initialisation
+    needed); a DeqsciHipError for the sizes the kernels refuse."""
+    nbytes = load().deqsci_realsn_workspace_bytes(cin, cout, h, w)
+    if nbytes == 0:
+        raise DeqsciHipError(f"realsn: no kernel for a ({cout},{cin},3,3) weight on a ({h},{w}) map: (C_in, C_out) must be (1,64), (64,64) "
+                             "or (64,1), and h * w at most 2^20")
+    return _partials(nbytes, device)
+
+
+def realsn_power(W, u, n_iters=1, sigma=1.0, eps=1e-12, workspace=None):
+    """n_iters power-iteration steps of a spectrally normalised 3x3 convolution (conv_sn_chen.py:29-50 in the reference) and the
+    normalised weight, R1 of csrc/realsn.hip: u (1, C_out, h, w) is read and OVERWRITTEN with the new left vector.
+    -> (weight = W / cur_sigma * sigma, u, v (1, C_in, h, w), record): record = float64 (|W^T u|, |W v|, cur_sigma) of the last
+    iteration, on the device.  3 n_iters + 1 launches, no host synchronisation."""
+    cin, cout, h, w = _realsn_dims(W, u, "realsn_power")
+    if int(n_iters) < 1:
+        raise DeqsciHipError(f"realsn_power: n_iters must be at least 1, got {n_iters}")
+    ws = realsn_workspace(cin, cout, h, w, W.device) if workspace is None else workspace
+    v = torch.empty((1, cin, h, w), device=W.device, dtype=torch.float32)
+    weight = torch.empty_like(W)
+    record = torch.empty((3,), device=W.device, dtype=torch.float64)
+    with _dev(W):
+        _check(load().deqsci_realsn_power_f32(_p(W, "W"), _p(u, "u"), v.data_ptr(), _p(weight, "weight"), record.data_ptr(), int(n_iters),
+                                              float(sigma), float(eps), cin, cout, h, w, ws.data_ptr(), _stream()), "realsn_power")
+    return weight, u, v, record
+
+
+def realsn_grad(G, W, u, v, record, sigma=1.0, workspace=None):
+    """dL/dW of weight = W / cur_sigma * sigma with cur_sigma = sum(u * (W v)), u and v constants (R2 of csrc/realsn.hip): G = dL/dweight,
+    u, v, record as realsn_power left them.  2 launches, no host synchronisation."""
+    cin, cout, h, w = _realsn_dims(W, u, "realsn_grad")
+    if tuple(G.shape) != tuple(W.shape) or tuple(v.shape) != (1, cin, h, w):
+        raise DeqsciHipError(f"realsn_grad: G {tuple(G.shape)} must have W's shape {tuple(W.shape)} and v {tuple(v.shape)} be {(1, cin, h, w)}")
+    if record.dtype != torch.float64 or record.numel() != 3 or not record.is_contiguous() or record.device != W.device:
+        raise DeqsciHipError("realsn_grad: record must be realsn_power's 3 float64 values on W's device")
+    ws = realsn_workspace(cin, cout, h, w, W.device) if workspace is None else workspace
+    dW = torch.empty_like(W)
+    with _dev(W):
+        _check(load().deqsci_realsn_grad_f32(_p(G, "G"), _p(W, "W"), _p(u, "u"), _p(v, "v"), record.data_ptr(), _p(dW, "dW"), float(sigma),
+                                             cin, cout, h, w, ws.data_ptr(), _stream()), "realsn_grad")
+    return dW
 
 
 # ----------------------------------------------------------------------------- Broyden (csrc/broyden.hip)

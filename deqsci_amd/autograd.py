@@ -22,8 +22,13 @@ mask shared by the batch, (1,H,W,B) or (H,W,B), gets the sum over the batch:
     z1 = gap_update(z, y, Phi, s)      r = (y - A z)/s, t = A(g)/s:  grad_Phi_b = r g_b - t z_b,  grad_s = -t r, and in the same launch
                                        grad_z = g - t Phi, grad_y = t where asked for               (G1 gap_update_grad)
 
+A spectrally normalised convolution in train mode (networks.simplecnn.RealSNConv2d) normalises its weight at every call:
+
+    weight, u' = realsn(W, u)          one power-iteration step and weight = W / cur_sigma * sigma (csrc/realsn.hip R1; u', v constants)
+                                       grad_W = (sigma / cur_sigma) (g - (sum(g W) / cur_sigma) C),  C = d cur_sigma / dW   (R2)
+
 With no mask gradient asked for, every backward makes the launches it always made.  The backwards are once-differentiable.
-(bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path.
+(bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path, except for realsn_weight (deqsci_amd.realsn's restatement).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -130,6 +135,43 @@ class _DenoiserNoise(torch.autograd.Function):
         finally:
             pg.release()
         return (None, gx, None, None) + tuple(dws)
+
+
+class _RealSNWeight(torch.autograd.Function):
+    """(weight, u_new) of deqsci_amd.realsn.power_iteration with the gradient of weight with respect to W; u_new carries none."""
+
+    @staticmethod
+    def forward(ctx, W, u, sigma, n, eps):
+        from . import realsn
+        Wd = _hip.f32c(W.detach())
+        if Wd.is_cuda:
+            weight, u_new, v, record = _hip.realsn_power(Wd, u.detach().clone(memory_format=torch.contiguous_format), n, sigma, eps)
+        else:
+            weight, u_new, v, cur_sigma = realsn.power_iteration(Wd, u, sigma, n, eps)
+            record = cur_sigma
+        ctx.sigma = float(sigma)
+        ctx.save_for_backward(Wd, u_new, v, record)
+        ctx.mark_non_differentiable(u_new)
+        return weight, u_new
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _gu):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        from . import realsn
+        W, u, v, record = ctx.saved_tensors
+        G = _hip.f32c(G)
+        if W.is_cuda:
+            return _hip.realsn_grad(G, W, u, v, record, ctx.sigma), None, None, None, None
+        return realsn.weight_grad(G, W, u, v, record, ctx.sigma), None, None, None, None
+
+
+def realsn_weight(weight_orig, u, sigma=1.0, n_power_iterations=1, eps=1e-12):
+    """-> (weight, u_new): the train-mode weight of a spectrally normalised convolution, differentiable in weight_orig (u_new and the
+    right vector are constants, as in the reference), and the new weight_u.  u is not modified.  Device tensors: csrc/realsn.hip, no host
+    synchronisation; CPU tensors: deqsci_amd.realsn's restatement.  Once-differentiable: a double backward raises."""
+    return _RealSNWeight.apply(weight_orig, u, float(sigma), int(n_power_iterations), float(eps))
 
 
 def denoiser_noise(net, x, sigma=None, frozen_bn=False):

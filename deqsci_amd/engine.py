@@ -27,7 +27,9 @@ Semantics are the reference's (same slots k % m, same bordered system, residual 
 batch as at :184, returned iterate = f(X_last)).  Deliberate deviations, all result-neutral for the
 reference's own usage: sigma restarts at every reconstruct() call (the reference restarts when
 y.mean() changes); the dead second f-call of DEQFixedPoint.forward (:271-272, only feeds the
-backward hook) is skipped unless `extra_call=True`.
+backward hook) is skipped unless `extra_call=True` - or the denoiser has a train-mode RealSNConv2d,
+whose every call advances module state (weight_u, weight): such a net gets all max_iter + 2 calls and
+runs eagerly, never as a captured graph.
 """
 import math
 import numpy as np
@@ -804,6 +806,12 @@ class DEQSCIEngine:
         if initial_point is not None:
             initial_point = _hip.f32c(initial_point)
         graph = self.use_graph if self.use_graph != "auto" else bsz * H * W <= self.GRAPH_AUTO_PIXELS
+        if self._train_mode_realsn():
+            # every f-call advances weight_u and rewrites weight: module state a replayed graph would not carry from call to call
+            if self.use_graph is True:
+                raise ValueError("use_graph=True: the denoiser has a train-mode RealSNConv2d, whose every call runs a power-iteration step on "
+                                 "its weight_u and weight buffers; such a net runs eagerly (use_graph='auto' or False, or net.eval())")
+            graph = False
         self._grouped = False
         extras = self._snaps is not None or self._trace
         plan = None if (graph or extras) else self._group_plan(bsz, H, W, B, y.device)
@@ -827,6 +835,11 @@ class DEQSCIEngine:
         self._add_extras(ws, rec, last, res_row)
         self._warn_if_not_finite()
         return rec
+
+    def _train_mode_realsn(self):
+        """True where an f-call mutates the denoiser: a RealSNConv2d in train mode (deqsci_amd.networks.simplecnn)."""
+        from .networks.simplecnn import RealSNConv2d
+        return isinstance(self._net, torch.nn.Module) and any(isinstance(m, RealSNConv2d) and m.training for m in self._net.modules())
 
     def _add_extras(self, ws, rec, last, res_row):
         """last_info["snapshots"] / ["trace"] of the call in progress from the workspace (the stream is synchronised and ws.host_res holds
@@ -1010,7 +1023,8 @@ class DEQSCIEngine:
         out = _hip.f32c(out)
         rec = _hip.residual_out(ws.z1, out, LAYOUT_HWB) if is_noise else _hip.transpose(out, LAYOUT_HWB)
         call += 1
-        if self.extra_call:                                   # dead f0 = f(z) of :271-272
+        # dead f0 = f(z) of :271-272 - not dead for a train-mode RealSNConv2d: the call advances weight_u, as it does in the reference
+        if self.extra_call or self._train_mode_realsn():
             yield "fcall"
             zt = _hip.transpose(rec, LAYOUT_BHW)
             _hip.gap_update(zt, phi, y, ps, LAYOUT_BHW, out=ws.z1)

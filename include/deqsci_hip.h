@@ -560,6 +560,26 @@ int deqsci_wgrad3x3_c64_c64_bn_f32(const float* x, const float* g, const float* 
 int deqsci_wgrad3x3_shuffle_f32(const float* img, const float* sigma, int64_t sigma_stride, const float* t, float* dw, int which, int64_t n,
                                 int64_t H, int64_t W, void* workspace, deqsci_stream_t stream);
 
+/* ---- real spectral normalisation in train mode (csrc/realsn.hip): the power-iteration step of a spectrally normalised 3x3 convolution and
+ * the gradient of its normalised weight.  W (C_out, C_in, 3, 3) dense fp32, u (C_out, h, w), v (C_in, h, w) planar fp32.
+ * R1 power   n_iters >= 1 times:  t1 = W^T u (the adjoint of the pad-1 convolution),  v = t1 / max(|t1|, eps),  t2 = W v,  u = t2 / max(|t2|, eps);
+ *            then cur_sigma = sum(u * (W v)) and weight = W / cur_sigma * sigma_t (fp32, in this order).  u is read and overwritten; v, weight
+ *            and record are written: record[0] = |W^T u|, record[1] = |W v|, record[2] = cur_sigma of the last iteration, in float64.
+ *            3 n_iters + 1 launches on `stream`.
+ * R2 grad    dW = (sigma_t / cur_sigma) * (G - (sum(G * W) / cur_sigma) * C),  C[o,i,ky,kx] = sum_p u[o,p] v[i, p + (ky-1, kx-1)] (zero outside
+ *            the map), from R1's u, v and record; G, dW in W's shape.  2 launches.
+ * The convolutions and C accumulate in fp32 in a fixed order; the sums of squares, cur_sigma and sum(G * W) in float64 (csrc/rows.hpp), sqrt in
+ * float64, then fp32: the rounded norm, max(., eps), the division.  No atomics (bit-equal run to run), no allocation, no host synchronisation.
+ * (C_in, C_out) in {(1,64), (64,64), (64,1)}, h, w >= 1, h * w <= 2^20.  workspace = deqsci_realsn_workspace_bytes(C_in, C_out, h, w) bytes
+ * (0 for sizes that are refused; serves both entries), 16-byte aligned, no initialisation needed.
+ * NULL -> -1; a non-positive size, n_iters < 1 -> -2; a float array or the workspace not 16-byte, record not 8-byte aligned -> -3; another
+ * (C_in, C_out), a larger map, an output or the workspace overlapping an input or one another -> -4.  All checked before any launch. */
+size_t deqsci_realsn_workspace_bytes(int64_t C_in, int64_t C_out, int64_t h, int64_t w);
+int deqsci_realsn_power_f32(const float* W, float* u, float* v, float* weight, double* record, int n_iters, float sigma_t, float eps,
+                            int64_t C_in, int64_t C_out, int64_t h, int64_t w, void* workspace, deqsci_stream_t stream);
+int deqsci_realsn_grad_f32(const float* G, const float* W, const float* u, const float* v, const double* record, float* dW, float sigma_t,
+                           int64_t C_in, int64_t C_out, int64_t h, int64_t w, void* workspace, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
