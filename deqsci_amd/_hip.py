@@ -14,6 +14,7 @@ LAYOUT_HWB = 0   # (bsz,H,W,B)  reference API layout
 LAYOUT_BHW = 1   # (bsz,B,H,W)  planar / denoiser layout
 MAX_M = 8
 PART_STRIDE = MAX_M + 1
+BN_TRAIN_CHUNK, BN_TRAIN_MAX_WG = 128, 1024   # DEQSCI_BN_TRAIN_CHUNK, DEQSCI_BN_TRAIN_MAX_WG: the pixels of a workgroup of csrc/bn_train.hip, its most workgroups
 WGRAD_CHAIN = 4096   # DEQSCI_WGRAD_CHAIN: the most products a weight-gradient entry sums in fp32 before the float64 stage
 
 # DEQSCI_HIP_LIB: another build of the SAME library (tools only: the -DDEQSCI_DIAG variant of `make diag`, a stamp build of tools/lib_variants.sh)
@@ -90,6 +91,10 @@ SIGNATURES = {
     "deqsci_wgrad3x3_shuffle_f32": [_ptr, _ptr, _i64, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_realsn_power_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _int, _f32, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_realsn_grad_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_bn_train_stats_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _i64, _ptr, _ptr],
+    "deqsci_bn_train_apply_f32": [_ptr, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _int, _i64, _ptr],
+    "deqsci_bn_train_grad_stats_f32": [_ptr, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr],
+    "deqsci_bn_train_grad_apply_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _ptr, _i64, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -98,7 +103,8 @@ OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunk
                  "deqsci_partials_bytes", "deqsci_gram_bytes", "deqsci_gram_ref_bytes", "deqsci_ssim_workspace_bytes",
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
                  "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
-                 "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes", "deqsci_realsn_workspace_bytes")
+                 "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes", "deqsci_realsn_workspace_bytes",
+                 "deqsci_bn_train_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -154,6 +160,8 @@ def load():
     lib.deqsci_wgrad_bn_workspace_bytes.argtypes = [_i64, _i64, _i64]
     lib.deqsci_realsn_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_realsn_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
+    lib.deqsci_bn_train_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_bn_train_workspace_bytes.argtypes = [_i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -697,6 +705,119 @@ def _mask_ptr(mask, n, H, W, what):
             or not mask.is_contiguous()):
         raise DeqsciHipError(f"{what}: mask must be the contiguous int64 (n,H,W) = {(n, H, W)} GPU tensor of relu_mask_pack")
     return mask.data_ptr()
+
+
+# ----------------------------------------------------------------------------- BatchNorm2d in train mode (csrc/bn_train.hip)
+def bn_train_workspace(P, device):
+    """The scratch buffer of bn_train_stats / bn_train_grad_stats for P pixels (deqsci_bn_train_workspace_bytes; uninitialised)."""
+    nbytes = load().deqsci_bn_train_workspace_bytes(P)
+    if nbytes == 0:
+        raise DeqsciHipError(f"bn_train_workspace: {P} pixels are not served (torch: expected more than 1 value per channel when training)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def _bn_ws(workspace, P, ref, what):
+    ws = workspace if workspace is not None else bn_train_workspace(P, ref.device)
+    if (ws.device != ref.device or not ws.is_contiguous() or ws.data_ptr() % 8
+            or ws.numel() * ws.element_size() < load().deqsci_bn_train_workspace_bytes(P)):
+        raise DeqsciHipError(f"{what}: workspace must be a contiguous tensor of bn_train_workspace({P})'s size on the activation's device")
+    return ws
+
+
+def _bn_vec(t, dtype, numel, ref, what, name):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != ref.device):
+        raise DeqsciHipError(f"{what}: {name} must be a contiguous {dtype} tensor of {numel} elements on the activation's device")
+    return t.data_ptr()
+
+
+def bn_train_stats(c, running_mean=None, running_var=None, num_batches_tracked=None, momentum=0.1, record=None, workspace=None):
+    """T1: the batch mean and BIASED variance per channel of the fp32 channels_last (n,64,H,W) activation c, in float64 -> record (128,)
+    float64 = mean, var.  running_mean, running_var (fp32 (64,)) and num_batches_tracked (int64 scalar), all three or none, are updated IN
+    PLACE as torch's train-mode BatchNorm2d does.  4 launches, no host synchronisation."""
+    _act64(c, "bn_train_stats", "c")
+    n, _, H, W = c.shape
+    P = n * H * W
+    bufs = (running_mean, running_var, num_batches_tracked)
+    if any(b is None for b in bufs) and not all(b is None for b in bufs):
+        raise DeqsciHipError("bn_train_stats: running_mean, running_var and num_batches_tracked go together: all three or none")
+    rec = torch.empty(128, dtype=torch.float64, device=c.device) if record is None else record
+    rp = _bn_vec(rec, torch.float64, 128, c, "bn_train_stats", "record")
+    if bufs[0] is None:
+        rm = rv = nbt = None
+    else:
+        rm = _bn_vec(running_mean, torch.float32, 64, c, "bn_train_stats", "running_mean")
+        rv = _bn_vec(running_var, torch.float32, 64, c, "bn_train_stats", "running_var")
+        nbt = _bn_vec(num_batches_tracked, torch.int64, 1, c, "bn_train_stats", "num_batches_tracked")
+    ws = _bn_ws(workspace, P, c, "bn_train_stats")
+    with _dev(c):
+        _check(load().deqsci_bn_train_stats_f32(c.data_ptr(), rp, rm, rv, nbt, float(momentum), P, ws.data_ptr(), _stream()), "bn_train_stats")
+    return rec
+
+
+def bn_train_apply(c, record, gamma, beta, eps, relu=True, out=None, mask=None, want_mask=False):
+    """T2: y = relu?(gamma (c - mean) / sqrt(var + eps) + beta) from T1's record (the order of operations: include/deqsci_hip.h) as a
+    channels_last (n,64,H,W) activation; out may be c.  want_mask / mask: relu_mask_pack's (n,H,W) int64 words of y, written in the same
+    pass.  -> y, or (y, mask).  1 launch."""
+    _act64(c, "bn_train_apply", "c")
+    n, _, H, W = c.shape
+    o = torch.empty_like(c, memory_format=torch.channels_last) if out is None else out
+    if o is not c:
+        _act64(o, "bn_train_apply", "out")
+        if o.shape != c.shape or o.device != c.device:
+            raise DeqsciHipError(f"bn_train_apply: out {tuple(o.shape)} must have c's shape {tuple(c.shape)} and device")
+    if mask is None and want_mask:
+        mask = torch.empty((n, H, W), dtype=torch.int64, device=c.device)
+    mp = None if mask is None else _mask_ptr(mask, n, H, W, "bn_train_apply")
+    rp = _bn_vec(record, torch.float64, 128, c, "bn_train_apply", "record")
+    gp, bp = _bn_vec(gamma, torch.float32, 64, c, "bn_train_apply", "gamma"), _bn_vec(beta, torch.float32, 64, c, "bn_train_apply", "beta")
+    with _dev(c):
+        _check(load().deqsci_bn_train_apply_f32(c.data_ptr(), rp, gp, bp, float(eps), o.data_ptr(), mp, 1 if relu else 0, n * H * W, _stream()),
+               "bn_train_apply")
+    return o if mask is None else (o, mask)
+
+
+def bn_train_grad_stats(gy, c, record, eps, workspace=None, out=None):
+    """T3: from the (already ReLU-masked) gradient gy behind the layer and the stored convolution output c -> (dgamma, dbeta, grad_record):
+    dbeta = sum gy, dgamma = sum gy (c - mean) / sqrt(var + eps) in float64 (grad_record (128,) = dbeta, dgamma), rounded once to the two
+    fp32 (64,) outputs.  out: the three tensors to write instead of new ones.  2 launches."""
+    _act64(gy, "bn_train_grad_stats", "gy"), _act64(c, "bn_train_grad_stats", "c")
+    if gy.shape != c.shape or gy.device != c.device:
+        raise DeqsciHipError(f"bn_train_grad_stats: gy {tuple(gy.shape)} and c {tuple(c.shape)} must have one shape and device")
+    n, _, H, W = c.shape
+    rp = _bn_vec(record, torch.float64, 128, c, "bn_train_grad_stats", "record")
+    if out is None:
+        grec = torch.empty(128, dtype=torch.float64, device=c.device)
+        dgamma, dbeta = torch.empty(64, dtype=torch.float32, device=c.device), torch.empty(64, dtype=torch.float32, device=c.device)
+    else:
+        dgamma, dbeta, grec = out
+        _bn_vec(dgamma, torch.float32, 64, c, "bn_train_grad_stats", "out[0] (dgamma)"), _bn_vec(dbeta, torch.float32, 64, c, "bn_train_grad_stats", "out[1] (dbeta)")
+        _bn_vec(grec, torch.float64, 128, c, "bn_train_grad_stats", "out[2] (grad_record)")
+    ws = _bn_ws(workspace, n * H * W, c, "bn_train_grad_stats")
+    with _dev(c):
+        _check(load().deqsci_bn_train_grad_stats_f32(gy.data_ptr(), c.data_ptr(), rp, float(eps), grec.data_ptr(), dgamma.data_ptr(),
+                                                     dbeta.data_ptr(), n * H * W, ws.data_ptr(), _stream()), "bn_train_grad_stats")
+    return dgamma, dbeta, grec
+
+
+def bn_train_grad_apply(gy, c, record, grad_record, gamma, eps, out=None):
+    """T4: dc = gamma / sqrt(var + eps) (gy - dbeta / P - xhat dgamma / P), the gradient behind the convolution, statistic terms included
+    (they reach the pixels the ReLU masked too); out may be gy.  1 launch."""
+    _act64(gy, "bn_train_grad_apply", "gy"), _act64(c, "bn_train_grad_apply", "c")
+    if gy.shape != c.shape or gy.device != c.device:
+        raise DeqsciHipError(f"bn_train_grad_apply: gy {tuple(gy.shape)} and c {tuple(c.shape)} must have one shape and device")
+    n, _, H, W = c.shape
+    o = torch.empty_like(gy, memory_format=torch.channels_last) if out is None else out
+    if o is not gy:
+        _act64(o, "bn_train_grad_apply", "out")
+        if o.shape != gy.shape or o.device != gy.device:
+            raise DeqsciHipError(f"bn_train_grad_apply: out {tuple(o.shape)} must have gy's shape {tuple(gy.shape)} and device")
+    rp = _bn_vec(record, torch.float64, 128, c, "bn_train_grad_apply", "record")
+    gr = _bn_vec(grad_record, torch.float64, 128, c, "bn_train_grad_apply", "grad_record")
+    gp = _bn_vec(gamma, torch.float32, 64, c, "bn_train_grad_apply", "gamma")
+    with _dev(c):
+        _check(load().deqsci_bn_train_grad_apply_f32(gy.data_ptr(), c.data_ptr(), rp, gr, gp, float(eps), o.data_ptr(), n * H * W, _stream()),
+               "bn_train_grad_apply")
+    return o
 
 
 def conv3x3_c1_to_64_masked(x, w_packed, mask, out=None):

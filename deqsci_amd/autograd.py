@@ -12,6 +12,8 @@ The operators are linear in the image / measurement, so every backward is again 
                                        (deqsci_amd.vjp.DenoiserParamGrads; DEQFixedPoint.parameter_backward = "device")
     ... with a frozen BatchNorm        grad_W_i = s R, grad_beta = sum gm, grad_gamma = (sum W R - mean grad_beta) / sqrt(var + eps)
                                        (csrc/wgrad_bn.hip; parameter_backward = "device+bn"; FFDNet: no grad_x, its input is detached)
+    ... with a train-mode BatchNorm    grad_beta = sum gm, grad_gamma = sum gm xhat, dc = gamma / sqrt(var + eps) (gm - grad_beta / P - xhat grad_gamma / P),
+                                       grad_W_i = wgrad(input, dc)   (csrc/bn_train.hip; parameter_backward = "device+bn-train")
 
 The masks are differentiable too (a learnable coded aperture); their gradients come from csrc/sci_grad.hip, in Phi's own shape - a
 mask shared by the batch, (1,H,W,B) or (H,W,B), gets the sum over the batch:
@@ -119,9 +121,9 @@ class _DenoiserNoise(torch.autograd.Function):
     (data: no gradient); FFDNet detaches its input, so it returns no input gradient either."""
 
     @staticmethod
-    def forward(ctx, net, x, sigma, frozen_bn, *params):
+    def forward(ctx, net, x, sigma, frozen_bn, train_bn, *params):
         from . import vjp
-        ctx.pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn)
+        ctx.pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn, train_bn)
         return ctx.pg.noise
 
     @staticmethod
@@ -130,11 +132,11 @@ class _DenoiserNoise(torch.autograd.Function):
         if pg is None:
             raise RuntimeError("denoiser_noise: backward ran already (the kept activations are freed after the first)")
         try:
-            dws = pg.grads(gv, need=ctx.needs_input_grad[4:])
+            dws = pg.grads(gv, need=ctx.needs_input_grad[5:])
             gx = pg.vjp(gv) if ctx.needs_input_grad[1] and not pg.ffdnet else None
         finally:
             pg.release()
-        return (None, gx, None, None) + tuple(dws)
+        return (None, gx, None, None, None) + tuple(dws)
 
 
 class _RealSNWeight(torch.autograd.Function):
@@ -174,13 +176,14 @@ def realsn_weight(weight_orig, u, sigma=1.0, n_power_iterations=1, eps=1e-12):
     return _RealSNWeight.apply(weight_orig, u, float(sigma), int(n_power_iterations), float(eps))
 
 
-def denoiser_noise(net, x, sigma=None, frozen_bn=False):
+def denoiser_noise(net, x, sigma=None, frozen_bn=False, train_bn=False):
     """net(x) - net(x, sigma) for FFDNet - with the weight gradients (and the input gradient, where x requires one and the net does not
     detach it) formed on the device.  frozen_bn=True: the nets vjp.param_eligibility(net, frozen_bn=True) accepts; the gradients go to
-    vjp.grad_parameters(net), the BatchNorm's gamma and beta among them."""
+    vjp.grad_parameters(net), the BatchNorm's gamma and beta among them.  train_bn=True: the nets vjp.param_eligibility(net, train_bn=True)
+    accepts, normalised by the batch (csrc/bn_train.hip); the call moves the BatchNorms' running buffers as the module's own forward would."""
     from . import vjp
-    params = vjp.grad_parameters(net) if frozen_bn else vjp.conv_weights(net)
-    return _DenoiserNoise.apply(net, x, sigma, bool(frozen_bn), *params)
+    params = vjp.grad_parameters(net, train_bn=True) if train_bn else vjp.grad_parameters(net) if frozen_bn else vjp.conv_weights(net)
+    return _DenoiserNoise.apply(net, x, sigma, bool(frozen_bn), bool(train_bn), *params)
 
 
 def taping(*tensors):

@@ -29,7 +29,9 @@ reference's own usage: sigma restarts at every reconstruct() call (the reference
 y.mean() changes); the dead second f-call of DEQFixedPoint.forward (:271-272, only feeds the
 backward hook) is skipped unless `extra_call=True` - or the denoiser has a train-mode RealSNConv2d,
 whose every call advances module state (weight_u, weight): such a net gets all max_iter + 2 calls and
-runs eagerly, never as a captured graph.
+runs eagerly, never as a captured graph.  The same holds for a net whose train-mode BatchNorms run on
+the device (train_bn="device": csrc/bn_train.hip moves running_mean / running_var /
+num_batches_tracked at every f-call, as the module's own forward does).
 """
 import math
 import numpy as np
@@ -131,9 +133,17 @@ class _Denoiser:
     solvers/equilibrium_solvers_yaping.py:402-425."""
 
     def __init__(self, net, fold_bn=True, channels_last=None, fused_epilogue=True, fused_edges=True, winograd=True, conv64="fast",
-                 act_range="data", blk32=True, stack=True, stack_kernel="w16"):
+                 act_range="data", blk32=True, stack=True, stack_kernel="w16", train_bn="module"):
         from .networks import FFDNet
         self.net = net
+        # train_bn: what runs an f-call of a net whose BatchNorm2d layers are in TRAIN mode (batch statistics; the reference trains FFDNet so) -
+        # "module" (default): the plugin's own forward (MIOpen); "device": head kernel -> per layer [fp32 Winograd raw convolution -> T1
+        # statistics + buffer update -> T2 normalise + ReLU] -> tail kernel (csrc/bn_train.hip), for a net vjp.param_eligibility(net,
+        # train_bn=True) accepts.  A net it cannot serve keeps "module"; train_why says why.
+        if train_bn not in ("module", "device"):
+            raise ValueError(f"train_bn={train_bn!r}: expected 'module' or 'device'")
+        self.train_bn = train_bn
+        self.train, self.train_why, self._bn_ws = None, None, {}
         # stack_kernel: which kernel a stack launch of FFDNet's run runs - "w16" (default): the split-fp16 arithmetic under Winograd F(2,3) x
         # direct (csrc/conv_w16.hip: a third fewer matrix-core products, p32 activations between FFDNet's first and last layer); "s16": the
         # split-fp16 direct convolution (csrc/conv_s16.hip).  The measuring f-call keeps the direct kernel; SimpleCNN's two middle layers (a run
@@ -203,6 +213,9 @@ class _Denoiser:
         self.fast = None
         self.wino = None
         self.edges = e = _Edges(2 if isinstance(net, FFDNet) else 1)
+        self.train, self.train_why = None, None
+        if self.train_bn == "device" and isinstance(net, torch.nn.Module) and net.training:
+            self._refresh_train_bn(e)
         seq = None
         if isinstance(net, FFDNet) and not net.training and net.num_input_channels == 1 and self.fold_bn:
             seq = net.intermediate_dncnn.itermediate_dncnn
@@ -237,6 +250,43 @@ class _Denoiser:
                 elif not e.ffdnet and tuple(w0.shape) == (64, 1, 3, 3):
                     e.head_w = e.head_w16 = _hip.pack_c1_to_64_weights(w0)      # (one stencil kernel, three output layouts)
 
+    def _refresh_train_bn(self, e):
+        """train_bn="device": the UNFOLDED layers of a net in train mode - self.train = [(Conv64Weights, BatchNorm2d or None)] for the 64->64
+        layers, the edge kernels' packs in e - or train_why, the reason the net stays on its module."""
+        from . import vjp
+        ok, why = vjp.param_eligibility(self.net, train_bn=True)
+        if ok and not all(t.is_cuda and t.dtype == torch.float32 for t in list(self.net.parameters()) + list(self.net.buffers()) if t.is_floating_point()):
+            ok, why = False, "the net's parameters and buffers are not fp32 tensors on the GPU"
+        if not ok:
+            self.train_why = why
+            return
+        stack = vjp._bn_stack(self.net, True)[0]
+        w0, wl = stack[0][0].weight.detach(), stack[-1][0].weight.detach()
+        if e.ffdnet:
+            e.head_w, e.tail_w = _hip.pack_head_weights(w0), _hip.pack_tail_weights(wl)
+        else:
+            e.head_w, e.tail_w = _hip.pack_c1_to_64_weights(w0), _hip.pack_c64_to_1_weights(wl)
+        e.relu = True
+        self.train = [(_hip.pack_conv64_weights(conv.weight.detach(), s16=False), bn) for conv, bn, _ in stack[1:-1]]
+
+    def _train_bn_call(self, x, sg):
+        """One f-call with the BatchNorms normalising by the batch: no activation is kept, the module's buffers move once per layer."""
+        e = self.edges
+        h = e.head(x, sg)
+        P = h.shape[0] * h.shape[2] * h.shape[3]
+        ws = self._bn_ws.get((P, h.device))
+        if ws is None:
+            self._bn_ws = {(P, h.device): (_hip.bn_train_workspace(P, h.device), torch.empty(128, dtype=torch.float64, device=h.device))}
+            ws = self._bn_ws[(P, h.device)]
+        for weights, bn in self.train:
+            if bn is None:
+                h = _hip.conv3x3_c64(h, weights, None, True, policy="fast32")
+                continue
+            c = _hip.conv3x3_c64(h, weights, None, False, policy="fast32")
+            rec = _hip.bn_train_stats(c, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, record=ws[1], workspace=ws[0])
+            h = _hip.bn_train_apply(c, rec, bn.weight.detach(), bn.bias.detach(), bn.eps, relu=True, out=c)
+        return e.tail(h)
+
     def _run_stack(self, h, skip_last=False, skip_first=False, defer_last_epilogue=False, native_out=False):
         """defer_last_epilogue: leave the bias+ReLU of the last executed layer to the consumer (the fused
         FFDNet tail applies it while staging its input) and return (raw conv output, bias) - only when that
@@ -264,6 +314,9 @@ class _Denoiser:
     # 1->64 layer -> the run as ONE stack launch -> 64->1 layer (_sliced).  Set on the instance by a prepare() that is told the f-call's
     # batch (n_img=: the engine's own); a bare prepare(n_calls, device) + run() keeps the launch per layer of the kernels' own tests and tools.
     plain_sliced = False
+    # train_bn="device": the unfolded layers of a net whose train-mode BatchNorms run on csrc/bn_train.hip (_refresh_train_bn), else None
+    # and, where the option was asked for and the net is in train mode, the reason
+    train, train_why = None, None
 
     def _stack_for(self, idx, device, w16=False):
         """The Split16Stack (w16: Wino16Stack) of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a
@@ -289,6 +342,8 @@ class _Denoiser:
     def _route(self, n, H, W, device, policy, cal):
         """The path (_run_gen) of an f-call on n images of H x W under the conv64 `policy`, calibrating (cal) or not, from the attributes as
         they are NOW: tests and tools set them between calls, and the engine turns `stack` off and `per_layer_w16` on behind a time-out."""
+        if self.train is not None and self.tag in ("ffdnet", "denoiser") and torch.device(device).type == "cuda":
+            return "train bn per layer"
         if self.fast is None or self.tag not in ("ffdnet", "denoiser"):
             return "module"
         e, cuda = self.edges, torch.device(device).type == "cuda"
@@ -439,7 +494,10 @@ class _Denoiser:
         path = self._route(bsz * B, H, W, x.device, self._policy, cal)
         if self.tag in ("ffdnet", "denoiser"):
             sg = self.sigma_table[call:call + 1] if self.tag == "ffdnet" else None      # (a plain network takes no sigma)
-            if path == "module":
+            if path == "train bn per layer":
+                self.last_path = path
+                out = self._train_bn_call(x, sg)
+            elif path == "module":
                 out = self.net(x) if sg is None else self.net(x, sg.expand(bsz * B))
             elif path == "layers":
                 self.last_path = "per layer"
@@ -546,7 +604,7 @@ class DEQSCIEngine:
     def __init__(self, denoiser, iterator="anderson", m=5, beta=1.0, lam=1e-2, max_iter=180, tol=1e-5,
                  fold_bn=True, extra_call=False, poll_residual=True, channels_last=None, fused_epilogue=True,
                  fused_edges=True, winograd=True, use_graph="auto", conv64="auto", conv64_f22_calls=None, act_range="data", blk32=True, anderson_arith="reference",
-                 stack=True, stack_kernel="w16", groups=1):
+                 stack=True, stack_kernel="w16", groups=1, train_bn="module"):
         if iterator not in ("anderson", "picard"):
             raise ValueError(iterator)
         if not (groups == "auto" or (isinstance(groups, int) and 1 <= groups <= 2)):
@@ -564,7 +622,7 @@ class DEQSCIEngine:
         self._ctor = dict(iterator=iterator, m=m, beta=beta, lam=lam, max_iter=max_iter, tol=tol, fold_bn=fold_bn, extra_call=extra_call,
                           channels_last=channels_last, fused_epilogue=fused_epilogue, fused_edges=fused_edges, winograd=winograd, conv64=conv64,
                           conv64_f22_calls=conv64_f22_calls, act_range=act_range, blk32=blk32, anderson_arith=anderson_arith, stack=stack,
-                          stack_kernel=stack_kernel)
+                          stack_kernel=stack_kernel, train_bn=train_bn)
         self._net = denoiser
         self._kids, self._gate, self._grouped = None, None, False
         if anderson_arith not in ("float64", "reference"):
@@ -602,7 +660,9 @@ class DEQSCIEngine:
         # scale-free; fp16 pieces are not); "fixed" = 2^8 throughout, the round-3 behaviour (activations of a few units).
         self.den = _Denoiser(denoiser, fold_bn=fold_bn, channels_last=channels_last, fused_epilogue=fused_epilogue,
                              fused_edges=fused_edges, winograd=winograd, conv64=self.conv64_policy, act_range=act_range, blk32=blk32, stack=stack,
-                             stack_kernel=stack_kernel)
+                             stack_kernel=stack_kernel, train_bn=train_bn)
+        self.train_bn = train_bn
+        self._solve_only = False
         self.den.f22_calls = self.conv64_f22_calls
         self.iterator = iterator
         self.m, self.beta, self.lam = int(m), float(beta), float(lam)
@@ -750,6 +810,12 @@ class DEQSCIEngine:
             self.last_info["stack_timeouts"] = timed_out     # 1: a stack launch of THIS call timed out (the result below is the per-layer redo)
             # what the run of 64->64 layers of the LAST f-call went out as (the kernel actually used, for every call)
             self.last_info["denoiser_path"] = (self._kids[0].den.last_path if (self._grouped and self._kids) else self.den.last_path)
+            if self.train_bn == "device":
+                # what the option did for this call: "device" where the f-calls ran csrc/bn_train.hip, else "module" and why
+                served = self._train_bn_device()
+                self.last_info["train_bn"] = "device" if served else "module"
+                self.last_info["train_bn_reason"] = None if served else (
+                    self.den.train_why or "the denoiser is not in train mode (net.eval(): its BatchNorm is folded into the convolutions)")
             fallback = None
             if self.conv64 == "auto" and not math.isfinite(self.last_info["res"]) and bool(torch.isfinite(y).all()):
                 # conv64="auto" promises the reference's fp32 range: a non-finite residual under the split-fp16 layers (already warned
@@ -806,6 +872,14 @@ class DEQSCIEngine:
         if initial_point is not None:
             initial_point = _hip.f32c(initial_point)
         graph = self.use_graph if self.use_graph != "auto" else bsz * H * W <= self.GRAPH_AUTO_PIXELS
+        self.den._refresh()
+        if self._train_bn_device():
+            # every f-call moves the BatchNorms' running buffers, and the batch statistics are those of the WHOLE f-call's batch
+            if self.use_graph is True:
+                raise ValueError("use_graph=True: train_bn='device' runs the denoiser's train-mode BatchNorm2d layers on the device, and every "
+                                 "f-call moves their running_mean / running_var / num_batches_tracked; such a net runs eagerly "
+                                 "(use_graph='auto' or False, or net.eval())")
+            graph = False
         if self._train_mode_realsn():
             # every f-call advances weight_u and rewrites weight: module state a replayed graph would not carry from call to call
             if self.use_graph is True:
@@ -814,7 +888,7 @@ class DEQSCIEngine:
             graph = False
         self._grouped = False
         extras = self._snaps is not None or self._trace
-        plan = None if (graph or extras) else self._group_plan(bsz, H, W, B, y.device)
+        plan = None if (graph or extras or self._solve_only or self._train_bn_device()) else self._group_plan(bsz, H, W, B, y.device)
         if plan is not None:
             rec = self._reconstruct_grouped(plan, y, Phi4, Phi_sum, initial_point)
             if rec is not None:
@@ -835,6 +909,21 @@ class DEQSCIEngine:
         self._add_extras(ws, rec, last, res_row)
         self._warn_if_not_finite()
         return rec
+
+    def _train_bn_device(self):
+        """True where the f-calls run train-mode BatchNorms on the device (train_bn="device" and a net it serves): each moves the running buffers."""
+        return self.den.train is not None
+
+    @torch.no_grad()
+    def solve(self, y, Phi, Phi_sum=None, initial_point=None):
+        """The iteration ALONE: z*, the iterate the reference's solver returns (new_equilibrium_utils_yaping.py:189, :222) - not f(z*), no
+        closing call - as (bsz,H,W,B); last_info as reconstruct leaves it, "f_calls" = the calls of the loop.  What a training step's
+        no-tape solve needs (DEQFixedPoint with engine_options["train_bn"] = "device"): the taped call f(z*) is the caller's."""
+        self._solve_only = True
+        try:
+            return self.reconstruct(y, Phi, Phi_sum, initial_point)
+        finally:
+            self._solve_only = False
 
     def _train_mode_realsn(self):
         """True where an f-call mutates the denoiser: a RealSNConv2d in train mode (deqsci_amd.networks.simplecnn)."""
@@ -1017,6 +1106,8 @@ class DEQSCIEngine:
         else:
             x_last, call, last = yield from self._picard(ws, y, phi, ps, poll)
         res_row = last
+        if self._solve_only:
+            return _hip.transpose(x_last, LAYOUT_HWB), call, last, res_row
         # z = f(z*)  (new_equilibrium_utils_yaping.py:268)
         _hip.gap_update(x_last, phi, y, ps, LAYOUT_BHW, out=ws.z1)
         out, is_noise = yield from self._denoise_steps(ws.z1, call)
@@ -1024,7 +1115,7 @@ class DEQSCIEngine:
         rec = _hip.residual_out(ws.z1, out, LAYOUT_HWB) if is_noise else _hip.transpose(out, LAYOUT_HWB)
         call += 1
         # dead f0 = f(z) of :271-272 - not dead for a train-mode RealSNConv2d: the call advances weight_u, as it does in the reference
-        if self.extra_call or self._train_mode_realsn():
+        if self.extra_call or self._train_mode_realsn() or self._train_bn_device():
             yield "fcall"
             zt = _hip.transpose(rec, LAYOUT_BHW)
             _hip.gap_update(zt, phi, y, ps, LAYOUT_BHW, out=ws.z1)
@@ -1036,7 +1127,7 @@ class DEQSCIEngine:
     def _replay(self, ws, y, Phi4, Phi_sum, initial_point):
         """-> reconstruction, or None when this call has to take the eager path (first call of a shape: it warms every
         kernel up; or the tolerance test fired inside the replayed run)."""
-        key = (tuple(y.shape), tuple(Phi4.shape), Phi_sum is not None, initial_point is not None, self.den._wkey, self.extra_call,
+        key = (tuple(y.shape), tuple(Phi4.shape), Phi_sum is not None, initial_point is not None, self.den._wkey, self.extra_call, self._solve_only,
                None if self.den.sigma_table is None else self.den.sigma_table.data_ptr(), self._snaps, self._trace and self._gt is not None)
         g = self._graph
         if g is None or g["key"] != key or g["ws"] is not ws:

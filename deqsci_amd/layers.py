@@ -16,10 +16,11 @@ def _conv_ok(conv):
             and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
 
 
-def conv_bn_stack(mods):
+def conv_bn_stack(mods, train_bn=False):
     """(stack, reason): the module sequence `mods` as [(conv module, BatchNorm2d module or None, relu)] - or (None, why not), by the rules
     of conv_stack (which folds this list): 3x3, stride-1, pad-1 convolutions without bias, each followed by an optional eval-mode
-    BatchNorm2d and an optional ReLU."""
+    BatchNorm2d and an optional ReLU.  train_bn=True: the same walk for a net whose BatchNorm2d layers normalise by the batch (nothing to
+    fold: vjp.param_eligibility(net, train_bn=True) says what they must be)."""
     from .networks.simplecnn import RealSNConv2d
     mods = list(mods)
     stack, i = [], 0
@@ -40,7 +41,7 @@ def conv_bn_stack(mods):
         i += 1
         if i < len(mods) and isinstance(mods[i], torch.nn.BatchNorm2d):
             bn = mods[i]
-            if bn.training or not bn.track_running_stats:
+            if not train_bn and (bn.training or not bn.track_running_stats):
                 return None, "BatchNorm2d in train mode (batch statistics: its Jacobian is not a fixed scale)"
             i += 1
         relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)

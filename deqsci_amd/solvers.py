@@ -54,6 +54,13 @@ class EquilibriumProxGradSCI(nn.Module):
             self.noise_sigma = self.noise_sigma * SIGMA_DECAY
         return self.noise_sigma
 
+    def _sigma_resume(self, y, n, sigma):
+        """Leave the sigma bookkeeping where f-calls made elsewhere (the engine's solve of a training step, which reads sigma from its table)
+        left it: `sigma` (one element) is the noise level of the last of those calls on y, so the next _sigma(y, n) decays it once more."""
+        self.y = y.mean()
+        self._y_ref, self._y_ver = y, y._version
+        self.noise_sigma = sigma.reshape(1).to(torch.float32).expand(n)
+
     def _forward_taped(self, z, y, Phi, Phi_sum):
         """The same map with autograd recording (training: :268-272 of the DEQ wrapper call f with the tape on): the GAP
         projection is the HIP kernel behind an autograd.Function, the denoiser is the PyTorch module itself and the
@@ -84,37 +91,54 @@ class EquilibriumProxGradSCI(nn.Module):
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
-    def device_param_eligibility(self, frozen_bn=False):
-        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility;
-        frozen_bn=True: also a frozen-BatchNorm stack and tag 'ffdnet', vjp.param_eligibility(net, frozen_bn=True))."""
+    def _param_mode(self, frozen_bn, train_bn):
+        """(mode, reason): which DenoiserParamGrads serves the denoiser - "plain", "frozen_bn", "train_bn" - or (None, why not)."""
+        op = self.nonlinear_op
         if not (self.A is A_torch_ and self.At is At_torch_):
-            return False, "custom A / At: the device call uses the HIP GAP projection"
-        ok, why = _vjp.param_eligibility(self.nonlinear_op)
-        if ok or not frozen_bn:
-            return ok, why
-        ok, why = _vjp.param_eligibility(self.nonlinear_op, frozen_bn=True)
-        if ok and isinstance(self.nonlinear_op, _vjp._modules()[1]) and getattr(self.nonlinear_op, "tag", None) != "ffdnet":
-            return False, f"FFDNet under nonlinear_op tag {getattr(self.nonlinear_op, 'tag', None)!r}: it gets its noise level under 'ffdnet' only"
-        return ok, why
+            return None, "custom A / At: the device call uses the HIP GAP projection"
+        ok, why = _vjp.param_eligibility(op)
+        if ok:
+            return "plain", why
+        if not (frozen_bn or train_bn):
+            return None, why
+        ffdnet_tag = isinstance(op, _vjp._modules()[1]) and getattr(op, "tag", None) != "ffdnet"
+        wrong_tag = f"FFDNet under nonlinear_op tag {getattr(op, 'tag', None)!r}: it gets its noise level under 'ffdnet' only"
+        ok, why = _vjp.param_eligibility(op, frozen_bn=True)
+        if ok:
+            return (None, wrong_tag) if ffdnet_tag else ("frozen_bn", why)
+        if not train_bn:
+            return None, why
+        ok, why_train = _vjp.param_eligibility(op, train_bn=True)
+        if ok:
+            return (None, wrong_tag) if ffdnet_tag else ("train_bn", why_train)
+        return None, why if "BatchNorm2d in eval mode" in why_train else why_train
 
-    def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False):
+    def device_param_eligibility(self, frozen_bn=False, train_bn=False):
+        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility;
+        frozen_bn=True: also a frozen-BatchNorm stack and tag 'ffdnet', vjp.param_eligibility(net, frozen_bn=True); train_bn=True: all of
+        that and the same nets with their BatchNorms in train mode, vjp.param_eligibility(net, train_bn=True))."""
+        mode, why = self._param_mode(frozen_bn, train_bn)
+        return mode is not None, why
+
+    def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False, train_bn=False):
         """The taped call f(z) = z1 - D(z1) whose backward forms the denoiser's weight gradients on the HIP kernels: gap_update ->
         autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called.  frozen_bn=True serves
-        what device_param_eligibility(frozen_bn=True) accepts; FFDNet with _forward_taped's sigma bookkeeping."""
-        ok, why = self.device_param_eligibility(frozen_bn)
-        if not ok:
+        what device_param_eligibility(frozen_bn=True) accepts; FFDNet with _forward_taped's sigma bookkeeping.  train_bn=True serves what
+        device_param_eligibility(train_bn=True) accepts: a train-mode BatchNorm normalises by the batch on csrc/bn_train.hip, and the call
+        moves its running buffers once, as the module's own forward would."""
+        mode, why = self._param_mode(frozen_bn, train_bn)
+        if mode is None:
             raise ValueError(f"forward_param_device: {why}")
         bsz, w, h, c = z.shape
         op = self.nonlinear_op
-        bn = frozen_bn and not _vjp.param_eligibility(op)[0]
         z1 = _ag.gap_update(z, y, Phi, Phi_sum)
         zp = z1.permute(0, 3, 1, 2).contiguous()
         self._taped = (zp.detach().view(bsz * c, 1, w, h), None)
         sigma = None
-        if bn and isinstance(op, _vjp._modules()[1]):
+        if mode != "plain" and isinstance(op, _vjp._modules()[1]):
             sigma = self._sigma(y, bsz * c)
             self._taped = (self._taped[0], sigma)
-        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, bn)
+        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, mode == "frozen_bn", mode == "train_bn")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
     def device_vjp_eligibility(self):
@@ -310,8 +334,10 @@ class DEQFixedPoint(nn.Module):
         # how the taped call z = f(z*) forms the denoiser's weight gradients: "autograd" (the torch module on the tape: MIOpen backward) or
         # "device" (EquilibriumProxGradSCI.forward_param_device: csrc/wgrad.hip, falling back to autograd where vjp.param_eligibility
         # refuses), or "device+bn" (everything "device" serves plus a frozen BatchNorm - conv + BN-eval + ReLU DnCNN, FFDNet: csrc/wgrad_bn.hip,
-        # vjp.param_eligibility(net, frozen_bn=True)).  last_parameter_path: the path of the last taped forward ("device" when served);
-        # parameter_fallback_reason: why not.  Independent of implicit_backward.
+        # vjp.param_eligibility(net, frozen_bn=True)), or "device+bn-train" (everything "device+bn" serves plus the same nets with their
+        # BatchNorms in TRAIN mode, as the reference trains them: csrc/bn_train.hip, vjp.param_eligibility(net, train_bn=True)).
+        # last_parameter_path: the path of the last taped forward ("device" when served); parameter_fallback_reason: why not.
+        # Independent of implicit_backward.
         self.parameter_backward = "autograd"
         self.last_parameter_path = None
         self.parameter_fallback_reason = None
@@ -338,6 +364,17 @@ class DEQFixedPoint(nn.Module):
             self._engine = (key, DEQSCIEngine(f.nonlinear_op, **{**cfg, **self.engine_options}))
         return self._engine[1]
 
+    def _train_bn_engine(self):
+        """The engine that runs a training step's no-tape solve: engine_options["train_bn"] == "device", f on the engine's path (not a
+        DataParallel) and a denoiser in train mode that the option serves - else None, and the solve takes the solver as it always did."""
+        if self.engine_options.get("train_bn") != "device" or isinstance(self.f, nn.DataParallel):
+            return None
+        eng = self._engine_for()
+        if eng is None:
+            return None
+        eng.den._refresh()
+        return eng if eng.den.train is not None else None
+
     def _device_map(self, Phi, Phi_sum):
         """implicit_backward = "device": the device map of the taped call just made, or None (autograd) with the reason recorded."""
         if self.implicit_backward not in ("autograd", "device"):
@@ -360,22 +397,24 @@ class DEQFixedPoint(nn.Module):
 
     def _taped_call(self, z, x, Phi, Phi_sum):
         """The taped call z = f(z*) (:268): on the device's weight-gradient path where parameter_backward asks for it and it is served."""
-        if self.parameter_backward not in ("autograd", "device", "device+bn"):
-            raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd', 'device' or 'device+bn'")
+        if self.parameter_backward not in ("autograd", "device", "device+bn", "device+bn-train"):
+            raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd', 'device' or 'device+bn' - or 'device+bn-train', "
+                             "which adds BatchNorm2d in train mode")
         self.parameter_fallback_reason = None
         self.last_parameter_path = "autograd"
         if self.parameter_backward != "autograd":
-            frozen_bn = self.parameter_backward == "device+bn"
+            train_bn = self.parameter_backward == "device+bn-train"
+            frozen_bn = train_bn or self.parameter_backward == "device+bn"
             f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
             if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
                 self.parameter_fallback_reason = "DataParallel over several devices (the taped call runs on replicas)"
             elif not isinstance(f, EquilibriumProxGradSCI):
                 self.parameter_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
             else:
-                ok, why = f.device_param_eligibility(frozen_bn)
+                ok, why = f.device_param_eligibility(frozen_bn, train_bn)
                 if ok:
                     self.last_parameter_path = "device"
-                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn)
+                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn, train_bn)
                 self.parameter_fallback_reason = why
         return self.f(z, x, Phi, Phi_sum)
 
@@ -422,8 +461,18 @@ class DEQFixedPoint(nn.Module):
             if extras:
                 raise NotImplementedError("snapshots / trace exist on the engine's inference path only: this is the taped training forward "
                                           "(pass train_flag=False or run under torch.no_grad())")
-            with torch.no_grad():
-                z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
+            eng = self._train_bn_engine()
+            if eng is not None:
+                # engine_options["train_bn"] = "device": the no-tape solve's f-calls on the engine's "train bn per layer" path
+                # (csrc/bn_train.hip; each moves the BatchNorms' buffers as the module's forward would), sigma from the engine's table
+                z = eng.solve(*_data(x, Phi, Phi_sum), initial_point=init_point.detach())
+                self.forward_res = eng.last_info["res"]
+                if eng.den.tag == "ffdnet":
+                    n_calls = eng.last_info["f_calls"]
+                    self.f._sigma_resume(x, z.shape[0] * z.shape[3], eng.den.sigma_table[n_calls - 1:n_calls])
+            else:
+                with torch.no_grad():
+                    z, self.forward_res = self.solver(lambda z: self.f(z, x, Phi, Phi_sum), init_point, **self.kwargs)
             z = self._taped_call(z, x, Phi, Phi_sum)                           # re-engage the tape (:268)
             z0 = z.clone().detach().requires_grad_()
             f0 = self.f(z0, *_data(x, Phi, Phi_sum))                           # Jacobian-vector products come from this graph

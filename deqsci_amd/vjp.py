@@ -36,6 +36,16 @@ with gm the masked gradient behind the ReLU and R = wgrad(x, gm):
 (sum_p gm c = sum W R: no stored pre-activation and no division by gamma, exact for gamma = 0 and gamma < 0; csrc/wgrad_bn.hip's W0-BN gives
 the three sums from one pass).  FFDNet's edge layers are read through the 2x2 pixel-(un)shuffle by W2 of the same file, sigma's channel of
 the first weight included.  grad_parameters names the parameters, plan_param_grads_frozen_bn is the host statement.
+
+With the BatchNorm in TRAIN mode - what the reference trains: it calls .eval() under --inference only; parameter_backward =
+"device+bn-train", param_eligibility(net, train_bn=True) - the layer is y = relu(gamma xhat + beta), xhat = (c - mean) / sqrt(var + eps) with
+the mean and the biased variance of c = conv(x, W) over the batch's P = n H W pixels, and with gm the masked gradient behind the ReLU:
+
+    dbeta = sum_p gm        dgamma = sum_p gm xhat        dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P)        dW = wgrad(x, dc)
+
+(csrc/bn_train.hip: T1 statistics and the running buffers' update, T2 apply + mask, T3 the two sums, T4 dc; dc goes down through the UNFOLDED
+transposed weight).  The statistic terms reach the pixels the ReLU masked too.  plan_forward_train_bn / plan_param_grads_train_bn are the
+host statements.
 """
 import torch
 import torch.nn.functional as F
@@ -191,9 +201,31 @@ def _bn_refusal(mods):
     return None
 
 
+def _train_bn_refusal(mods):
+    """Why a BatchNorm2d of `mods` is not a train-mode BatchNorm the batch-statistics kernels serve, or None."""
+    for m in mods:
+        if isinstance(m, torch.nn.BatchNorm2d):
+            if not m.training:
+                return 'BatchNorm2d in eval mode (frozen statistics: that is parameter_backward = "device+bn")'
+            if not m.affine or m.weight is None or m.bias is None:
+                return "BatchNorm2d without affine parameters (affine=False)"
+            if not m.track_running_stats or m.running_mean is None or m.running_var is None or m.num_batches_tracked is None:
+                return "BatchNorm2d without running statistics (track_running_stats=False: the kernels update them)"
+            if m.momentum is None:
+                return "BatchNorm2d with momentum=None (the cumulative moving average has no device kernel)"
+            if isinstance(m.momentum, bool) or not isinstance(m.momentum, float):
+                return f"BatchNorm2d with momentum={m.momentum!r}: a float is required"
+    return None
+
+
 def _frozen_bn_stack(net):
     """(stack, ffdnet, reason): layers.conv_bn_stack of a net the frozen-BatchNorm weight gradients serve - [(conv, bn or None, relu)] and
     whether its edge layers are FFDNet's - or (None, None, why not)."""
+    return _bn_stack(net, False)
+
+
+def _bn_stack(net, train):
+    """_frozen_bn_stack (train=False), or the same for a net whose BatchNorms are in train mode (train=True)."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     ffdnet = isinstance(net, FFDNet)
     if ffdnet:
@@ -208,10 +240,10 @@ def _frozen_bn_stack(net):
         mods = list(net.dncnn)
     if any(isinstance(m, RealSNConv2d) for m in mods):
         return None, None, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
-    why = _bn_refusal(mods)
+    why = _train_bn_refusal(mods) if train else _bn_refusal(mods)
     if why is not None:
         return None, None, ("FFDNet: " if ffdnet else "") + why
-    stack, why = conv_bn_stack(mods)
+    stack, why = conv_bn_stack(mods, train_bn=train)
     if stack is None:
         return None, None, why
     shapes = [tuple(c.weight.shape) for c, _, _ in stack]
@@ -227,12 +259,23 @@ def _frozen_bn_stack(net):
     return stack, ffdnet, None
 
 
-def param_eligibility(net, frozen_bn=False):
+_TRAIN_BN_OK, _TRAIN_FFDNET_OK = "bias-free conv [+ train-mode BN] + ReLU stack", "FFDNet with its BatchNorm in train mode"
+
+
+def param_eligibility(net, frozen_bn=False, train_bn=False):
     """(ok, reason): whether DenoiserParamGrads (and DEQFixedPoint.parameter_backward = "device") can form the weight gradients of `net`:
     a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0,
     no_bn=True) of any depth >= 2.  frozen_bn=True (parameter_backward = "device+bn") accepts in addition an eval-mode affine BatchNorm2d
     with running statistics behind every 64 -> 64 conv - DnCNN(..., no_bn=False).eval() - and the grayscale FFDNet with its BatchNorms in
-    eval mode.  CPU-safe."""
+    eval mode.  train_bn=True (parameter_backward = "device+bn-train") accepts those two families with their BatchNorms in TRAIN mode -
+    affine, with running statistics and a float momentum (csrc/bn_train.hip) - and refuses an eval-mode BatchNorm.  CPU-safe."""
+    if train_bn:
+        if frozen_bn:
+            raise ValueError("param_eligibility: frozen_bn and train_bn exclude one another")
+        stack, ffdnet, why = _bn_stack(net, True)
+        if stack is None:
+            return False, why
+        return True, _TRAIN_FFDNET_OK if ffdnet else _TRAIN_BN_OK
     if frozen_bn:
         stack, ffdnet, why = _frozen_bn_stack(net)
         if stack is None:
@@ -268,10 +311,11 @@ def conv_weights(net):
     return [m.weight for m in net.dncnn if isinstance(m, torch.nn.Conv2d)]
 
 
-def grad_parameters(net):
+def grad_parameters(net, train_bn=False):
     """The nn.Parameters of a net param_eligibility(net, frozen_bn=True) accepts, in module order - per layer the conv weight, then its
-    BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for."""
-    stack, _, why = _frozen_bn_stack(net)
+    BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for.  train_bn=True:
+    the same for a net param_eligibility(net, train_bn=True) accepts."""
+    stack, _, why = _bn_stack(net, bool(train_bn))
     if stack is None:
         raise ValueError(f"grad_parameters: {why}")
     out = []
@@ -338,6 +382,99 @@ def plan_param_grads_frozen_bn(net, x, v, sigma=None, masks=None):
             if used[i - 1] is not None:
                 g = g * used[i - 1]
     return [t for layer in per_layer for t in layer], used
+
+
+# ----------------------------------------------------------------------------- BatchNorm in train mode: the host statements
+def _train_bn_walk(who, net, x, sigma, masks, update):
+    """One train-mode forward of a net param_eligibility(net, train_bn=True) accepts, in x's dtype.  -> (stack, ffdnet, noise, tape), tape =
+    per layer but the last (input, c, xhat or None, 1 / sqrt(var + eps) or None, mask or None), then the last layer's input."""
+    stack, ffdnet, why = _bn_stack(net, True)
+    if stack is None:
+        raise ValueError(f"{who}: {why}")
+    T = lambda p: p.detach().to(x)
+    if ffdnet:
+        _even(x, who)
+        if sigma is None:
+            raise ValueError(f"{who}: FFDNet is evaluated at a noise level: sigma is required")
+        h = torch.cat((_sigma_map(sigma, x), F.pixel_unshuffle(x, 2)), 1)
+    else:
+        h = x
+    tape = []
+    for i, (conv, bn, relu) in enumerate(stack[:-1]):
+        c = F.conv2d(h, T(conv.weight), padding=1)
+        xhat = inv = None
+        y = c
+        if bn is not None:
+            P = c.numel() // c.shape[1]
+            if P < 2:
+                raise ValueError(f"{who}: expected more than 1 value per channel when training, got input size {list(c.shape)}")
+            mean, var = c.mean((0, 2, 3)), c.var((0, 2, 3), unbiased=False)
+            inv = 1.0 / torch.sqrt(var + bn.eps)
+            xhat = (c - mean.view(1, -1, 1, 1)) * inv.view(1, -1, 1, 1)
+            y = xhat * T(bn.weight).view(1, -1, 1, 1) + T(bn.bias).view(1, -1, 1, 1)
+            if update:
+                with torch.no_grad():
+                    m = bn.momentum
+                    bn.running_mean.copy_((1.0 - m) * bn.running_mean.to(mean) + m * mean)
+                    bn.running_var.copy_((1.0 - m) * bn.running_var.to(var) + m * (var * (P / (P - 1))))
+                    bn.num_batches_tracked += 1
+        m = (masks[i] if masks is not None else y > 0) if relu else None
+        tape.append((h, c, xhat, inv, m))
+        h = y if m is None else y * m
+    tape.append(h)
+    noise = F.conv2d(h, T(stack[-1][0].weight), padding=1)
+    return stack, ffdnet, (F.pixel_shuffle(noise, 2) if ffdnet else noise), tape
+
+
+def plan_forward_train_bn(net, x, sigma=None, update=True):
+    """One train-mode forward of a net param_eligibility(net, train_bn=True) accepts, restated in x's dtype: per BatchNorm layer the mean and
+    the biased variance of c = conv(x, W) over the batch, y = gamma (c - mean) / sqrt(var + eps) + beta, the ReLU; FFDNet at the noise level
+    sigma through its pixel-(un)shuffle.  update=True moves the module's buffers as torch does: running_mean <- (1 - m) running_mean + m mean,
+    running_var <- (1 - m) running_var + m var P / (P - 1), num_batches_tracked += 1.  -> (noise, masks)."""
+    _, _, noise, tape = _train_bn_walk("plan_forward_train_bn", net, x, sigma, None, update)
+    return noise, [t[4] for t in tape[:-1]]
+
+
+def _train_bn_backward(stack, ffdnet, tape, v):
+    """The walk back of plan_param_grads_train_bn.  -> (gradients in grad_parameters order, the input gradient or None for FFDNet)."""
+    T = lambda p: p.detach().to(v)
+    per_layer = [None] * len(stack)
+    dc = F.pixel_unshuffle(v, 2) if ffdnet else v
+    for i in range(len(stack) - 1, -1, -1):
+        conv, bn, _ = stack[i]
+        W = T(conv.weight)
+        inp = tape[i] if i == len(stack) - 1 else tape[i][0]
+        if i < len(stack) - 1:
+            _, c, xhat, inv, m = tape[i]
+            gm = g if m is None else g * m
+            if bn is None:
+                per_layer[i], dc = [None], gm
+            else:
+                P = c.numel() // c.shape[1]
+                dbeta, dgamma = gm.sum((0, 2, 3)), (gm * xhat).sum((0, 2, 3))
+                dc = (T(bn.weight) * inv).view(1, -1, 1, 1) * (gm - (dbeta / P).view(1, -1, 1, 1) - xhat * (dgamma / P).view(1, -1, 1, 1))
+                per_layer[i] = [None, dgamma, dbeta]
+        else:
+            per_layer[i] = [None]
+        per_layer[i][0] = torch.nn.grad.conv2d_weight(inp, W.shape, dc, padding=1)
+        if i > 0:
+            g = F.conv2d(dc, _transposed(W), padding=1)
+    gx = None if ffdnet else F.conv2d(dc, _transposed(T(stack[0][0].weight)), padding=1)
+    return [t for layer in per_layer for t in layer], gx
+
+
+def plan_param_grads_train_bn(net, x, v, sigma=None, masks=None, input_grad=False):
+    """(dD/dtheta)^T v of a net param_eligibility(net, train_bn=True) accepts, at x, in x's dtype - the host statement of what
+    DenoiserParamGrads(..., train_bn=True).grads runs: one train-mode forward (plan_forward_train_bn's, the buffers left alone) keeps each
+    layer's input, c and xhat; walking back, per layer with a BatchNorm and gm the gradient masked by its ReLU: dbeta = sum gm,
+    dgamma = sum gm xhat, dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P), dW = conv2d_weight(input, dc), and dc goes down
+    through the UNFOLDED transposed weight.  masks: those of another forward pass (the device's, unpack_masks).  Returns (gradients in
+    grad_parameters(net, train_bn=True) order, masks) - with input_grad=True (gradients, masks, J_D(x)^T v: the true input product,
+    statistic terms included; None for FFDNet, which detaches its input)."""
+    stack, ffdnet, _, tape = _train_bn_walk("plan_param_grads_train_bn", net, x, sigma, masks, False)
+    grads, gx = _train_bn_backward(stack, ffdnet, tape, v)
+    used = [t[4] for t in tape[:-1]]
+    return (grads, used, gx) if input_grad else (grads, used)
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
@@ -540,9 +677,23 @@ class DenoiserParamGrads:
     _MaskedStack; .grads answers for grad_parameters(net) in its order (per layer dW, then dgamma, dbeta) and `need` has one bool per
     parameter.  A 64 -> 64 layer with a BatchNorm runs csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass).
     FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
-    ffdnet_tail's, and .vjp is zero: its input is detached."""
+    ffdnet_tail's, and .vjp is zero: its input is detached.
 
-    def __init__(self, net, x, sigma=None, frozen_bn=False):
+    train_bn=True: the nets param_eligibility(net, train_bn=True) accepts - the BatchNorms in TRAIN mode, as the reference trains them.  The
+    forward runs per layer the raw convolution (Winograd F(2x2,3x3), no bias, no ReLU), csrc/bn_train.hip's T1 (batch statistics; the
+    module's running_mean / running_var / num_batches_tracked are updated IN PLACE on the device, exactly once per construction) and T2
+    (normalise + ReLU + the mask words in one pass), and keeps per BatchNorm layer the convolution output c AND the post-ReLU activation:
+    (2 (k-2) + 1) n 64 H W 4 bytes for k layers (FFDNet: 27 activations at half resolution), twice the frozen mode's.  .grads answers for
+    grad_parameters(net, train_bn=True): T3 (dgamma, dbeta) -> T4 (dc, in place) -> W0 on dc -> the masked transposed Winograd layer with
+    the plain (unfolded) transposed weight.  .vjp(v) is the true input product, the statistic terms included (FFDNet: zero)."""
+
+    def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False):
+        self._train = None
+        if train_bn:
+            if frozen_bn:
+                raise ValueError("DenoiserParamGrads: frozen_bn and train_bn exclude one another")
+            self._init_train_bn(net, x, sigma)
+            return
         ok, why = param_eligibility(net, frozen_bn=frozen_bn)
         if not ok:
             raise ValueError(f"DenoiserParamGrads: {why}")
@@ -588,9 +739,104 @@ class DenoiserParamGrads:
             raise _hip.DeqsciHipError(f"DenoiserParamGrads.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
         return _hip.f32c(v)
 
+    def _init_train_bn(self, net, x, sigma):
+        stack, ffdnet, why = _bn_stack(net, True)
+        if stack is None:
+            raise ValueError(f"DenoiserParamGrads: {why}")
+        self.shape = _image(x, "DenoiserParamGrads")
+        self._x = _hip.f32c(x.detach())
+        n, _, H, W = self.shape
+        self.ffdnet, self._sigma = ffdnet, None
+        if ffdnet:
+            _even(x, "DenoiserParamGrads")
+            if sigma is None:
+                raise ValueError("DenoiserParamGrads: FFDNet is evaluated at a noise level: sigma is required")
+            self._sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1)
+            if self._sigma.numel() not in (1, n):
+                raise ValueError(f"DenoiserParamGrads: sigma must have 1 or {n} elements, got {self._sigma.numel()}")
+            if self._sigma.numel() > 1 and self._sigma.stride(0) not in (0, 1):
+                self._sigma = self._sigma.contiguous()
+            H, W = H // 2, W // 2
+        if n * H * W < 2:
+            raise ValueError(f"DenoiserParamGrads: expected more than 1 value per channel when training, got {n * H * W}")
+        dev = lambda t: t.detach().to(x.device, torch.float32).contiguous()
+        t = self._train = type("_TrainBN", (), {})()
+        with torch.no_grad():
+            w0, wt = dev(stack[0][0].weight), dev(stack[-1][0].weight)
+            if ffdnet:
+                t.tail_f, t.tail_t, t.head_t = _hip.pack_tail_weights(wt), _hip.pack_head_masked_weights(_transposed(wt)), None
+                h = _hip.ffdnet_head(self._x, _hip.pack_head_weights(w0), self._sigma)
+            else:
+                t.tail_f, t.tail_t = _hip.pack_c64_to_1_weights(wt), _hip.pack_c1_to_64_weights(_transposed(wt))
+                t.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
+                h = _hip.conv3x3_c1_to_64(self._x, _hip.pack_c1_to_64_weights(w0), relu=True)
+            t.ws = _hip.bn_train_workspace(n * H * W, x.device)
+            self.masks, t.acts, t.layers = [_hip.relu_mask_pack(h)], [h], []        # layers[i - 1] of 64 -> 64 layer i: (transposed pack, bn state)
+            for conv, bn, _ in stack[1:-1]:
+                w = dev(conv.weight)
+                u, ut = _hip.pack_winograd_weights(w), _hip.pack_winograd_weights(_transposed(w))
+                if bn is None:
+                    h = _hip.conv3x3_c64_winograd(h, u, None, True)
+                    self.masks.append(_hip.relu_mask_pack(h))
+                    t.layers.append((ut, None))
+                else:
+                    c = _hip.conv3x3_c64_winograd(h, u, None, False)
+                    rec = _hip.bn_train_stats(c, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, workspace=t.ws)
+                    gamma = dev(bn.weight)
+                    h, mk = _hip.bn_train_apply(c, rec, gamma, dev(bn.bias), bn.eps, relu=True, want_mask=True)
+                    self.masks.append(mk)
+                    t.layers.append((ut, (c, rec, gamma, float(bn.eps))))
+                t.acts.append(h)
+            self.noise = (_hip.ffdnet_tail if ffdnet else _hip.conv3x3_c64_to_1)(h, t.tail_f)
+        self._ws = _hip.wgrad_workspace(n, H, W, x.device)
+        self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, x.device) if ffdnet else None
+
+    def _walk_train_bn(self, v, need, want_input):
+        """The walk back in train mode: (gradients in grad_parameters(net, train_bn=True) order - None where not needed, the input product or None)."""
+        t = self._train
+        if t.acts is None:
+            raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
+        k = len(t.layers) + 2
+        counts = [1] + [1 if bn is None else 3 for _, bn in t.layers] + [1]
+        first = [sum(counts[:i]) for i in range(k)]
+        total = sum(counts)
+        need = [False] * total if need is None else [bool(b) for b in need]
+        if len(need) != total:
+            raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {total} parameters")
+        out = [None] * total
+        if not any(need) and not want_input:
+            return out, None
+        wanted = [any(need[first[i]:first[i] + counts[i]]) for i in range(k)]
+        lowest = -1 if want_input else wanted.index(True)
+        if wanted[k - 1]:
+            out[first[k - 1]] = (_hip.wgrad_shuffle(v, t.acts[-1], 1, None, self._ws_bn) if self.ffdnet
+                                 else _hip.wgrad_c1_c64(v, t.acts[-1], 1, self._ws))
+        if lowest == k - 1:
+            return out, None
+        g = (_hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked)(v, t.tail_t, self.masks[-1])
+        for i in range(k - 2, 0, -1):
+            ut, bn = t.layers[i - 1]
+            got = [None] * counts[i]
+            if bn is not None:
+                c, rec, gamma, eps = bn
+                got[1], got[2], grec = _hip.bn_train_grad_stats(g, c, rec, eps, t.ws)
+                g = _hip.bn_train_grad_apply(g, c, rec, grec, gamma, eps, out=g)         # dc, statistic terms included, in place
+            if need[first[i]]:
+                got[0] = _hip.wgrad_c64_c64(t.acts[i - 1], g, self._ws)
+            for j, tensor in enumerate(got):
+                out[first[i] + j] = tensor if need[first[i] + j] else None
+            if i == lowest:
+                return out, None
+            g = _hip.conv3x3_c64_winograd_masked(g, ut, self.masks[i - 1])
+        if need[0]:
+            out[0] = _hip.wgrad_shuffle(self._x, g, 0, self._sigma, self._ws_bn) if self.ffdnet else _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
+        return out, (_hip.conv3x3_c64_to_1(g, t.head_t) if want_input else None)
+
     def vjp(self, v):
         v = self._v(v, "vjp")
-        return torch.zeros_like(v) if self.ffdnet else self._stack.vjp(v)
+        if self.ffdnet:
+            return torch.zeros_like(v)
+        return self._walk_train_bn(v, None, True)[1] if self._train is not None else self._stack.vjp(v)
 
     def _middle(self, i, g):
         """[dW] of 64 -> 64 layer i, or [dW, dgamma, dbeta] where it has a BatchNorm, from its input and the masked gradient g behind it."""
@@ -603,6 +849,9 @@ class DenoiserParamGrads:
         return [dw, ((ddot.double() - mean * dsum.double()) * inv).float(), dsum]
 
     def grads(self, v, need=None):
+        if self._train is not None:
+            total = 2 + sum(1 if bn is None else 3 for _, bn in self._train.layers)
+            return self._walk_train_bn(self._v(v, "grads"), [True] * total if need is None else need, False)[0]
         st = self._stack
         if st.acts is None:
             raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
@@ -637,4 +886,8 @@ class DenoiserParamGrads:
         return out
 
     def release(self):
-        self._stack.acts = None
+        if self._train is not None:
+            self._train.acts = None
+            self._train.layers = [(ut, None if bn is None else (None,) + bn[1:]) for ut, bn in self._train.layers]
+        else:
+            self._stack.acts = None

@@ -580,6 +580,43 @@ int deqsci_realsn_power_f32(const float* W, float* u, float* v, float* weight, d
 int deqsci_realsn_grad_f32(const float* G, const float* W, const float* u, const float* v, const double* record, float* dW, float sigma_t,
                            int64_t C_in, int64_t C_out, int64_t h, int64_t w, void* workspace, deqsci_stream_t stream);
 
+/* ---- BatchNorm2d in TRAIN mode behind a 64 -> 64 convolution (csrc/bn_train.hip): batch statistics, normalisation and their backward on the
+ * fp32 channels_last activation (P, 64), P = n H W pixels.  A workgroup owns a fixed run of pixels (DEQSCI_BN_TRAIN_CHUNK, or
+ * ceil(P / DEQSCI_BN_TRAIN_MAX_WG) rounded up to 16 where that is more), a thread sums its pixels in float64, the workgroup folds them in a
+ * fixed order into one float64 partial, and a closing launch sums the partials in a fixed order: no atomics, bit-equal run to run.
+ * record = double[128]: the batch mean [0, 64) and the BIASED batch variance [64, 128);  grad_record = double[128]: dbeta, then dgamma.
+ * T1 stats       mean = sum(c) / P;  var = sum((c - mean)^2) / P from a second, centred pass (it keeps its digits under any offset of c).
+ *                The closing launch applies torch's update in float64, rounded once: running_mean = (1 - momentum) running_mean +
+ *                momentum mean,  running_var = (1 - momentum) running_var + momentum var P / (P - 1),  *num_batches_tracked += 1.
+ *                The three buffer pointers may ALL be NULL (no update; some but not all: -1).  4 launches.
+ * T2 apply       per channel, float64: inv = 1 / sqrt(var + eps), a = gamma * inv;  per element
+ *                    y = (float) fma(a, (double)c - mean, (double)beta)      (one fused multiply-add, rounded once to fp32)
+ *                then max(y, 0) where relu = 1 (a NaN stays a NaN).  y may BE c.  mask (NULL: skipped): one word per pixel in
+ *                deqsci_relu_mask_pack_f32's format, bit ch = (y > 0), written in the same pass.  1 launch.
+ * T3 grad stats  gy = the gradient behind the layer, already masked by its ReLU; c the stored convolution output.  float64 products and sums:
+ *                    dbeta = sum gy,   dgamma = inv * sum gy * ((double)c - mean)
+ *                kept in grad_record for T4 and rounded once to the fp32 outputs dgamma[64], dbeta[64].  2 launches.
+ * T4 grad apply  per channel, float64: k1 = dbeta / P,  k2 = dgamma * inv / P,  a = gamma * inv;  per element
+ *                    dc = (float)(a * (((double)gy - k1) - ((double)c - mean) * k2))
+ *                (every operation rounded in float64, the result once to fp32).  dc may BE gy.  A pixel the ReLU masked (gy = 0) still
+ *                receives the two statistic terms.  1 launch.
+ * c, gy, y, dc 16-byte aligned; records, the workspace and num_batches_tracked 8-byte, the rest 4-byte.  workspace =
+ * deqsci_bn_train_workspace_bytes(P) bytes (0 for P < 2 or P >= 2^31; T1 and T3), no initialisation needed.  No allocation, no host
+ * synchronisation, graph-capturable.  P = 0 launches nothing and returns 0.  NULL -> -1;  P < 0, P = 1 (torch: "Expected more than 1 value
+ * per channel when training"), P >= 2^31 -> -2;  misaligned -> -3;  an output or the workspace overlapping an input or another output
+ * (other than y == c, dc == gy), relu other than 0 / 1 -> -4. */
+#define DEQSCI_BN_TRAIN_CHUNK 128
+#define DEQSCI_BN_TRAIN_MAX_WG 1024
+size_t deqsci_bn_train_workspace_bytes(int64_t P);
+int deqsci_bn_train_stats_f32(const float* c, double* record, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                              double momentum, int64_t P, void* workspace, deqsci_stream_t stream);
+int deqsci_bn_train_apply_f32(const float* c, const double* record, const float* gamma, const float* beta, double eps, float* y,
+                              uint64_t* mask, int relu, int64_t P, deqsci_stream_t stream);
+int deqsci_bn_train_grad_stats_f32(const float* gy, const float* c, const double* record, double eps, double* grad_record, float* dgamma,
+                                   float* dbeta, int64_t P, void* workspace, deqsci_stream_t stream);
+int deqsci_bn_train_grad_apply_f32(const float* gy, const float* c, const double* record, const double* grad_record, const float* gamma,
+                                   double eps, float* dc, int64_t P, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
