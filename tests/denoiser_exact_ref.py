@@ -1,5 +1,7 @@
-"""The denoiser's forward kernels element by element, stated once for tests/test_denoiser_exact_host.py (this helper against itself and
-CPU fp32) and tests/test_denoiser_exact_gpu.py (the kernels).  A helper module, not a test.  Shapes and seams: tests/nonfinite_ref.py.
+"""The denoiser's forward kernels, and the masked kernels its backward and Jacobian products run through, element by element: stated
+once for tests/test_denoiser_exact_host.py (this helper against itself and CPU fp32), tests/test_denoiser_exact_gpu.py (the forward
+kernels) and tests/test_backward_exact_gpu.py (the masked kernels, the transposed packs vjp._MaskedStack builds, one whole masked
+stack).  A helper module, not a test.  Shapes and seams: tests/nonfinite_ref.py.
 
 (a) EXACT.  Integer operands - x in [-8, 8] with a seeded quarter exactly 0, weights in [-4, 4] without 0 (times KERNELS[k]["wmult"]
     where a transform divides), integer bias and sigma - make every product and every partial sum of a kernel an integer (or one
@@ -18,14 +20,20 @@ CPU fp32) and tests/test_denoiser_exact_gpu.py (the kernels).  A helper module, 
     lo . lo product is dropped (<= 2^-22 |x| |w|): rep = (3 2^-22 S + floors)(1 + 2^-10), the last factor for the products of two errors.
     An sp16 OUTPUT adds its own split: 2^-22 |y| + 2^(-25 - e_out).  No atol, nothing fitted.
 (c) GUARDS.  Arena: every operand a view inside a buffer of NaN, every output a view pre-filled with NaN inside a buffer of sentinels;
-    guards of at least two image rows of 64 channels, a multiple of 256 bytes."""
+    guards of at least two image rows of 64 channels, a multiple of 256 bytes.
+A MASKED kernel is the unmasked sum behind a select (mask ? v : 0; nonfinite_ref.conv_ref(mask=)): (a) on the same integer data under a
+mask drawn on the CPU (mask_bits; check_masked_caps keeps it from passing vacuously), (b) the unmasked kernel's c 2^-24 S times the mask -
+an element under a cleared bit must equal 0 -, (c) with the int64 mask words inside guard words that are all ones in the case's first
+launch and all zeros in its second (Arena.words)."""
 import functools
+import itertools
 import math
 
 import torch
 import torch.nn.functional as Fn
 
 import nonfinite_ref as nf
+from deqsci_amd import vjp as _vjp
 
 U = 2.0 ** -24
 SENTINEL = -7776.0                # (a multiple of 4: the same number in fp16)
@@ -76,12 +84,21 @@ KERNELS = {
                      c="2*3*64 + 9"),
     # f32_to_split16: held to the representation rule directly (no sum: c = 0)
     "to_split16": dict(symbols=("deqsci_f32_to_split16",), nf=("s16",), wino=None, wmult=1, exact=True, split=True, c="0"),
+    # ---- the masked kernels of the backward and of the Jacobian products (tests/test_backward_exact_gpu.py): y = mask ? conv : 0, no bias,
+    # no ReLU; the select rounds nothing, so c is the sum's alone
+    # csrc/winograd.hip winograd_conv64_body<MASK = 1>: the same body as "f22" - transform() 2 additions deep, U rounded once by
+    # pack_winograd_weights, 64 products on v_mfma_f32_16x16x4_f32 (from zero: no bias), epilogue (m0+m1)+m2 twice: 4
+    "f22_masked": dict(symbols=("deqsci_conv3x3_c64_winograd_masked_f32",), nf=("f22",), wino=(2, 2), wmult=4, exact=True,
+                       c="2 + 1 + 2*64 + 4"),
+    # csrc/ffdnet_edges.hip conv_c1_to_64_kernel<3>: nine fma4 from zero
+    "c1_to_64_masked": dict(symbols=("deqsci_conv3x3_c1_to_64_masked_f32",), nf=("c1_to_64",), wino=None, wmult=1, exact=True, c="9"),
+    # csrc/jacobian.hip ffdnet_head_masked_kernel<16 | 32>: 6 patch rows x 6 patch columns = 4 channels x 9 taps, each one v_pk_fma_f32
+    # per register pair, from zero (no sigma plane)
+    "head_masked": dict(symbols=("deqsci_ffdnet_head_masked_f32",), nf=("head_valu",), wino=None, wmult=1, exact=True, c="36"),
 }
+MASKED = ("f22_masked", "c1_to_64_masked", "head_masked")
 # forward denoiser entries of _hip.SIGNATURES that this table leaves out, and why (tests/test_denoiser_exact_host.py: no other may be missing)
 OUT_OF_SCOPE = {
-    "deqsci_conv3x3_c64_winograd_masked_f32": "masked: held by the vjp / jacobian tests",
-    "deqsci_conv3x3_c1_to_64_masked_f32": "masked: held by the vjp / jacobian tests",
-    "deqsci_ffdnet_head_masked_f32": "masked: held by the vjp / jacobian tests",
     "deqsci_conv3x3_c64_split16_stack": "stack launch: held bit for bit to per-layer launches",
     "deqsci_conv3x3_c64_wino16_stack": "stack launch: held bit for bit to per-layer launches",
     "deqsci_conv3x3_c64_winograd_timed_f32": "the same kernel and arguments as deqsci_conv3x3_c64_winograd_f32 between two events",
@@ -100,12 +117,15 @@ def c_of(kernel, in_bias=False):
 
 
 def shapes_of(kernel):
-    """name -> (n, H, W) of the grid the kernel tiles: nonfinite_ref's, and for a 64 -> 64 kernel one pixel and the many-tile launch."""
+    """name -> (n, H, W) of the grid the kernel tiles: nonfinite_ref's, and for a 64 -> 64 kernel one pixel and the many-tile launch;
+    the masked head: one position (a 2 x 2 image), and the smallest ragged launch of its 32 x 32 form (the matrix-core head's threshold)."""
     out = {name: nf.CASES[name]["shape"] for name in KERNELS[kernel]["nf"]}
-    if kernel in CONV64:
+    if kernel in CONV64 or kernel == "f22_masked":
         out.update(one=ONE, many=MANY)
     if kernel == "head_mfma":
         out["head_mfma_ragged"] = HEAD_MFMA_RAGGED
+    if kernel == "head_masked":
+        out.update(one=ONE, head_masked_ragged=HEAD_MFMA_RAGGED)
     return out
 
 
@@ -202,6 +222,162 @@ def tail_data(shape, mode, cout, in_bias, measured):
         b = torch.randn((64,), generator=g) * 0.3
     h = h * image_scales(n, measured).view(-1, 1, 1, 1)
     return h, w, (b if in_bias else None)
+
+
+# ----------------------------------------------------------------------------- the masked kernels: operands, masks, reference, S
+MASK_FORMS = ("random", "checker")
+
+
+@functools.lru_cache(maxsize=None)
+def mask_bits(shape, form, k=None):
+    """bool (k, 64, H, W), drawn on the CPU (k distinct images of a launch that repeats them; None: the shape's n).  "random": every bit
+    independent, p = 1/2.  "checker": pixels of even (row + column) hold a word with only bits 0..31 set, the others only bits 32..63 -
+    a swapped half-word, or the word of a neighbouring pixel, changes whole half-pixels."""
+    n, H, W = shape
+    k = n if k is None else k
+    if form == "random":
+        return torch.rand((k, 64, H, W), generator=_gen(4000 + 7 * H + W)) < 0.5
+    assert form == "checker"
+    even = ((torch.arange(H).view(H, 1) + torch.arange(W).view(1, W)) % 2 == 0).view(1, 1, H, W)
+    low = (torch.arange(64) < 32).view(1, 64, 1, 1)
+    return (even == low).expand(k, 64, H, W).contiguous()
+
+
+def masked_bits(kernel, shape, form):
+    """The mask of a masked case: one image of bits per distinct image of its operand."""
+    return mask_bits(shape, form, masked_operands(kernel, shape, "int", False)[0].shape[0])
+
+
+def mask_guard_fills():
+    """The guard words of the two launches of a masked case (Arena.words): all ones, then all zeros (and so on)."""
+    return itertools.cycle((-1, 0))
+
+
+@functools.lru_cache(maxsize=None)
+def masked_operands(kernel, shape, mode, transposed):
+    """(x, w) of a masked case.  x: the unmasked kernel's own drawn operand - (n,64,H,W), (n,1,H,W), or the masked head's (k,1,2H,2W).  w:
+    the drawn forward weight ((64,64,3,3), (64,1,3,3), (64,4,3,3) = FFDNet's first layer without sigma's channel), or with transposed
+    what the backward launches: vjp._transposed of a weight in the shape of the layer it transposes ((64,64,3,3), the last layers'
+    (1,64,3,3) and (4,64,3,3))."""
+    n, H, W = shape
+    wmult = KERNELS[kernel]["wmult"] if mode == "int" else 1
+    if kernel == "f22_masked":
+        x, w, _, _ = conv64_data(shape, mode, wmult, False, False)
+        return x, (_vjp._transposed(w) if transposed else w)
+    cin = 1 if kernel == "c1_to_64_masked" else 5
+    x, _, w = head_data(shape, mode, cin, False)
+    if not transposed:
+        return x, (w if cin == 1 else w[:, 1:5].contiguous())
+    g = _gen(5000 + 7 * H + W + cin)
+    last = (1 if cin == 1 else 4, 64, 3, 3)
+    wt = _ints(last, -4, 4, g, nonzero=True) if mode == "int" else torch.randn(last, generator=g) * 0.05
+    return x, _vjp._transposed(wt)
+
+
+def masked_input(kernel, x):
+    """What a masked kernel convolves, float64: the activation, the image, or the masked head's four unshuffled channels."""
+    return Fn.pixel_unshuffle(x.double(), 2) if kernel == "head_masked" else x.double()
+
+
+@functools.lru_cache(maxsize=None)
+def masked_unmasked_ref(kernel, shape, mode, transposed):
+    """The float64 convolution WITHOUT the mask (k distinct images), formed once per case: the caps need it, and (a)'s reference is its select."""
+    x, w = masked_operands(kernel, shape, mode, transposed)
+    return nf.ffdnet_head_ref(x, None, w, relu=False, with_sigma=False) if kernel == "head_masked" else nf.conv_ref(x, w)
+
+
+def masked_ref(kernel, shape, mode, transposed, form):
+    """nonfinite_ref's masked reference itself (a select: an element under a cleared bit is 0), k distinct images."""
+    x, w = masked_operands(kernel, shape, mode, transposed)
+    bits = masked_bits(kernel, shape, form)
+    if kernel == "head_masked":
+        return nf.ffdnet_head_ref(x, None, w, relu=False, mask=bits, with_sigma=False)
+    return nf.conv_ref(x, w, mask=bits)
+
+
+@functools.lru_cache(maxsize=None)
+def masked_S(kernel, shape, transposed):
+    """S of the real data: the unmasked kernel's own (the propagation of F(2x2,3x3), or the direct sum)."""
+    x, w = masked_operands(kernel, shape, "real", transposed)
+    xa = masked_input(kernel, x).abs()
+    return s_wino(xa, w.abs(), KERNELS[kernel]["wino"]) if KERNELS[kernel]["wino"] else s_plain(xa, w.abs())
+
+
+def masked_bound(kernel, shape, transposed, form):
+    """(b) of a masked kernel: the unmasked kernel's c 2^-24 S times the mask - an element under a cleared bit must EQUAL 0."""
+    return c_of(kernel) * U * masked_S(kernel, shape, transposed) * masked_bits(kernel, shape, form)
+
+
+def check_masked_caps(unmasked, bits, what, one_pixel=False):
+    """(a) of a masked kernel cannot pass vacuously: magnitudes below 2^24; the unmasked integer reference non-zero on at least a quarter
+    of ALL elements under a set bit, and on a quarter of all elements under a cleared bit (a kernel that ignores the mask fails); every
+    output channel of every image with a non-zero reference element under a set bit.  One pixel: the magnitude alone."""
+    assert float(unmasked.abs().max()) < 2.0 ** 24, what
+    if one_pixel:
+        return None
+    live = unmasked != 0
+    kept, cleared = float((live & bits).double().mean()), float((live & ~bits).double().mean())
+    assert kept >= 0.25 and cleared >= 0.25, (what, kept, cleared)
+    n, C = unmasked.shape[:2]
+    assert bool((live & bits).reshape(n, C, -1).any(-1).all()), (what, "a channel of an image has no non-zero element under a set bit")
+    return kept, cleared
+
+
+def mask_fault(got, unmasked, bits):
+    """What a masked kernel did to its mask, read from the zero pattern of its output alone (so it serves (a) and (b)): None when every
+    element is zero exactly where the select says, else every one of these readings of the mask that explains ALL misplaced zeros -
+    the two 32-bit halves of the word swapped, the word of a neighbouring pixel (the checker mask cannot tell these two apart, the
+    random one can), the mask ignored - or that none of them does.  All three tensors (n,64,H,W) on one device."""
+    live = unmasked != 0
+    z = got != 0
+    bad = (z != (bits & live)) & torch.isfinite(got)          # (an element never written, or NaN, is no reading of the mask: hold() names it)
+    if not bool(bad.any()):
+        return None
+    readings = [("the two 32-bit halves of the mask word swapped (channel c under bit c ^ 32)", bits.roll(32, 1))]
+    for dy, dx_ in ((0, -1), (-1, 0), (-1, -1), (0, 1), (1, 0), (1, 1)):
+        readings.append((f"the word of the pixel at (row {dy:+d}, column {dx_:+d}) taken for this one", bits.roll((-dy, -dx_), (2, 3))))
+    readings.append(("the mask ignored: elements under a cleared bit were kept", torch.ones_like(bits)))
+    names = [name for name, alt in readings if bool(((alt & live) == z)[bad].all())]
+    if names:
+        return f"{int(bad.sum())} elements zero / non-zero against the mask: " + ", or ".join(names)
+    return f"{int(bad.sum())} elements zero / non-zero against the mask, by no single mislaid word (first at {tuple(bad.nonzero()[0].tolist())})"
+
+
+# ----------------------------------------------------------------------------- one whole masked stack on integers (both directions)
+@functools.lru_cache(maxsize=None)
+def stack_data(ffdnet):
+    """(layers, x, sigma, v): a three-layer plan 1 -> 64 -> 64 -> 1 (FFDNet's twin: 5 -> 64 -> 64 -> 4, sigma (1,)) whose Jacobian
+    products are integers below 2^24 under a worst-case argument (stack_worst_case: all-ones masks, absolute values): first and last
+    weights in {-1, +1}, middle weights in {-4, +4} (U = G w G^T an integer, |U| <= 9), integer middle bias, v in {-1, 0, 1} - for
+    FFDNet supported on one pixel phase (rows and columns even: one unshuffled channel).  x = rand: the masks are those of a real
+    forward pass."""
+    g = _gen(6000 + int(ffdnet))
+    sign = lambda shape, m: (torch.randint(0, 2, shape, generator=g).float() * 2 - 1) * m
+    n, H, W = nf.CASES["head_valu" if ffdnet else "f22"]["shape"]
+    f = 2 if ffdnet else 1
+    layers = [(sign((64, 5 if ffdnet else 1, 3, 3), 1), None, True), (sign((64, 64, 3, 3), 4), _ints((64,), -8, 8, g), True),
+              (sign((4 if ffdnet else 1, 64, 3, 3), 1), None, False)]
+    x = torch.rand((n, 1, f * H, f * W), generator=g)
+    v = torch.randint(-1, 2, (n, 1, f * H, f * W), generator=g).float()
+    if ffdnet:
+        phase = torch.zeros(1, 1, f * H, f * W)
+        phase[..., ::2, ::2] = 1
+        v = v * phase
+    return layers, x, (torch.tensor([0.1]) if ffdnet else None), v
+
+
+def stack_worst_case(layers, v, ffdnet, direction):
+    """The largest absolute value that any partial sum of _MaskedStack.jvp / .vjp can take on (layers, v), float64: every mask all ones,
+    every operand its absolute value.  -> the maxima behind the first launch, behind the middle one (its values: the direct sum), of
+    the middle one's own partial sums (the propagation of its F(2x2,3x3) transforms), and behind the last launch."""
+    read, cin, write = _vjp.FFDNET_EDGES if ffdnet else _vjp.PLAIN_EDGES
+    w0, w1, w2 = (l[0].double().abs() for l in layers)
+    w0 = w0[:, cin]
+    if direction == "vjp":
+        w0, w1, w2 = _vjp._transposed(w2), _vjp._transposed(w1), _vjp._transposed(w0)
+    t1 = s_plain(read(v.double().abs()), w0)
+    t2 = s_plain(t1, w1)
+    return float(t1.max()), float(t2.max()), float(s_wino(t1, w1, (2, 2)).max()), float(s_plain(t2, w2).max())
 
 
 # ----------------------------------------------------------------------------- float64 references and S
@@ -360,6 +536,15 @@ class Arena:
         cl = t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
         assert cl or t.is_contiguous()
         _, _, view = self._carve(tuple(t.shape), t.dtype, float("nan"), cl)
+        view.copy_(t)
+        return view
+
+    def words(self, t, fill):
+        """An integer operand (the int64 mask words: no NaN exists for them) in a view of t's shape inside guard words of the caller's
+        `fill`.  A case launches once inside all-ones and once inside all-zero words: a kernel that takes any word from outside the mask
+        then differs between its two launches, or from the reference."""
+        assert not t.dtype.is_floating_point and t.is_contiguous()
+        _, _, view = self._carve(tuple(t.shape), t.dtype, fill, False)
         view.copy_(t)
         return view
 

@@ -1,5 +1,6 @@
 """Every forward kernel of the denoiser against float64, element by element (statement, data, constants: tests/denoiser_exact_ref.py;
-the helper itself is held by tests/test_denoiser_exact_host.py; measured ratios: profiles/denoiser_exact.md).
+the helper itself is held by tests/test_denoiser_exact_host.py; measured ratios: profiles/denoiser_exact.md).  The masked kernels of the
+backward are held the same way, with this file's hold(), in tests/test_backward_exact_gpu.py.
 
 Each case runs one entry point of deqsci_amd/_hip.py in one form at one shape of nonfinite_ref.CASES (64 -> 64 kernels: also one pixel
 and a launch of more block tiles than persistent workgroups), twice:
@@ -40,9 +41,10 @@ def exps(slot, fixed, n):
     return [fixed] * n if slot is None else [_hip.act_exp(v) for v in slot.tolist()]
 
 
-def hold(kernel, form, shape, mode, launch, ref, bound):
+def hold(kernel, form, shape, mode, launch, ref, bound, explain=None):
     """(a) or (b), and (c), of one case.  launch() -> (got fp32 (n,C,H,W) on the device, [padding tensors], arena); ref: float64 on the
-    CPU; bound: float64 on the CPU (mode "real"), or a function of the reference for an output that is itself split."""
+    CPU; bound: float64 on the CPU (mode "real"), or a function of the reference for an output that is itself split.  explain(got) ->
+    a sentence or None, asked only when the case fails (the masked kernels: what was done to the mask)."""
     got, pads, arena = launch()
     again, pads2, arena2 = launch()
     torch.cuda.synchronize()
@@ -71,6 +73,9 @@ def hold(kernel, form, shape, mode, launch, ref, bound):
         print(f"ROW | {kernel} | {form} | {shape[0]}x{shape[1]}x{shape[2]} | {ratio:.3g} |")
         if not bool((err <= b).all()):
             fails.append(f"{int((~(err <= b)).sum())} elements beyond the bound, worst err/bound {ratio:.3f}")
+    said = explain(got) if fails and explain is not None else None
+    if said:
+        fails.append(said)
     assert not fails, f"{kernel} {form} {shape} {mode}: " + "; ".join(fails)
 
 
