@@ -260,7 +260,7 @@ class _Denoiser:
         if not ok:
             self.train_why = why
             return
-        stack = vjp._bn_stack(self.net, True)[0]
+        stack = vjp.bn_stack(self.net, True)[0]
         w0, wl = stack[0][0].weight.detach(), stack[-1][0].weight.detach()
         if e.ffdnet:
             e.head_w, e.tail_w = _hip.pack_head_weights(w0), _hip.pack_tail_weights(wl)

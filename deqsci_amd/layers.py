@@ -1,8 +1,9 @@
 """What a "conv stack" is, decided once: a denoiser's module sequence (conv -> optional BatchNorm -> optional ReLU, repeated) as
 [(weight, bias or None, relu)] with eval-mode BatchNorm folded into the convolution.  The engine's f-call (engine._Denoiser), the implicit
 backward and the Jacobian diagnostics (vjp.host_plan, vjp.ffdnet_plan) all run this list.  conv_bn_stack is the same walk unfolded -
-[(conv, bn or None, relu)], the modules themselves - for what needs the BatchNorm's own parameters (vjp.grad_parameters and the
-frozen-BatchNorm weight gradients).  CPU-safe."""
+[(conv, bn or None, relu)], the modules themselves - for what needs the BatchNorm's own parameters: vjp.bn_stack, and behind it
+vjp.grad_parameters and the one backward walk of the weight gradients with its three layer rules (no BatchNorm, frozen, train mode);
+`folded` turns that list into conv_stack's.  CPU-safe."""
 import torch
 
 
@@ -58,12 +59,15 @@ def conv_stack(mods):
     BatchNorm folded (weight * s, bias = beta - mean * s) - or (None, why not) when it is anything but 3x3, stride-1, pad-1 convolutions
     without bias, each followed by an optional eval-mode BatchNorm2d and an optional ReLU."""
     stack, why = conv_bn_stack(mods)
-    if stack is None:
-        return None, why
+    return (None, why) if stack is None else (folded(stack), None)
+
+
+def folded(stack):
+    """conv_bn_stack's list as conv_stack's: [(weight, bias or None, relu)], detached, every (eval-mode) BatchNorm folded."""
     layers = []
     for conv, bn, relu in stack:
         w, b = conv.weight.detach(), None
         if bn is not None:
             w, b = (t.detach() for t in _fold_bn(w, bn))
         layers.append((w, b, relu))
-    return layers, None
+    return layers

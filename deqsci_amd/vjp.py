@@ -22,36 +22,43 @@ The same masked kernels compute J_D(x) v (forward mode) when they are handed the
 the map the iteration applies, sigma a constant of the linearisation - on csrc/jacobian.hip's masked first layer and the existing last
 layer's kernel.  DenoiserVJP and eligibility are the training hook's and do not change.
 
-The weight gradients (dD/dtheta)^T v of a bias-free conv + ReLU stack come from the same walk: the forward keeps each layer's input, the
-transposed masked layers carry v down, and layer i's dW_i is the correlation of its input with the masked gradient behind it
-(csrc/wgrad.hip: W0 for a 64 -> 64 layer, W1 for the two edge layers).  plan_param_grads is the host statement, DenoiserParamGrads the
-device's, param_eligibility says which nets qualify (DEQFixedPoint.parameter_backward = "device").
+The weight gradients (dD/dtheta)^T v come from ONE walk in every BatchNorm mode, stated once on the host (_taped_forward, _walk_back) and
+once on the device (_MaskedStack's forward, DenoiserParamGrads._walk): a forward that keeps each layer's input, then the transposed masked
+layers carry v down and every layer forms its gradients from its input and the masked gradient gm behind it.  What a layer is - how it
+runs forward, what it forms, what it hands down and through which transposed weight - is its RULE, and there are three (_PlainRule,
+_FrozenRule, _TrainRule on the host; _Conv64, _Frozen64, _Train64 on the device); the edge layers, plain or FFDNet's, come from
+PLAIN_EDGES / FFDNET_EDGES.  bn_stack says which nets qualify and _structure_refusal what shape they must have; param_eligibility,
+grad_parameters, the host statements (plan_param_grads, plan_param_grads_frozen_bn, plan_forward_train_bn, plan_param_grads_train_bn) and
+DenoiserParamGrads are thin callers.
 
-With a frozen (eval-mode) BatchNorm behind a conv - FFDNet, a conv + BN + ReLU DnCNN; parameter_backward = "device+bn",
+No BatchNorm - a bias-free conv + ReLU stack, DEQFixedPoint.parameter_backward = "device", param_eligibility(net): dW = wgrad(x, gm), the
+correlation of the layer's input with the masked gradient behind it (csrc/wgrad.hip: W0 for a 64 -> 64 layer, W1 for the two edge
+layers), and gm goes down through W^T.
+
+A frozen (eval-mode) BatchNorm behind the conv - FFDNet, a conv + BN + ReLU DnCNN; parameter_backward = "device+bn",
 param_eligibility(net, frozen_bn=True) - the layer is y = relu(s c + t), c = conv(x, W), s = gamma / sqrt(var + eps), t = beta - mean s, and
-with gm the masked gradient behind the ReLU and R = wgrad(x, gm):
+with R = wgrad(x, gm), gm going down through (s W)^T:
 
     dW = s R        dbeta = sum_p gm        dgamma = (sum_{ci,tap} W R - mean dbeta) / sqrt(var + eps)
 
 (sum_p gm c = sum W R: no stored pre-activation and no division by gamma, exact for gamma = 0 and gamma < 0; csrc/wgrad_bn.hip's W0-BN gives
 the three sums from one pass).  FFDNet's edge layers are read through the 2x2 pixel-(un)shuffle by W2 of the same file, sigma's channel of
-the first weight included.  grad_parameters names the parameters, plan_param_grads_frozen_bn is the host statement.
+the first weight included.
 
-With the BatchNorm in TRAIN mode - what the reference trains: it calls .eval() under --inference only; parameter_backward =
+The BatchNorm in TRAIN mode - what the reference trains: it calls .eval() under --inference only; parameter_backward =
 "device+bn-train", param_eligibility(net, train_bn=True) - the layer is y = relu(gamma xhat + beta), xhat = (c - mean) / sqrt(var + eps) with
-the mean and the biased variance of c = conv(x, W) over the batch's P = n H W pixels, and with gm the masked gradient behind the ReLU:
+the mean and the biased variance of c = conv(x, W) over the batch's P = n H W pixels, and:
 
     dbeta = sum_p gm        dgamma = sum_p gm xhat        dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P)        dW = wgrad(x, dc)
 
 (csrc/bn_train.hip: T1 statistics and the running buffers' update, T2 apply + mask, T3 the two sums, T4 dc; dc goes down through the UNFOLDED
-transposed weight).  The statistic terms reach the pixels the ReLU masked too.  plan_forward_train_bn / plan_param_grads_train_bn are the
-host statements.
+transposed weight).  The statistic terms reach the pixels the ReLU masked too.
 """
 import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .layers import conv_bn_stack, conv_stack
+from .layers import conv_bn_stack, conv_stack, folded
 
 _FFDNET_OK = "FFDNet detaches its input: J_D^T = 0"
 
@@ -72,28 +79,47 @@ def host_plan(net):
     return conv_stack(net.dncnn)
 
 
+_FFDNET_COLOUR = "FFDNet with 3 channels (the HIP kernels cover the grayscale network only)"
+
+
+def _structure_refusal(stack, ffdnet):
+    """What the kernels cover, stated once for eligibility, bn_stack (so param_eligibility and grad_parameters) and ffdnet_plan: None, or
+    why the layers `stack` = [(conv or its weight, what sits behind it - a BatchNorm2d or its folded bias - or None, relu)] are not
+    1 -> 64 -> ... -> 64 -> 1 (ffdnet: 5 -> 64 -> ... -> 64 -> 4) with a ReLU behind every layer but the last and nothing else behind the
+    two edge layers."""
+    shapes = [tuple(getattr(c, "weight", c).shape) for c, _, _ in stack]
+    first, last = ((64, 5, 3, 3), (4, 64, 3, 3)) if ffdnet else ((64, 1, 3, 3), (1, 64, 3, 3))
+    if len(shapes) < 2 or shapes[0] != first or shapes[-1] != last or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
+        return f"layer shapes {shapes}: the kernels cover {first[1]} -> 64 -> ... -> 64 -> {last[0]}"
+    if not all(r for _, _, r in stack[:-1]) or stack[-1][2]:
+        return "ReLU pattern other than after every layer but the last"
+    if stack[0][1] is not None or stack[-1][1] is not None:
+        return "BatchNorm2d behind the first or the last layer (the edge kernels have no scale)"
+    return None
+
+
+def _plugin_refusal(net, what):
+    """Why `net` is no 'denoiser' plugin made of a module sequence .dncnn, or None."""
+    if getattr(net, "tag", None) != "denoiser":
+        return f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' and 'ffdnet' plugins have {what}"
+    if not isinstance(net, _modules()[0]):
+        return f"not a conv [+BN] + ReLU stack: {type(net).__name__}"
+    return None
+
+
 def eligibility(net):
     """(ok, reason): whether DenoiserVJP (and DEQFixedPoint.implicit_backward = "device") can differentiate through `net`.  CPU-safe."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     if isinstance(net, FFDNet):
         if net.num_input_channels != 1:
-            return False, "FFDNet with 3 channels (the HIP kernels cover the grayscale network only)"
+            return False, _FFDNET_COLOUR
         if any(isinstance(m, torch.nn.BatchNorm2d) and m.training for m in net.modules()):
             return False, "FFDNet with BatchNorm2d in train mode"
         return True, _FFDNET_OK
-    if getattr(net, "tag", None) != "denoiser":
-        return False, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' and 'ffdnet' plugins have a device VJP"
-    layers, why = host_plan(net)
-    if layers is None:
-        return False, why
-    shapes = [tuple(w.shape) for w, _, _ in layers]
-    if len(layers) < 2 or shapes[0] != (64, 1, 3, 3) or shapes[-1] != (1, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
-        return False, f"layer shapes {shapes}: the kernels cover 1 -> 64 -> ... -> 64 -> 1"
-    if layers[0][1] is not None or layers[-1][1] is not None:
-        return False, "bias on the first or the last layer"
-    if not all(r for _, _, r in layers[:-1]) or layers[-1][2]:
-        return False, "ReLU pattern other than after every layer but the last"
-    return True, "conv [+BN-eval] + ReLU stack"
+    why = _plugin_refusal(net, "a device VJP")
+    layers, why = (None, why) if why else host_plan(net)
+    why = _structure_refusal(layers, False) if layers is not None else why
+    return (True, "conv [+BN-eval] + ReLU stack") if why is None else (False, why)
 
 
 def _transposed(w):
@@ -162,27 +188,118 @@ def plan_jvp(layers, x, v, masks=None):
     return masked_jvp(layers, masks, v), masks
 
 
-def plan_param_grads(layers, x, v, masks=None):
-    """(dD/dtheta)^T v of the stack `layers` at x, one tensor per conv weight, in x's dtype - the host statement of what
-    DenoiserParamGrads.grads runs, next to plan_vjp: one masked forward keeps each layer's input, the layers are walked backwards with
-    masked_vjp's steps, and dW_i comes from layer i's input and the masked gradient behind it.  masks: those of another forward pass (the
-    device's, unpack_masks) in place of the decisions at x.  Returns ([dW_0 .. dW_{k-1}], masks)."""
-    inputs, used, h = [x], [], x
-    for i, (w, b, relu) in enumerate(layers[:-1]):
-        h = F.conv2d(h, w.to(x), None if b is None else b.to(x), padding=1)
-        m = (masks[i] if masks is not None else h > 0) if relu else None
+# ----------------------------------------------------------------------------- the weight gradients: one walk, three layer rules
+# A layer rule is what one convolution of the stack is on the host, in its weight W's dtype: .forward(h) -> (y in front of the ReLU, what
+# the way back needs of it), .backward(input, kept, gm) -> ([the gradients of the layer's parameters], the gradient behind the convolution)
+# for gm the gradient masked by the layer's ReLU, and .down, the weight whose transpose carries that gradient to the layer below.
+class _PlainRule:
+    """y = conv(x, W) [+ bias]:  dW = wgrad(x, gm), gm goes down through W^T."""
+
+    def __init__(self, W, bias=None):
+        self.W, self.bias, self.down = W, bias, W
+
+    def forward(self, h):
+        return F.conv2d(h, self.W, self.bias, padding=1), None
+
+    def backward(self, inp, kept, gm):
+        return [torch.nn.grad.conv2d_weight(inp, self.W.shape, gm, padding=1)], gm
+
+
+class _FrozenRule:
+    """y = s conv(x, W) + t of an eval-mode BatchNorm:  R = wgrad(x, gm), dW = s R, dgamma = (sum W R - mean dbeta) / sqrt(var + eps),
+    dbeta = sum gm; gm goes down through (s W)^T."""
+
+    def __init__(self, W, bn):
+        self.W, (self.s, self.mean, self.inv) = W, _bn_scale(bn, W)
+        self.shift, self.down = bn.bias.detach().to(W) - self.mean * self.s, W * self.s.view(-1, 1, 1, 1)
+
+    def forward(self, h):
+        return F.conv2d(h, self.W, padding=1) * self.s.view(1, -1, 1, 1) + self.shift.view(1, -1, 1, 1), None
+
+    def backward(self, inp, kept, gm):
+        R = torch.nn.grad.conv2d_weight(inp, self.W.shape, gm, padding=1)
+        dbeta = gm.sum((0, 2, 3))
+        return [self.s.view(-1, 1, 1, 1) * R, ((self.W * R).sum((1, 2, 3)) - self.mean * dbeta) * self.inv, dbeta], gm
+
+
+class _TrainRule:
+    """y = gamma xhat + beta of a train-mode BatchNorm, xhat = (c - mean) / sqrt(var + eps) by the batch's statistics of c = conv(x, W):
+    dbeta = sum gm, dgamma = sum gm xhat, dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P), dW = wgrad(x, dc); dc goes down
+    through W^T.  update: the forward moves the module's running buffers as torch does."""
+
+    def __init__(self, W, bn, update, who):
+        self.W, self.down, self.bn, self.update, self.who = W, W, bn, update, who
+        self.gamma, self.beta = bn.weight.detach().to(W), bn.bias.detach().to(W)
+
+    def forward(self, h):
+        c, bn = F.conv2d(h, self.W, padding=1), self.bn
+        P = c.numel() // c.shape[1]
+        if P < 2:
+            raise ValueError(f"{self.who}: expected more than 1 value per channel when training, got input size {list(c.shape)}")
+        mean, var = c.mean((0, 2, 3)), c.var((0, 2, 3), unbiased=False)
+        inv = 1.0 / torch.sqrt(var + bn.eps)
+        xhat = (c - mean.view(1, -1, 1, 1)) * inv.view(1, -1, 1, 1)
+        if self.update:
+            with torch.no_grad():
+                m = bn.momentum
+                bn.running_mean.copy_((1.0 - m) * bn.running_mean.to(mean) + m * mean)
+                bn.running_var.copy_((1.0 - m) * bn.running_var.to(var) + m * (var * (P / (P - 1))))
+                bn.num_batches_tracked += 1
+        return xhat * self.gamma.view(1, -1, 1, 1) + self.beta.view(1, -1, 1, 1), (xhat, inv, P)
+
+    def backward(self, inp, kept, gm):
+        xhat, inv, P = kept
+        dbeta, dgamma = gm.sum((0, 2, 3)), (gm * xhat).sum((0, 2, 3))
+        dc = (self.gamma * inv).view(1, -1, 1, 1) * (gm - (dbeta / P).view(1, -1, 1, 1) - xhat * (dgamma / P).view(1, -1, 1, 1))
+        return [torch.nn.grad.conv2d_weight(inp, self.W.shape, dc, padding=1), dgamma, dbeta], dc
+
+
+def _first_input(who, edges, x, sigma):
+    """What the first layer reads of the image x: x itself, or FFDNet's pixel-unshuffle of it behind the noise-level map."""
+    if edges is PLAIN_EDGES:
+        return x
+    _even(x, who)
+    if sigma is None:
+        raise ValueError(f"{who}: FFDNet is evaluated at a noise level: sigma is required")
+    return torch.cat((_sigma_map(sigma, x), edges[0](x)), 1)
+
+
+def _taped_forward(rules, relus, h, masks=None):
+    """The forward that keeps the tape: every layer but the last on the first layer's input h.  -> (tape, masks): tape[i] = (layer i's
+    input, what its rule kept), masks[i] the ReLU decision behind layer i - those handed in, else the ones at h - or None without a ReLU."""
+    tape, used = [], []
+    for i, (rule, relu) in enumerate(zip(rules[:-1], relus)):
+        y, kept = rule.forward(h)
+        m = (masks[i] if masks is not None else y > 0) if relu else None
+        tape.append((h, kept))
         used.append(m)
-        if m is not None:
-            h = h * m
-        inputs.append(h)
-    grads, g = [None] * len(layers), v
-    for i in range(len(layers) - 1, -1, -1):
-        grads[i] = torch.nn.grad.conv2d_weight(inputs[i], layers[i][0].shape, g, padding=1)
+        h = y if m is None else y * m
+    return tape + [(h, None)], used
+
+
+def _walk_back(rules, tape, used, v, edges, want_input=False):
+    """The walk back from the gradient v of the stack's output: each rule forms its layer's gradients, and what it hands down goes through
+    the transposed weight and the ReLU mask of the layer below.  -> (the gradients layer by layer in one list, J^T v or None)."""
+    read, cin, write = edges
+    per_layer, g = [None] * len(rules), read(v)
+    for i in range(len(rules) - 1, -1, -1):
+        per_layer[i], g = rules[i].backward(*tape[i], g)
         if i > 0:
-            g = F.conv2d(g, _transposed(layers[i][0].to(v)), padding=1)
+            g = F.conv2d(g, _transposed(rules[i].down), padding=1)
             if used[i - 1] is not None:
                 g = g * used[i - 1]
-    return grads, used
+    gx = write(F.conv2d(g, _transposed(rules[0].down[:, cin]), padding=1)) if want_input else None
+    return [t for layer in per_layer for t in layer], gx
+
+
+def plan_param_grads(layers, x, v, masks=None):
+    """(dD/dtheta)^T v of the stack `layers` at x, one tensor per conv weight, in x's dtype - the host statement of what
+    DenoiserParamGrads.grads runs, next to plan_vjp: the taped forward keeps each layer's input, the layers are walked backwards with
+    masked_vjp's steps, and dW_i comes from layer i's input and the masked gradient behind it.  masks: those of another forward pass (the
+    device's, unpack_masks) in place of the decisions at x.  Returns ([dW_0 .. dW_{k-1}], masks)."""
+    rules = [_PlainRule(w.to(x), None if b is None else b.to(x)) for w, b, _ in layers]
+    tape, used = _taped_forward(rules, [relu for _, _, relu in layers], x, masks)
+    return _walk_back(rules, tape, used, v, PLAIN_EDGES)[0], used
 
 
 _FROZEN_BN_OK, _FROZEN_FFDNET_OK = "bias-free conv [+ frozen BN] + ReLU stack", "FFDNet with its BatchNorm frozen"
@@ -218,48 +335,51 @@ def _train_bn_refusal(mods):
     return None
 
 
-def _frozen_bn_stack(net):
-    """(stack, ffdnet, reason): layers.conv_bn_stack of a net the frozen-BatchNorm weight gradients serve - [(conv, bn or None, relu)] and
-    whether its edge layers are FFDNet's - or (None, None, why not)."""
-    return _bn_stack(net, False)
+def _no_bn_refusal(mods):
+    if any(isinstance(m, torch.nn.BatchNorm2d) for m in mods):
+        return "BatchNorm2d (its gamma / beta gradients, and the batch statistics in train mode, have no device kernel)"
+    return None
 
 
-def _bn_stack(net, train):
-    """_frozen_bn_stack (train=False), or the same for a net whose BatchNorms are in train mode (train=True)."""
+_BN_REFUSAL = {None: _no_bn_refusal, False: _bn_refusal, True: _train_bn_refusal}
+
+
+def bn_stack(net, train):
+    """(stack, ffdnet, reason): layers.conv_bn_stack of a net the device weight gradients serve - [(conv, bn or None, relu)] and whether its
+    edge layers are FFDNet's - or (None, None, why not).  train: False - every BatchNorm frozen (eval mode), True - every BatchNorm in train
+    mode, None - no BatchNorm at all (and no FFDNet: parameter_backward = "device").  Refusals in this order: the plugin's tag and type,
+    its modules (RealSN, the BatchNorms' state), layers.conv_bn_stack's own, _structure_refusal's, a weight that is no nn.Parameter."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     ffdnet = isinstance(net, FFDNet)
-    if ffdnet:
-        if net.num_input_channels != 1:
-            return None, None, "FFDNet with 3 channels (the HIP kernels cover the grayscale network only)"
-        mods = list(net.intermediate_dncnn.itermediate_dncnn)
-    else:
-        if getattr(net, "tag", None) != "denoiser":
-            return None, None, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' and 'ffdnet' plugins have device weight gradients"
-        if not isinstance(net, DnCNN):
-            return None, None, f"not a conv [+BN] + ReLU stack: {type(net).__name__}"
-        mods = list(net.dncnn)
+    if ffdnet and train is None:
+        return None, None, "FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient"
+    why = (_FFDNET_COLOUR if net.num_input_channels != 1 else None) if ffdnet else _plugin_refusal(net, "device weight gradients")
+    if why is not None:
+        return None, None, why
+    mods = list(net.intermediate_dncnn.itermediate_dncnn if ffdnet else net.dncnn)
     if any(isinstance(m, RealSNConv2d) for m in mods):
         return None, None, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
-    why = _train_bn_refusal(mods) if train else _bn_refusal(mods)
+    why = _BN_REFUSAL[train](mods)
     if why is not None:
         return None, None, ("FFDNet: " if ffdnet else "") + why
-    stack, why = conv_bn_stack(mods, train_bn=train)
-    if stack is None:
-        return None, None, why
-    shapes = [tuple(c.weight.shape) for c, _, _ in stack]
-    first, last = ((64, 5, 3, 3), (4, 64, 3, 3)) if ffdnet else ((64, 1, 3, 3), (1, 64, 3, 3))
-    if len(stack) < 2 or shapes[0] != first or shapes[-1] != last or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
-        return None, None, f"layer shapes {shapes}: the kernels cover {first[1]} -> 64 -> ... -> 64 -> {last[0]}"
-    if not all(r for _, _, r in stack[:-1]) or stack[-1][2]:
-        return None, None, "ReLU pattern other than after every layer but the last"
-    if stack[0][1] is not None or stack[-1][1] is not None:
-        return None, None, "BatchNorm2d behind the first or the last layer (the edge kernels have no scale)"
-    if not all(isinstance(c.weight, torch.nn.Parameter) for c, _, _ in stack):
-        return None, None, "a conv weight that is not an nn.Parameter"
-    return stack, ffdnet, None
+    stack, why = conv_bn_stack(mods, train_bn=bool(train))
+    why = _structure_refusal(stack, ffdnet) if stack is not None else why
+    if why is None and not all(isinstance(c.weight, torch.nn.Parameter) for c, _, _ in stack):
+        why = "a conv weight that is not an nn.Parameter"
+    return (stack, ffdnet, None) if why is None else (None, None, why)
 
 
 _TRAIN_BN_OK, _TRAIN_FFDNET_OK = "bias-free conv [+ train-mode BN] + ReLU stack", "FFDNet with its BatchNorm in train mode"
+
+
+_PARAM_OK = {None: ("bias-free conv + ReLU stack", None), False: (_FROZEN_BN_OK, _FROZEN_FFDNET_OK), True: (_TRAIN_BN_OK, _TRAIN_FFDNET_OK)}
+
+
+def _bn_mode(who, frozen_bn, train_bn):
+    """The two keywords as bn_stack's `train`."""
+    if train_bn and frozen_bn:
+        raise ValueError(f"{who}: frozen_bn and train_bn exclude one another")
+    return True if train_bn else (False if frozen_bn else None)
 
 
 def param_eligibility(net, frozen_bn=False, train_bn=False):
@@ -268,42 +388,11 @@ def param_eligibility(net, frozen_bn=False, train_bn=False):
     no_bn=True) of any depth >= 2.  frozen_bn=True (parameter_backward = "device+bn") accepts in addition an eval-mode affine BatchNorm2d
     with running statistics behind every 64 -> 64 conv - DnCNN(..., no_bn=False).eval() - and the grayscale FFDNet with its BatchNorms in
     eval mode.  train_bn=True (parameter_backward = "device+bn-train") accepts those two families with their BatchNorms in TRAIN mode -
-    affine, with running statistics and a float momentum (csrc/bn_train.hip) - and refuses an eval-mode BatchNorm.  CPU-safe."""
-    if train_bn:
-        if frozen_bn:
-            raise ValueError("param_eligibility: frozen_bn and train_bn exclude one another")
-        stack, ffdnet, why = _bn_stack(net, True)
-        if stack is None:
-            return False, why
-        return True, _TRAIN_FFDNET_OK if ffdnet else _TRAIN_BN_OK
-    if frozen_bn:
-        stack, ffdnet, why = _frozen_bn_stack(net)
-        if stack is None:
-            return False, why
-        return True, _FROZEN_FFDNET_OK if ffdnet else _FROZEN_BN_OK
-    DnCNN, FFDNet, RealSNConv2d = _modules()
-    if isinstance(net, FFDNet):
-        return False, "FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient"
-    if getattr(net, "tag", None) != "denoiser":
-        return False, f"nonlinear_op tag {getattr(net, 'tag', None)!r}: only 'denoiser' plugins have device weight gradients"
-    if not isinstance(net, DnCNN):
-        return False, f"not a conv + ReLU stack: {type(net).__name__}"
-    mods = list(net.dncnn)
-    if any(isinstance(m, torch.nn.BatchNorm2d) for m in mods):
-        return False, "BatchNorm2d (its gamma / beta gradients, and the batch statistics in train mode, have no device kernel)"
-    if any(isinstance(m, RealSNConv2d) for m in mods):
-        return False, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
-    layers, why = conv_stack(mods)
-    if layers is None:
-        return False, why
-    shapes = [tuple(w.shape) for w, _, _ in layers]
-    if len(layers) < 2 or shapes[0] != (64, 1, 3, 3) or shapes[-1] != (1, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1]):
-        return False, f"layer shapes {shapes}: the kernels cover 1 -> 64 -> ... -> 64 -> 1"
-    if not all(r for _, _, r in layers[:-1]) or layers[-1][2]:
-        return False, "ReLU pattern other than after every layer but the last"
-    if not all(isinstance(m.weight, torch.nn.Parameter) for m in mods if isinstance(m, torch.nn.Conv2d)):
-        return False, "a conv weight that is not an nn.Parameter"
-    return True, "bias-free conv + ReLU stack"
+    affine, with running statistics and a float momentum (csrc/bn_train.hip) - and refuses an eval-mode BatchNorm.  bn_stack decides.
+    CPU-safe."""
+    mode = _bn_mode("param_eligibility", frozen_bn, train_bn)
+    stack, ffdnet, why = bn_stack(net, mode)
+    return (False, why) if stack is None else (True, _PARAM_OK[mode][ffdnet])
 
 
 def conv_weights(net):
@@ -315,7 +404,7 @@ def grad_parameters(net, train_bn=False):
     """The nn.Parameters of a net param_eligibility(net, frozen_bn=True) accepts, in module order - per layer the conv weight, then its
     BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for.  train_bn=True:
     the same for a net param_eligibility(net, train_bn=True) accepts."""
-    stack, _, why = _bn_stack(net, bool(train_bn))
+    stack, _, why = bn_stack(net, bool(train_bn))
     if stack is None:
         raise ValueError(f"grad_parameters: {why}")
     out = []
@@ -333,97 +422,32 @@ def _bn_scale(bn, like):
     return T(bn.weight) * inv, T(bn.running_mean), inv
 
 
-def plan_param_grads_frozen_bn(net, x, v, sigma=None, masks=None):
-    """(dD/dtheta)^T v of a net param_eligibility(net, frozen_bn=True) accepts, at x, in x's dtype - the host statement of what
-    DenoiserParamGrads(..., frozen_bn=True).grads runs: one masked forward of the unfolded layers y = relu(s conv(x, W) + t) keeps each
-    layer's input, the walk back carries gm with the folded transposed weights, and per layer R = conv2d_weight(input, gm) gives
-    dW = s R, dbeta = sum gm, dgamma = (sum W R - mean dbeta) / sqrt(var + eps).  FFDNet goes through FFDNET_EDGES at the noise level sigma
-    (1 or n values; sigma's channel of the first weight included) and differentiates nothing through its input.  masks: those of another
-    forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters order, masks)."""
-    stack, ffdnet, why = _frozen_bn_stack(net)
-    if stack is None:
-        raise ValueError(f"plan_param_grads_frozen_bn: {why}")
-    T = lambda p: p.detach().to(x)
-    if ffdnet:
-        _even(x, "plan_param_grads_frozen_bn")
-        if sigma is None:
-            raise ValueError("plan_param_grads_frozen_bn: FFDNet is evaluated at a noise level: sigma is required")
-        read = FFDNET_EDGES[0]
-        h, g = torch.cat((_sigma_map(sigma, x), read(x)), 1), read(v)
-    else:
-        h, g = x, v
-    inputs, used, bns = [h], [], []
-    for i, (conv, bn, relu) in enumerate(stack):
-        bns.append(None if bn is None else _bn_scale(bn, x))
-        if i == len(stack) - 1:
-            break
-        h = F.conv2d(h, T(conv.weight), padding=1)
-        if bn is not None:
-            s, mean, _ = bns[i]
-            h = h * s.view(1, -1, 1, 1) + (T(bn.bias) - mean * s).view(1, -1, 1, 1)
-        m = (masks[i] if masks is not None else h > 0) if relu else None
-        used.append(m)
-        if m is not None:
-            h = h * m
-        inputs.append(h)
-    per_layer = [None] * len(stack)
-    for i in range(len(stack) - 1, -1, -1):
-        W = T(stack[i][0].weight)
-        R = torch.nn.grad.conv2d_weight(inputs[i], W.shape, g, padding=1)
-        if bns[i] is None:
-            per_layer[i], folded = [R], W
-        else:
-            s, mean, inv = bns[i]
-            dbeta = g.sum((0, 2, 3))
-            per_layer[i] = [s.view(-1, 1, 1, 1) * R, ((W * R).sum((1, 2, 3)) - mean * dbeta) * inv, dbeta]
-            folded = W * s.view(-1, 1, 1, 1)
-        if i > 0:
-            g = F.conv2d(g, _transposed(folded), padding=1)
-            if used[i - 1] is not None:
-                g = g * used[i - 1]
-    return [t for layer in per_layer for t in layer], used
-
-
-# ----------------------------------------------------------------------------- BatchNorm in train mode: the host statements
-def _train_bn_walk(who, net, x, sigma, masks, update):
-    """One train-mode forward of a net param_eligibility(net, train_bn=True) accepts, in x's dtype.  -> (stack, ffdnet, noise, tape), tape =
-    per layer but the last (input, c, xhat or None, 1 / sqrt(var + eps) or None, mask or None), then the last layer's input."""
-    stack, ffdnet, why = _bn_stack(net, True)
+def _net_rules(who, net, train, like, update=False):
+    """bn_stack(net, train) as the host walk takes it, in like's dtype: (one rule per layer, the ReLU flags, the edges, ffdnet)."""
+    stack, ffdnet, why = bn_stack(net, train)
     if stack is None:
         raise ValueError(f"{who}: {why}")
-    T = lambda p: p.detach().to(x)
-    if ffdnet:
-        _even(x, who)
-        if sigma is None:
-            raise ValueError(f"{who}: FFDNet is evaluated at a noise level: sigma is required")
-        h = torch.cat((_sigma_map(sigma, x), F.pixel_unshuffle(x, 2)), 1)
-    else:
-        h = x
-    tape = []
-    for i, (conv, bn, relu) in enumerate(stack[:-1]):
-        c = F.conv2d(h, T(conv.weight), padding=1)
-        xhat = inv = None
-        y = c
-        if bn is not None:
-            P = c.numel() // c.shape[1]
-            if P < 2:
-                raise ValueError(f"{who}: expected more than 1 value per channel when training, got input size {list(c.shape)}")
-            mean, var = c.mean((0, 2, 3)), c.var((0, 2, 3), unbiased=False)
-            inv = 1.0 / torch.sqrt(var + bn.eps)
-            xhat = (c - mean.view(1, -1, 1, 1)) * inv.view(1, -1, 1, 1)
-            y = xhat * T(bn.weight).view(1, -1, 1, 1) + T(bn.bias).view(1, -1, 1, 1)
-            if update:
-                with torch.no_grad():
-                    m = bn.momentum
-                    bn.running_mean.copy_((1.0 - m) * bn.running_mean.to(mean) + m * mean)
-                    bn.running_var.copy_((1.0 - m) * bn.running_var.to(var) + m * (var * (P / (P - 1))))
-                    bn.num_batches_tracked += 1
-        m = (masks[i] if masks is not None else y > 0) if relu else None
-        tape.append((h, c, xhat, inv, m))
-        h = y if m is None else y * m
-    tape.append(h)
-    noise = F.conv2d(h, T(stack[-1][0].weight), padding=1)
-    return stack, ffdnet, (F.pixel_shuffle(noise, 2) if ffdnet else noise), tape
+    W = lambda conv: conv.weight.detach().to(like)
+    rules = [_PlainRule(W(c)) if bn is None else _TrainRule(W(c), bn, update, who) if train else _FrozenRule(W(c), bn) for c, bn, _ in stack]
+    return rules, [relu for _, _, relu in stack], FFDNET_EDGES if ffdnet else PLAIN_EDGES, ffdnet
+
+
+def _net_param_grads(who, net, train, x, v, sigma, masks, want_input=False):
+    """The host walk of a net: -> (gradients in grad_parameters order, masks, J_D(x)^T v or None)."""
+    rules, relus, edges, ffdnet = _net_rules(who, net, train, x)
+    tape, used = _taped_forward(rules, relus, _first_input(who, edges, x, sigma), masks)
+    grads, gx = _walk_back(rules, tape, used, v, edges, want_input and not ffdnet)          # (FFDNet detaches its input)
+    return grads, used, gx
+
+
+def plan_param_grads_frozen_bn(net, x, v, sigma=None, masks=None):
+    """(dD/dtheta)^T v of a net param_eligibility(net, frozen_bn=True) accepts, at x, in x's dtype - the host statement of what
+    DenoiserParamGrads(..., frozen_bn=True).grads runs: plan_param_grads' walk with _FrozenRule where a layer has a BatchNorm - the
+    forward runs the unfolded layers y = relu(s conv(x, W) + t), the walk back carries gm with the folded transposed weights.  FFDNet goes
+    through FFDNET_EDGES at the noise level sigma (1 or n values; sigma's channel of the first weight included) and differentiates nothing
+    through its input.  masks: those of another forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters order,
+    masks)."""
+    return _net_param_grads("plan_param_grads_frozen_bn", net, False, x, v, sigma, masks)[:2]
 
 
 def plan_forward_train_bn(net, x, sigma=None, update=True):
@@ -431,50 +455,20 @@ def plan_forward_train_bn(net, x, sigma=None, update=True):
     the biased variance of c = conv(x, W) over the batch, y = gamma (c - mean) / sqrt(var + eps) + beta, the ReLU; FFDNet at the noise level
     sigma through its pixel-(un)shuffle.  update=True moves the module's buffers as torch does: running_mean <- (1 - m) running_mean + m mean,
     running_var <- (1 - m) running_var + m var P / (P - 1), num_batches_tracked += 1.  -> (noise, masks)."""
-    _, _, noise, tape = _train_bn_walk("plan_forward_train_bn", net, x, sigma, None, update)
-    return noise, [t[4] for t in tape[:-1]]
-
-
-def _train_bn_backward(stack, ffdnet, tape, v):
-    """The walk back of plan_param_grads_train_bn.  -> (gradients in grad_parameters order, the input gradient or None for FFDNet)."""
-    T = lambda p: p.detach().to(v)
-    per_layer = [None] * len(stack)
-    dc = F.pixel_unshuffle(v, 2) if ffdnet else v
-    for i in range(len(stack) - 1, -1, -1):
-        conv, bn, _ = stack[i]
-        W = T(conv.weight)
-        inp = tape[i] if i == len(stack) - 1 else tape[i][0]
-        if i < len(stack) - 1:
-            _, c, xhat, inv, m = tape[i]
-            gm = g if m is None else g * m
-            if bn is None:
-                per_layer[i], dc = [None], gm
-            else:
-                P = c.numel() // c.shape[1]
-                dbeta, dgamma = gm.sum((0, 2, 3)), (gm * xhat).sum((0, 2, 3))
-                dc = (T(bn.weight) * inv).view(1, -1, 1, 1) * (gm - (dbeta / P).view(1, -1, 1, 1) - xhat * (dgamma / P).view(1, -1, 1, 1))
-                per_layer[i] = [None, dgamma, dbeta]
-        else:
-            per_layer[i] = [None]
-        per_layer[i][0] = torch.nn.grad.conv2d_weight(inp, W.shape, dc, padding=1)
-        if i > 0:
-            g = F.conv2d(dc, _transposed(W), padding=1)
-    gx = None if ffdnet else F.conv2d(dc, _transposed(T(stack[0][0].weight)), padding=1)
-    return [t for layer in per_layer for t in layer], gx
+    rules, relus, edges, _ = _net_rules("plan_forward_train_bn", net, True, x, update)
+    tape, used = _taped_forward(rules, relus, _first_input("plan_forward_train_bn", edges, x, sigma))
+    return edges[2](rules[-1].forward(tape[-1][0])[0]), used
 
 
 def plan_param_grads_train_bn(net, x, v, sigma=None, masks=None, input_grad=False):
     """(dD/dtheta)^T v of a net param_eligibility(net, train_bn=True) accepts, at x, in x's dtype - the host statement of what
-    DenoiserParamGrads(..., train_bn=True).grads runs: one train-mode forward (plan_forward_train_bn's, the buffers left alone) keeps each
-    layer's input, c and xhat; walking back, per layer with a BatchNorm and gm the gradient masked by its ReLU: dbeta = sum gm,
-    dgamma = sum gm xhat, dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P), dW = conv2d_weight(input, dc), and dc goes down
-    through the UNFOLDED transposed weight.  masks: those of another forward pass (the device's, unpack_masks).  Returns (gradients in
-    grad_parameters(net, train_bn=True) order, masks) - with input_grad=True (gradients, masks, J_D(x)^T v: the true input product,
-    statistic terms included; None for FFDNet, which detaches its input)."""
-    stack, ffdnet, _, tape = _train_bn_walk("plan_param_grads_train_bn", net, x, sigma, masks, False)
-    grads, gx = _train_bn_backward(stack, ffdnet, tape, v)
-    used = [t[4] for t in tape[:-1]]
-    return (grads, used, gx) if input_grad else (grads, used)
+    DenoiserParamGrads(..., train_bn=True).grads runs: plan_param_grads' walk with _TrainRule where a layer has a BatchNorm - the
+    forward is plan_forward_train_bn's with the buffers left alone, and dc goes down through the UNFOLDED transposed weight.  masks: those
+    of another forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters(net, train_bn=True) order, masks) - with
+    input_grad=True (gradients, masks, J_D(x)^T v: the true input product, statistic terms included; None for FFDNet, which detaches its
+    input)."""
+    out = _net_param_grads("plan_param_grads_train_bn", net, True, x, v, sigma, masks, input_grad)
+    return out if input_grad else out[:2]
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
@@ -488,12 +482,9 @@ def ffdnet_plan(net):
     if any(isinstance(m, RealSNConv2d) for m in mods):
         raise ValueError("ffdnet_plan: RealSNConv2d where FFDNet has a Conv2d")
     layers, why = conv_stack(mods)
-    if layers is None:
+    why = _structure_refusal(layers, True) if layers is not None else why
+    if why is not None:
         raise ValueError(f"ffdnet_plan: {why}")
-    shapes = [tuple(w.shape) for w, _, _ in layers]
-    if (len(layers) < 3 or shapes[0] != (64, 5, 3, 3) or shapes[-1] != (4, 64, 3, 3) or any(s != (64, 64, 3, 3) for s in shapes[1:-1])
-            or not all(r for _, _, r in layers[:-1]) or layers[-1][2] or layers[0][1] is not None or layers[-1][1] is not None):
-        raise ValueError(f"ffdnet_plan: layer shapes {shapes} are not the grayscale network's")
     return layers
 
 
@@ -554,57 +545,150 @@ class _MaskedStack:
     noise levels on x's device - its plan (ffdnet_plan), read through the 2x2 pixel-unshuffle: csrc/jacobian.hip's masked first layer
     serves the linearised head and the transposed tail, deqsci_ffdnet_tail_f32 without bias the linearised tail and the transposed head.
     None: a 1 -> 64 -> ... -> 64 -> 1 stack (host_plan).  keep: hold every post-ReLU activation of the forward pass (.acts[i] = the input
-    of layer i + 1, (k-1) n 64 H W 4 bytes in all) - what the weight gradients are formed from (DenoiserParamGrads)."""
+    of layer i + 1, (k-1) n 64 H W 4 bytes in all) and run the last layer on the last of them (.noise) - what the weight gradients are
+    formed from (DenoiserParamGrads).  It is the forward of every BatchNorm mode: rules are the 64 -> 64 layers as device rules (below) in
+    place of _Conv64 of `layers`' own.  through_input=False (FFDNet under DenoiserParamGrads: its input is detached, nothing is carried
+    through the first layer) builds no head_f / head_t."""
 
-    def __init__(self, layers, x, sigma=None, keep=False):
+    def __init__(self, layers, x, sigma=None, keep=False, rules=None, through_input=True):
         x = _hip.f32c(x.detach())
         f32 = lambda t: t.to(x.device, torch.float32)
         self.ffdnet = sigma is not None
+        pack_in, pack_out, self._first, self._last = _FFDNET_KERNELS if self.ffdnet else _PLAIN_KERNELS
         with torch.no_grad():
             w0, wt = f32(layers[0][0]), f32(layers[-1][0])
-            mid = [f32(w) for w, _, _ in layers[1:-1]]
-            if self.ffdnet:
-                win = w0[:, 1:5]                                    # (channel 0 is sigma's: it carries no tangent)
-                self.head_f = _hip.pack_head_masked_weights(win.contiguous())
-                self.tail_f = _hip.pack_tail_weights(wt)
-                self.tail_t = _hip.pack_head_masked_weights(_transposed(wt))
-                self.head_t = _hip.pack_tail_weights(_transposed(win))
-                h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), sigma)
-            else:
-                self.head_f = _hip.pack_c1_to_64_weights(w0)
-                self.tail_f = _hip.pack_c64_to_1_weights(wt)
-                self.tail_t = _hip.pack_c1_to_64_weights(_transposed(wt))
-                self.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
-                h = _hip.conv3x3_c1_to_64(x, self.head_f, relu=True)
-            self.mid_f = [_hip.pack_winograd_weights(w) for w in mid]
-            self.mid_t = [_hip.pack_winograd_weights(_transposed(w)) for w in mid]
+            win = w0[:, 1:5] if self.ffdnet else w0                 # (FFDNet's channel 0 is sigma's: it carries no tangent)
+            self.head_f, self.head_t = (pack_in(win.contiguous()), pack_out(_transposed(win))) if through_input else (None, None)
+            self.tail_f, self.tail_t = pack_out(wt), pack_in(_transposed(wt))
+            self.rules = [_Conv64(f32(w), b) for w, b, _ in layers[1:-1]] if rules is None else rules
+            h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), sigma) if self.ffdnet else _hip.conv3x3_c1_to_64(x, self.head_f, relu=True)
             self.masks = [_hip.relu_mask_pack(h)]
             self.acts = [h] if keep else None
-            for u, (_, b, _) in zip(self.mid_f, layers[1:-1]):
-                h = _hip.conv3x3_c64_winograd(h, u, None if b is None else f32(b).contiguous(), True)
-                self.masks.append(_hip.relu_mask_pack(h))
+            for rule in self.rules:
+                h, mask = rule.forward(h)
+                self.masks.append(mask)
                 if keep:
                     self.acts.append(h)
+            self.noise = self._last(h, self.tail_f) if keep else None
+            for rule in self.rules:         # (the way back's BatchNorm state comes last: the host prepares it while the device runs the forward)
+                rule.after_forward()
+            self.mid_f, self.mid_t = [r.u for r in self.rules], [r.ut for r in self.rules]
 
     def jvp(self, v):
-        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
-        t = first(_hip.f32c(v), self.head_f, self.masks[0])
+        t = self._first(_hip.f32c(v), self.head_f, self.masks[0])
         for i, u in enumerate(self.mid_f):
             t = _hip.conv3x3_c64_winograd_masked(t, u, self.masks[i + 1])
-        return _hip.ffdnet_tail(t, self.tail_f) if self.ffdnet else _hip.conv3x3_c64_to_1(t, self.tail_f)
+        return self._last(t, self.tail_f)
 
     def vjp(self, v):
-        first = _hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked
-        g = first(_hip.f32c(v), self.tail_t, self.masks[-1])
+        g = self._first(_hip.f32c(v), self.tail_t, self.masks[-1])
         for i in range(len(self.mid_t) - 1, -1, -1):           # layer i + 1 transposed, masked by the ReLU in front of it
             g = _hip.conv3x3_c64_winograd_masked(g, self.mid_t[i], self.masks[i])
-        return _hip.ffdnet_tail(g, self.head_t) if self.ffdnet else _hip.conv3x3_c64_to_1(g, self.head_t)
+        return self._last(g, self.head_t)
 
 
-def _image(x, who):
+# The device kernels of a family's edge layers: (the pack of a k -> 64 weight, the pack of a 64 -> k weight, the masked k -> 64 kernel, the
+# 64 -> k kernel), k = 1 or FFDNet's 4 channels of the 2x2 pixel-unshuffle.
+_PLAIN_KERNELS = (_hip.pack_c1_to_64_weights, _hip.pack_c64_to_1_weights, _hip.conv3x3_c1_to_64_masked, _hip.conv3x3_c64_to_1)
+_FFDNET_KERNELS = (_hip.pack_head_masked_weights, _hip.pack_tail_weights, _hip.ffdnet_head_masked, _hip.ffdnet_tail)
+
+
+# A device rule is what one 64 -> 64 layer of _MaskedStack is: .u / .ut its weight and its transposed weight - the one the gradient goes
+# down through - as Winograd packs, .count its parameters, .forward(h) -> (the post-ReLU activation, its mask words), .after_forward(),
+# which makes what only the way back needs - no pack: a pack copies from the host, and the stream would wait - behind the whole forward, and
+# .backward(input, g, need) -> ([one gradient or None per parameter], the gradient behind the convolution) for g the gradient masked by the
+# layer's ReLU and need one bool per parameter.  .ws: the scratch buffer of the rule's weight-gradient kernel, which its owner assigns.
+class _Conv64:
+    """conv [+ folded bias] + ReLU: Winograd F(2x2,3x3) with the bias and the ReLU, relu_mask_pack; W0 if the weight is asked for."""
+    count, bn_workspace = 1, False
+
+    def __init__(self, w, bias=None):
+        self.u, self.ut, self.ws = _hip.pack_winograd_weights(w), _hip.pack_winograd_weights(_transposed(w)), None
+        self.bias = None if bias is None else bias.to(w.device, torch.float32).contiguous()
+
+    def forward(self, h):
+        h = _hip.conv3x3_c64_winograd(h, self.u, self.bias, True)
+        return h, _hip.relu_mask_pack(h)
+
+    def after_forward(self):
+        pass
+
+    def backward(self, inp, g, need):
+        return [_hip.wgrad_c64_c64(inp, g, self.ws) if need[0] else None], g
+
+    def release(self):
+        pass
+
+
+class _Frozen64(_Conv64):
+    """The same forward and transposed pack with the eval-mode BatchNorm folded in (w = s W, bias = t); W0-BN and the float64 dgamma line
+    if any of W, gamma, beta is asked for.  W, s fp32 and mean, 1 / sqrt(var + eps) float64 are the unfolded layer's."""
+    count, bn_workspace = 3, True
+
+    def __init__(self, w, bias, conv, bn):
+        super().__init__(w, bias)
+        self.conv, self.bn = conv, bn
+
+    def after_forward(self):
+        dev = lambda t, dt=torch.float32: t.detach().to(self.u.device, dt).contiguous()
+        self.inv = 1.0 / torch.sqrt(dev(self.bn.running_var, torch.float64) + self.bn.eps)
+        self.s, self.mean = (dev(self.bn.weight, torch.float64) * self.inv).float(), dev(self.bn.running_mean, torch.float64)
+        self.W = dev(self.conv.weight)
+
+    def backward(self, inp, g, need):
+        if not any(need):
+            return [None] * 3, g
+        dw, dsum, ddot = _hip.wgrad_c64_c64_bn(inp, g, self.W, self.s, self.ws)
+        return [dw, ((ddot.double() - self.mean * dsum.double()) * self.inv).float(), dsum], g
+
+
+class _Train64(_Conv64):
+    """Train-mode BatchNorm: the raw Winograd convolution c, T1 (batch statistics; the module's running buffers move, once), T2 (normalise +
+    ReLU + the mask words); c is kept.  Back: T3 (dgamma, dbeta), T4 (dc, in place), W0 on dc if the weight is asked for; dc goes down
+    through the UNFOLDED transposed weight.  ws_bn: bn_train_workspace's buffer."""
+    count = 3
+
+    def __init__(self, w, bn, ws_bn):
+        super().__init__(w)
+        self.bn, self.ws_bn, self.eps = bn, ws_bn, float(bn.eps)
+        self.gamma = bn.weight.detach().to(w.device, torch.float32).contiguous()
+
+    def forward(self, h):
+        bn = self.bn
+        self.c = _hip.conv3x3_c64_winograd(h, self.u, None, False)
+        self.rec = _hip.bn_train_stats(self.c, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, workspace=self.ws_bn)
+        return _hip.bn_train_apply(self.c, self.rec, self.gamma, bn.bias.detach().to(self.gamma).contiguous(), self.eps, relu=True, want_mask=True)
+
+    def backward(self, inp, g, need):
+        if self.c is None:
+            raise RuntimeError(_RELEASED)
+        dgamma, dbeta, grec = _hip.bn_train_grad_stats(g, self.c, self.rec, self.eps, self.ws_bn)
+        g = _hip.bn_train_grad_apply(g, self.c, self.rec, grec, self.gamma, self.eps, out=g)         # dc, statistic terms included, in place
+        return [_hip.wgrad_c64_c64(inp, g, self.ws) if need[0] else None, dgamma, dbeta], g
+
+    def release(self):
+        self.c = None
+
+
+_RELEASED = "DenoiserParamGrads.grads: the activations were released"
+
+
+def _image(who, x, sigma=None, ffdnet=False):
+    """The checks of a (n,1,H,W) GPU image x and, for FFDNet, of its noise levels.  -> (x's shape, sigma as a (1,) or (n,) fp32 vector on x's
+    device that the kernels can stride - None without FFDNet)."""
     if x.dim() != 4 or x.shape[1] != 1 or not x.is_cuda:
         raise _hip.DeqsciHipError(f"{who}: x must be a (n,1,H,W) GPU image, got {tuple(x.shape)} on {x.device}")
-    return tuple(x.shape)
+    if not ffdnet:
+        return tuple(x.shape), None
+    _even(x, who)
+    if sigma is None:
+        raise ValueError(f"{who}: FFDNet is evaluated at a noise level: sigma is required")
+    sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1)
+    if sigma.numel() not in (1, x.shape[0]):
+        raise ValueError(f"{who}: sigma must have 1 or {x.shape[0]} elements, got {sigma.numel()}")
+    if sigma.numel() > 1 and sigma.stride(0) not in (0, 1):
+        sigma = sigma.contiguous()
+    return tuple(x.shape), sigma
 
 
 class DenoiserJacobian:
@@ -617,18 +701,9 @@ class DenoiserJacobian:
         ok, why = jacobian_eligibility(net)
         if not ok:
             raise ValueError(f"DenoiserJacobian: {why}")
-        self.shape = _image(x, "DenoiserJacobian")
-        if why == FFDNET_THROUGH_INPUT:
-            _even(x, "DenoiserJacobian")
-            if sigma is None:
-                raise ValueError("DenoiserJacobian: FFDNet is linearised at a noise level: sigma is required")
-            layers = ffdnet_plan(net)
-            sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1).contiguous()
-            if sigma.numel() not in (1, x.shape[0]):
-                raise ValueError(f"DenoiserJacobian: sigma must have 1 or {x.shape[0]} elements, got {sigma.numel()}")
-        else:
-            layers, sigma = host_plan(net)[0], None
-        self._stack = _MaskedStack(layers, x, sigma)
+        ffdnet = why == FFDNET_THROUGH_INPUT
+        self.shape, sigma = _image("DenoiserJacobian", x, sigma, ffdnet)
+        self._stack = _MaskedStack(ffdnet_plan(net) if ffdnet else host_plan(net)[0], x, sigma)
         self.masks = self._stack.masks
 
     def _v(self, v, what):
@@ -653,7 +728,7 @@ class DenoiserVJP:
         ok, why = eligibility(net)
         if not ok:
             raise ValueError(f"DenoiserVJP: {why}")
-        self.shape = _image(x, "DenoiserVJP")
+        self.shape = _image("DenoiserVJP", x)[0]
         self.zero = why == _FFDNET_OK
         self._stack = None if self.zero else _MaskedStack(host_plan(net)[0], x)
         self.masks = [] if self.zero else self._stack.masks
@@ -665,229 +740,106 @@ class DenoiserVJP:
 
 
 class DenoiserParamGrads:
-    """The denoiser's weight gradients on the device, for a (n,1,H,W) fp32 GPU image x: one forward pass on _MaskedStack's kernels
-    (1 -> 64 stencil, Winograd F(2x2,3x3), relu_mask_pack) that keeps the post-ReLU activations - (k-1) n 64 H W 4 bytes - and the masks;
-    .noise = D(x) from that pass (the 64 -> 1 stencil), .masks, .shape.  .grads(v) -> [dW_0 .. dW_{k-1}] = (dD/dtheta)^T v, one tensor per
-    conv weight (conv_weights(net)): the masked transposed layers of .vjp carry the gradient down, csrc/wgrad.hip's W1 serves the two edge
-    layers and W0 every 64 -> 64 layer.  need: one bool per weight - the walk stops below the lowest layer asked for, the others are None.
-    .vjp(v) is the input product J_D(x)^T v.  .release() drops the activations.  Everything is enqueued on the current stream with no host
-    synchronisation.  Raises ValueError with param_eligibility()'s reason.
+    """The denoiser's weight gradients on the device, for a (n,1,H,W) fp32 GPU image x: one forward pass of _MaskedStack that keeps the
+    post-ReLU activations - (k-1) n 64 H W 4 bytes - and the masks; .noise = D(x) from that pass, .masks, .shape, .ffdnet.  .grads(v) ->
+    (dD/dtheta)^T v, one tensor per parameter, and .vjp(v) -> the input product J_D(x)^T v are ONE walk back: the masked transposed layers
+    carry the gradient down, csrc/wgrad.hip's W1 serves the two edge layers, and every 64 -> 64 layer does what its rule says.  need: one
+    bool per parameter - the walk stops below the lowest layer asked for, the others are None.  .release() drops the activations.
+    Everything is enqueued on the current stream with no host synchronisation.  Raises ValueError with param_eligibility()'s reason.
 
-    frozen_bn=True: the nets param_eligibility(net, frozen_bn=True) accepts, the BatchNorm folded into the forward and the walk as in
-    _MaskedStack; .grads answers for grad_parameters(net) in its order (per layer dW, then dgamma, dbeta) and `need` has one bool per
-    parameter.  A 64 -> 64 layer with a BatchNorm runs csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass).
-    FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
+    The default serves the nets param_eligibility(net) accepts and answers for conv_weights(net): every 64 -> 64 layer is _Conv64 (W0).
+
+    frozen_bn=True: the nets param_eligibility(net, frozen_bn=True) accepts; .grads answers for grad_parameters(net) in its order (per
+    layer dW, then dgamma, dbeta).  A 64 -> 64 layer with a BatchNorm is _Frozen64: the BatchNorm folded into the forward and into the
+    walk, csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass) - skipped where none of the three is asked
+    for.  FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
     ffdnet_tail's, and .vjp is zero: its input is detached.
 
-    train_bn=True: the nets param_eligibility(net, train_bn=True) accepts - the BatchNorms in TRAIN mode, as the reference trains them.  The
-    forward runs per layer the raw convolution (Winograd F(2x2,3x3), no bias, no ReLU), csrc/bn_train.hip's T1 (batch statistics; the
-    module's running_mean / running_var / num_batches_tracked are updated IN PLACE on the device, exactly once per construction) and T2
-    (normalise + ReLU + the mask words in one pass), and keeps per BatchNorm layer the convolution output c AND the post-ReLU activation:
-    (2 (k-2) + 1) n 64 H W 4 bytes for k layers (FFDNet: 27 activations at half resolution), twice the frozen mode's.  .grads answers for
-    grad_parameters(net, train_bn=True): T3 (dgamma, dbeta) -> T4 (dc, in place) -> W0 on dc -> the masked transposed Winograd layer with
-    the plain (unfolded) transposed weight.  .vjp(v) is the true input product, the statistic terms included (FFDNet: zero)."""
+    train_bn=True: the nets param_eligibility(net, train_bn=True) accepts - the BatchNorms in TRAIN mode, as the reference trains them -
+    and grad_parameters(net, train_bn=True).  A 64 -> 64 layer with a BatchNorm is _Train64: csrc/bn_train.hip's T1 updates the module's
+    running_mean / running_var / num_batches_tracked IN PLACE on the device, exactly once per construction, and the layer keeps its
+    convolution output c beside the post-ReLU activation: (2 (k-2) + 1) n 64 H W 4 bytes for k layers (FFDNet: 27 activations at half
+    resolution), twice the frozen mode's.  T3 and T4 run wherever the walk passes, asked for or not: dc is what goes down, through the
+    plain (unfolded) transposed weight, so .vjp(v) is the true input product, the statistic terms included (FFDNet: zero)."""
 
     def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False):
-        self._train = None
-        if train_bn:
-            if frozen_bn:
-                raise ValueError("DenoiserParamGrads: frozen_bn and train_bn exclude one another")
-            self._init_train_bn(net, x, sigma)
-            return
-        ok, why = param_eligibility(net, frozen_bn=frozen_bn)
-        if not ok:
+        train = _bn_mode("DenoiserParamGrads", frozen_bn, train_bn)
+        stack, self.ffdnet, why = bn_stack(net, train)
+        if stack is None:
             raise ValueError(f"DenoiserParamGrads: {why}")
-        self.shape = _image(x, "DenoiserParamGrads")
+        self.shape, self._sigma = _image("DenoiserParamGrads", x, sigma, self.ffdnet)
         self._x = _hip.f32c(x.detach())
-        n, _, H, W = self.shape
-        self.ffdnet = why == _FROZEN_FFDNET_OK
-        self._sigma, self._bn, self._ws_bn = None, None, None
-        if self.ffdnet:
-            _even(x, "DenoiserParamGrads")
-            if sigma is None:
-                raise ValueError("DenoiserParamGrads: FFDNet is evaluated at a noise level: sigma is required")
-            self._sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1)
-            if self._sigma.numel() not in (1, n):
-                raise ValueError(f"DenoiserParamGrads: sigma must have 1 or {n} elements, got {self._sigma.numel()}")
-            if self._sigma.numel() > 1 and self._sigma.stride(0) not in (0, 1):
-                self._sigma = self._sigma.contiguous()
-            self._stack = _MaskedStack(ffdnet_plan(net), self._x, self._sigma, keep=True)
-            self.noise = _hip.ffdnet_tail(self._stack.acts[-1], self._stack.tail_f)
-            H, W = H // 2, W // 2
-        else:
-            self._stack = _MaskedStack(host_plan(net)[0], self._x, keep=True)
-            self.noise = _hip.conv3x3_c64_to_1(self._stack.acts[-1], self._stack.tail_f)
-        self.masks = self._stack.masks
-        plain = True
-        if frozen_bn:
-            stack = _frozen_bn_stack(net)[0]
-            dev = lambda t, dt=torch.float32: t.detach().to(x.device, dt).contiguous()
-            self._bn = []                                                    # per layer None, or (w, s fp32; mean, 1 / sqrt(var + eps) float64)
-            for conv, bn, _ in stack:
-                if bn is None:
-                    self._bn.append(None)
-                else:
-                    inv = 1.0 / torch.sqrt(dev(bn.running_var, torch.float64) + bn.eps)
-                    self._bn.append((dev(conv.weight), (dev(bn.weight, torch.float64) * inv).float(), dev(bn.running_mean, torch.float64), inv))
-            if self.ffdnet or any(b is not None for b in self._bn):
-                self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, self._x.device)
-            plain = not self.ffdnet or any(b is None for b in self._bn[1:-1])
-        self._ws = _hip.wgrad_workspace(n, H, W, self._x.device) if plain else None
+        n, H, W = (self.shape[0], self.shape[2] // 2, self.shape[3] // 2) if self.ffdnet else (self.shape[0],) + self.shape[2:]
+        if train and n * H * W < 2:
+            raise ValueError(f"DenoiserParamGrads: expected more than 1 value per channel when training, got {n * H * W}")
+        kinds = [_Conv64 if bn is None else _Train64 if train else _Frozen64 for _, bn, _ in stack[1:-1]]
+        ws_train = _hip.bn_train_workspace(n * H * W, x.device) if _Train64 in kinds else None
+        layers = [(conv.weight.detach(), None, relu) for conv, _, relu in stack] if train else folded(stack)
+        f32 = lambda t: t.to(x.device, torch.float32)
+        with torch.no_grad():
+            rules = [_Conv64(f32(w), b) if kind is _Conv64 else _Train64(f32(w), bn, ws_train) if train else _Frozen64(f32(w), b, conv, bn)
+                     for kind, (conv, bn, _), (w, b, _) in zip(kinds, stack[1:-1], layers[1:-1])]
+        self._stack = _MaskedStack(layers, self._x, self._sigma, keep=True, rules=rules, through_input=not self.ffdnet)
+        self._counts = [1] + [r.count for r in rules] + [1]                 # parameters per layer
+        self.masks, self.noise = self._stack.masks, self._stack.noise
+        # the scratch buffers of the walk's kernels, behind the forward's activations: W1 and W0 share one, W2 and W0-BN the other
+        self._ws = _hip.wgrad_workspace(n, H, W, x.device) if not self.ffdnet or not all(k.bn_workspace for k in kinds) else None
+        self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, x.device) if self.ffdnet or any(k.bn_workspace for k in kinds) else None
+        for rule in rules:
+            rule.ws = self._ws_bn if rule.bn_workspace else self._ws
 
     def _v(self, v, what):
         if tuple(v.shape) != self.shape:
             raise _hip.DeqsciHipError(f"DenoiserParamGrads.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
         return _hip.f32c(v)
 
-    def _init_train_bn(self, net, x, sigma):
-        stack, ffdnet, why = _bn_stack(net, True)
-        if stack is None:
-            raise ValueError(f"DenoiserParamGrads: {why}")
-        self.shape = _image(x, "DenoiserParamGrads")
-        self._x = _hip.f32c(x.detach())
-        n, _, H, W = self.shape
-        self.ffdnet, self._sigma = ffdnet, None
-        if ffdnet:
-            _even(x, "DenoiserParamGrads")
-            if sigma is None:
-                raise ValueError("DenoiserParamGrads: FFDNet is evaluated at a noise level: sigma is required")
-            self._sigma = torch.as_tensor(sigma, dtype=torch.float32, device=x.device).reshape(-1)
-            if self._sigma.numel() not in (1, n):
-                raise ValueError(f"DenoiserParamGrads: sigma must have 1 or {n} elements, got {self._sigma.numel()}")
-            if self._sigma.numel() > 1 and self._sigma.stride(0) not in (0, 1):
-                self._sigma = self._sigma.contiguous()
-            H, W = H // 2, W // 2
-        if n * H * W < 2:
-            raise ValueError(f"DenoiserParamGrads: expected more than 1 value per channel when training, got {n * H * W}")
-        dev = lambda t: t.detach().to(x.device, torch.float32).contiguous()
-        t = self._train = type("_TrainBN", (), {})()
-        with torch.no_grad():
-            w0, wt = dev(stack[0][0].weight), dev(stack[-1][0].weight)
-            if ffdnet:
-                t.tail_f, t.tail_t, t.head_t = _hip.pack_tail_weights(wt), _hip.pack_head_masked_weights(_transposed(wt)), None
-                h = _hip.ffdnet_head(self._x, _hip.pack_head_weights(w0), self._sigma)
-            else:
-                t.tail_f, t.tail_t = _hip.pack_c64_to_1_weights(wt), _hip.pack_c1_to_64_weights(_transposed(wt))
-                t.head_t = _hip.pack_c64_to_1_weights(_transposed(w0))
-                h = _hip.conv3x3_c1_to_64(self._x, _hip.pack_c1_to_64_weights(w0), relu=True)
-            t.ws = _hip.bn_train_workspace(n * H * W, x.device)
-            self.masks, t.acts, t.layers = [_hip.relu_mask_pack(h)], [h], []        # layers[i - 1] of 64 -> 64 layer i: (transposed pack, bn state)
-            for conv, bn, _ in stack[1:-1]:
-                w = dev(conv.weight)
-                u, ut = _hip.pack_winograd_weights(w), _hip.pack_winograd_weights(_transposed(w))
-                if bn is None:
-                    h = _hip.conv3x3_c64_winograd(h, u, None, True)
-                    self.masks.append(_hip.relu_mask_pack(h))
-                    t.layers.append((ut, None))
-                else:
-                    c = _hip.conv3x3_c64_winograd(h, u, None, False)
-                    rec = _hip.bn_train_stats(c, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, workspace=t.ws)
-                    gamma = dev(bn.weight)
-                    h, mk = _hip.bn_train_apply(c, rec, gamma, dev(bn.bias), bn.eps, relu=True, want_mask=True)
-                    self.masks.append(mk)
-                    t.layers.append((ut, (c, rec, gamma, float(bn.eps))))
-                t.acts.append(h)
-            self.noise = (_hip.ffdnet_tail if ffdnet else _hip.conv3x3_c64_to_1)(h, t.tail_f)
-        self._ws = _hip.wgrad_workspace(n, H, W, x.device)
-        self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, x.device) if ffdnet else None
+    def _edge(self, img, t, which):
+        """The weight gradient of the first (which = 0) or the last (1) layer from the image side img and the 64-channel side t."""
+        if self.ffdnet:
+            return _hip.wgrad_shuffle(img, t, which, None if which else self._sigma, self._ws_bn)
+        return _hip.wgrad_c1_c64(img, t, which, self._ws)
 
-    def _walk_train_bn(self, v, need, want_input):
-        """The walk back in train mode: (gradients in grad_parameters(net, train_bn=True) order - None where not needed, the input product or None)."""
-        t = self._train
-        if t.acts is None:
-            raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
-        k = len(t.layers) + 2
-        counts = [1] + [1 if bn is None else 3 for _, bn in t.layers] + [1]
+    def _walk(self, v, need, want_input):
+        """The walk back from the gradient v of the noise.  -> (one gradient per parameter - None where `need` is false -, J_D(x)^T v if
+        want_input, else None).  Nothing asked for launches nothing."""
+        st, counts = self._stack, self._counts
+        k, total = len(counts), sum(counts)
         first = [sum(counts[:i]) for i in range(k)]
-        total = sum(counts)
-        need = [False] * total if need is None else [bool(b) for b in need]
+        need = [bool(b) for b in need]
         if len(need) != total:
             raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {total} parameters")
         out = [None] * total
         if not any(need) and not want_input:
             return out, None
+        acts = st.acts if st.acts is not None else [None] * (k - 1)
         wanted = [any(need[first[i]:first[i] + counts[i]]) for i in range(k)]
         lowest = -1 if want_input else wanted.index(True)
         if wanted[k - 1]:
-            out[first[k - 1]] = (_hip.wgrad_shuffle(v, t.acts[-1], 1, None, self._ws_bn) if self.ffdnet
-                                 else _hip.wgrad_c1_c64(v, t.acts[-1], 1, self._ws))
+            out[first[k - 1]] = self._edge(v, acts[-1], 1)
         if lowest == k - 1:
             return out, None
-        g = (_hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked)(v, t.tail_t, self.masks[-1])
+        g = st._first(v, st.tail_t, st.masks[-1])                          # the gradient behind layer k-2, masked by its ReLU
         for i in range(k - 2, 0, -1):
-            ut, bn = t.layers[i - 1]
-            got = [None] * counts[i]
-            if bn is not None:
-                c, rec, gamma, eps = bn
-                got[1], got[2], grec = _hip.bn_train_grad_stats(g, c, rec, eps, t.ws)
-                g = _hip.bn_train_grad_apply(g, c, rec, grec, gamma, eps, out=g)         # dc, statistic terms included, in place
-            if need[first[i]]:
-                got[0] = _hip.wgrad_c64_c64(t.acts[i - 1], g, self._ws)
-            for j, tensor in enumerate(got):
-                out[first[i] + j] = tensor if need[first[i] + j] else None
+            mine = slice(first[i], first[i] + counts[i])
+            got, g = st.rules[i - 1].backward(acts[i - 1], g, need[mine])
+            out[mine] = [t if b else None for t, b in zip(got, need[mine])]
             if i == lowest:
                 return out, None
-            g = _hip.conv3x3_c64_winograd_masked(g, ut, self.masks[i - 1])
+            g = _hip.conv3x3_c64_winograd_masked(g, st.mid_t[i - 1], st.masks[i - 1])
         if need[0]:
-            out[0] = _hip.wgrad_shuffle(self._x, g, 0, self._sigma, self._ws_bn) if self.ffdnet else _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
-        return out, (_hip.conv3x3_c64_to_1(g, t.head_t) if want_input else None)
+            out[0] = self._edge(self._x, g, 0)
+        return out, (st._last(g, st.head_t) if want_input else None)
+
+    def grads(self, v, need=None):
+        if self._stack.acts is None:
+            raise RuntimeError(_RELEASED)
+        return self._walk(self._v(v, "grads"), [True] * sum(self._counts) if need is None else need, False)[0]
 
     def vjp(self, v):
         v = self._v(v, "vjp")
-        if self.ffdnet:
-            return torch.zeros_like(v)
-        return self._walk_train_bn(v, None, True)[1] if self._train is not None else self._stack.vjp(v)
-
-    def _middle(self, i, g):
-        """[dW] of 64 -> 64 layer i, or [dW, dgamma, dbeta] where it has a BatchNorm, from its input and the masked gradient g behind it."""
-        st = self._stack
-        bn = None if self._bn is None else self._bn[i]
-        if bn is None:
-            return [_hip.wgrad_c64_c64(st.acts[i - 1], g, self._ws)]
-        w, s, mean, inv = bn
-        dw, dsum, ddot = _hip.wgrad_c64_c64_bn(st.acts[i - 1], g, w, s, self._ws_bn)
-        return [dw, ((ddot.double() - mean * dsum.double()) * inv).float(), dsum]
-
-    def grads(self, v, need=None):
-        if self._train is not None:
-            total = 2 + sum(1 if bn is None else 3 for _, bn in self._train.layers)
-            return self._walk_train_bn(self._v(v, "grads"), [True] * total if need is None else need, False)[0]
-        st = self._stack
-        if st.acts is None:
-            raise RuntimeError("DenoiserParamGrads.grads: the activations were released")
-        k = len(st.mid_t) + 2
-        counts = [1] * k if self._bn is None else [1 if b is None else 3 for b in self._bn]      # parameters per layer
-        first = [sum(counts[:i]) for i in range(k)]
-        total = sum(counts)
-        need = [True] * total if need is None else [bool(b) for b in need]
-        if len(need) != total:
-            raise ValueError(f"DenoiserParamGrads.grads: need has {len(need)} entries for {total} parameters")
-        v = self._v(v, "grads")
-        out = [None] * total
-        if not any(need):
-            return out
-        wanted = [any(need[first[i]:first[i] + counts[i]]) for i in range(k)]
-        lowest = wanted.index(True)
-        if wanted[k - 1]:
-            out[first[k - 1]] = (_hip.wgrad_shuffle(v, st.acts[-1], 1, None, self._ws_bn) if self.ffdnet
-                                 else _hip.wgrad_c1_c64(v, st.acts[-1], 1, self._ws))
-        if lowest == k - 1:
-            return out
-        # the gradient behind layer k-2, masked by its ReLU
-        g = (_hip.ffdnet_head_masked if self.ffdnet else _hip.conv3x3_c1_to_64_masked)(v, st.tail_t, st.masks[-1])
-        for i in range(k - 2, 0, -1):
-            if wanted[i]:
-                for j, t in enumerate(self._middle(i, g)):
-                    out[first[i] + j] = t if need[first[i] + j] else None
-            if i == lowest:
-                return out
-            g = _hip.conv3x3_c64_winograd_masked(g, st.mid_t[i - 1], st.masks[i - 1])
-        out[0] = _hip.wgrad_shuffle(self._x, g, 0, self._sigma, self._ws_bn) if self.ffdnet else _hip.wgrad_c1_c64(self._x, g, 0, self._ws)
-        return out
+        return torch.zeros_like(v) if self.ffdnet else self._walk(v, [False] * sum(self._counts), True)[1]
 
     def release(self):
-        if self._train is not None:
-            self._train.acts = None
-            self._train.layers = [(ut, None if bn is None else (None,) + bn[1:]) for ut, bn in self._train.layers]
-        else:
-            self._stack.acts = None
+        self._stack.acts = None
+        for rule in self._stack.rules:
+            rule.release()

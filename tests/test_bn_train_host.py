@@ -15,7 +15,7 @@ from deqsci_amd import _hip, checkpoint, vjp
 from deqsci_amd.cli import build_denoiser, build_pipeline
 from deqsci_amd.layers import conv_bn_stack, conv_stack
 from deqsci_amd.networks import DnCNN, FFDNet
-from test_wgrad_bn_host import seeded_bn_dncnn, seeded_ffdnet
+from test_wgrad_bn_host import mixed_bn_dncnn, seeded_bn_dncnn, seeded_ffdnet
 
 OLD_REFUSAL = "BatchNorm2d in train mode (batch statistics have no device kernel)"
 
@@ -164,6 +164,16 @@ def test_plan_param_grads_train_bn_equals_float64_autograd():
         vjp.plan_param_grads_train_bn(ffd, x, v)
     with pytest.raises(ValueError, match="more than 1 value per channel"):
         vjp.plan_forward_train_bn(seeded_bn_dncnn(3, 1).train(), torch.zeros(1, 1, 1, 1))
+
+
+def test_plan_param_grads_train_bn_equals_float64_autograd_mixed_net():
+    """64 -> 64 layers with and without a BatchNorm in one stack: the walk takes a rule per layer."""
+    net = mixed_bn_dncnn().double().train()
+    assert vjp.param_eligibility(net, train_bn=True) == (True, "bias-free conv [+ train-mode BN] + ReLU stack")
+    g = torch.Generator().manual_seed(8)
+    x = torch.rand(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    v = torch.randn(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    assert len(_check_against_autograd(net, x, v, None)) == 2 + 3 + 1 + 3
 
 
 def test_golden_one_fcall_through_the_host_plan():

@@ -200,7 +200,7 @@ def _masked_float64(net, masks):
     """(float64 copy of the module with every ReLU replaced by `h * mask` - the device forward's decisions; its layer sequence, its
     conv_bn_stack and its grad_parameters)."""
     m64 = copy.deepcopy(net).double()
-    stack, params = vjp._frozen_bn_stack(m64)[0], vjp.grad_parameters(m64)      # (read before the ReLUs go: the walk knows no _FixedMask)
+    stack, params = vjp.bn_stack(m64, False)[0], vjp.grad_parameters(m64)      # (read before the ReLUs go: the walk knows no _FixedMask)
     seq, k = (m64.intermediate_dncnn.itermediate_dncnn if hasattr(m64, "intermediate_dncnn") else m64.dncnn), 0
     for i, mod in enumerate(list(seq)):
         if isinstance(mod, torch.nn.ReLU):

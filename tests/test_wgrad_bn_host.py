@@ -162,6 +162,122 @@ def test_plan_param_grads_frozen_bn_equals_float64_autograd_bn_dncnn():
     assert all(torch.equal(p, q) for p, q in zip(a, b))
 
 
+def mixed_bn_dncnn():
+    """seeded_bn_dncnn(5, 6) without its second BatchNorm: 64 -> 64 layers with and without one in the same stack (eval mode)."""
+    net = seeded_bn_dncnn(5, 6)
+    del net.dncnn[[i for i, m in enumerate(net.dncnn) if isinstance(m, torch.nn.BatchNorm2d)][1]]
+    return net
+
+
+def test_plan_param_grads_frozen_bn_equals_float64_autograd_mixed_net():
+    net = mixed_bn_dncnn().double()
+    assert vjp.param_eligibility(net, frozen_bn=True) == (True, "bias-free conv [+ frozen BN] + ReLU stack")
+    g = torch.Generator().manual_seed(8)
+    x = torch.rand(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    v = torch.randn(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    assert len(_check_against_autograd(net, x, v, None)) == 2 + 3 + 1 + 3
+
+
+def test_a_plain_net_gets_the_same_gradients_from_all_three_host_statements():
+    """One walk: without a BatchNorm the three statements run the same rule in the same order, so their gradients are bit-equal."""
+    net = build_pipeline("SimpleCNN", checkpoint.shipped("cnn"), 4, device="cpu")[0].nonlinear_op.double()
+    g = torch.Generator().manual_seed(9)
+    x = torch.rand(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    v = torch.randn(2, 1, 12, 20, generator=g, dtype=torch.float64)
+    plain, masks = vjp.plan_param_grads(vjp.host_plan(net)[0], x, v)
+    frozen, _ = vjp.plan_param_grads_frozen_bn(net.eval(), x, v)
+    train, masks_train, gx = vjp.plan_param_grads_train_bn(net.train(), x, v, input_grad=True)
+    assert len(plain) == len(frozen) == len(train) == len(vjp.conv_weights(net))
+    assert all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(plain, frozen, train))
+    assert all(torch.equal(a, b) for a, b in zip(masks, masks_train)) and torch.equal(gx, vjp.plan_vjp(vjp.host_plan(net)[0], x, v)[0])
+
+
+# ----------------------------------------------------------------------------- one structure check behind every entry point
+def _convs(seq):
+    return [i for i, m in enumerate(seq) if isinstance(m, torch.nn.Conv2d)]
+
+
+def _wrong_middle_shape(seq):
+    seq[_convs(seq)[1]] = torch.nn.Conv2d(32, 64, kernel_size=3, padding=1, bias=False)
+
+
+def _missing_relu(seq):
+    del seq[[i for i, m in enumerate(seq) if isinstance(m, torch.nn.ReLU)][1]]
+
+
+def _relu_behind_the_last(seq):
+    seq.append(torch.nn.ReLU())
+
+
+def _bn_behind_the_first(seq):
+    seq.insert(1, torch.nn.BatchNorm2d(64))
+
+
+def _bn_behind_the_last(seq):
+    seq.append(torch.nn.BatchNorm2d(seq[_convs(seq)[-1]].out_channels))
+
+
+def _too_few_layers(seq):
+    del seq[2:]
+
+
+def _weight_no_parameter(seq):
+    conv = seq[_convs(seq)[1]]
+    w = conv.weight.detach().clone()
+    del conv.weight
+    conv.register_buffer("weight", w)
+
+
+# malformation -> (the cause every entry point names, the entry points that look at weights as nn.Parameters only)
+MALFORMED = {_wrong_middle_shape: ("layer shapes", False), _missing_relu: ("ReLU pattern", False), _relu_behind_the_last: ("ReLU pattern", False),
+             _bn_behind_the_first: ("BatchNorm2d behind the first or the last layer", False),
+             _bn_behind_the_last: ("BatchNorm2d behind the first or the last layer", False), _too_few_layers: ("layer shapes", False),
+             _weight_no_parameter: ("not an nn.Parameter", True)}
+FAMILIES = {"plain": lambda: DnCNN(1, num_of_layers=5, lip=0.0, no_bn=True, tag="denoiser"), "bn-dncnn": lambda: seeded_bn_dncnn(5, 1),
+            "ffdnet": lambda: seeded_ffdnet(1)}
+
+
+def _raised(fn, *args, **kw):
+    with pytest.raises(ValueError) as info:
+        fn(*args, **kw)
+    return False, str(info.value)
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("malform", list(MALFORMED), ids=lambda f: f.__name__.strip("_"))
+def test_every_entry_point_refuses_a_malformed_stack_with_the_same_cause(malform, family):
+    """eligibility, jacobian_eligibility, param_eligibility in its three modes, grad_parameters and ffdnet_plan all ask vjp._structure_refusal
+    (the parameter entry points through vjp.bn_stack): a malformed stack is refused everywhere, for the same cause."""
+    cause, parameters_only = MALFORMED[malform]
+    net = FAMILIES[family]()
+    seq = net.intermediate_dncnn.itermediate_dncnn if family == "ffdnet" else net.dncnn
+    assert vjp.param_eligibility(net.eval(), frozen_bn=True)[0] and vjp.param_eligibility(net.train(), train_bn=True)[0]
+    malform(seq)
+    answers = {}
+    net.eval()
+    if not parameters_only:
+        if family == "ffdnet":
+            answers["ffdnet_plan"] = _raised(vjp.ffdnet_plan, net)
+        else:
+            answers["eligibility"], answers["jacobian_eligibility"] = vjp.eligibility(net), vjp.jacobian_eligibility(net)
+    elif family == "ffdnet":
+        assert len(vjp.ffdnet_plan(net)) == 15                                  # (the input product needs no nn.Parameter)
+    else:
+        assert vjp.eligibility(net)[0] and vjp.jacobian_eligibility(net)[0]
+    if family == "plain" and "BatchNorm2d" not in cause:                       # (the default mode refuses any BatchNorm2d before it looks further)
+        answers["param_eligibility"] = vjp.param_eligibility(net)
+    answers["param_eligibility frozen"] = vjp.param_eligibility(net, frozen_bn=True)
+    answers["grad_parameters"] = _raised(vjp.grad_parameters, net)
+    net.train()
+    answers["param_eligibility train"] = vjp.param_eligibility(net, train_bn=True)
+    answers["grad_parameters train"] = _raised(vjp.grad_parameters, net, train_bn=True)
+    for who, (ok, why) in answers.items():
+        assert not ok and cause in why, (who, why)
+    if family == "plain" and "BatchNorm2d" in cause:
+        ok, why = vjp.param_eligibility(net)
+        assert not ok and "BatchNorm2d" in why
+
+
 def test_deq_switch_accepts_device_bn_and_refuses_a_misspelling():
     import deqsci_amd
     solver, deq = build_pipeline("ffdnet", checkpoint.shipped("ffdnet_gray"), 4, device="cpu")
