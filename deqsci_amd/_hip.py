@@ -91,6 +91,7 @@ SIGNATURES = {
     "deqsci_wgrad3x3_shuffle_f32": [_ptr, _ptr, _i64, _ptr, _ptr, _int, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_realsn_power_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _int, _f32, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
     "deqsci_realsn_grad_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f32, _i64, _i64, _i64, _i64, _ptr, _ptr],
+    "deqsci_realsn_pack_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr],
     "deqsci_bn_train_stats_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _i64, _ptr, _ptr],
     "deqsci_bn_train_apply_f32": [_ptr, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _int, _i64, _ptr],
     "deqsci_bn_train_grad_stats_f32": [_ptr, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr],
@@ -1535,9 +1536,10 @@ class Conv64Weights:
     - the engine does whenever its policy can pick that kernel, so that the pack never falls inside a hipGraph capture - or on first use."""
     __slots__ = ("f22", "f44", "_w", "_s16", "_w16")
 
-    def __init__(self, w, s16=False):
-        self.f22 = pack_winograd_weights(w)
-        self.f44 = pack_winograd44_weights(w)
+    def __init__(self, w, s16=False, f22=None, f44=None):
+        # f22 / f44: the caller's own pack buffers, which realsn_pack fills on the device (a weight that changes at every f-call)
+        self.f22 = pack_winograd_weights(w) if f22 is None else f22
+        self.f44 = pack_winograd44_weights(w) if f44 is None else f44
         self._w, self._s16, self._w16 = w.detach(), None, None
         if s16:
             self._s16 = Split16Weights(self._w)
@@ -1775,18 +1777,23 @@ def realsn_workspace(cin, cout, h, w, device):
     return _partials(nbytes, device)
 
 
-def realsn_power(W, u, n_iters=1, sigma=1.0, eps=1e-12, workspace=None):
+def realsn_power(W, u, n_iters=1, sigma=1.0, eps=1e-12, workspace=None, weight=None, v=None, record=None):
     """n_iters power-iteration steps of a spectrally normalised 3x3 convolution (conv_sn_chen.py:29-50 in the reference) and the
     normalised weight, R1 of csrc/realsn.hip: u (1, C_out, h, w) is read and OVERWRITTEN with the new left vector.
     -> (weight = W / cur_sigma * sigma, u, v (1, C_in, h, w), record): record = float64 (|W^T u|, |W v|, cur_sigma) of the last
-    iteration, on the device.  3 n_iters + 1 launches, no host synchronisation."""
+    iteration, on the device.  3 n_iters + 1 launches, no host synchronisation.  weight / v / record: the caller's own buffers to write
+    (a module's `weight` buffer, in place); with all three and the workspace given the call allocates nothing."""
     cin, cout, h, w = _realsn_dims(W, u, "realsn_power")
     if int(n_iters) < 1:
         raise DeqsciHipError(f"realsn_power: n_iters must be at least 1, got {n_iters}")
     ws = realsn_workspace(cin, cout, h, w, W.device) if workspace is None else workspace
-    v = torch.empty((1, cin, h, w), device=W.device, dtype=torch.float32)
-    weight = torch.empty_like(W)
-    record = torch.empty((3,), device=W.device, dtype=torch.float64)
+    v = torch.empty((1, cin, h, w), device=W.device, dtype=torch.float32) if v is None else v
+    weight = torch.empty_like(W) if weight is None else weight
+    record = torch.empty((3,), device=W.device, dtype=torch.float64) if record is None else record
+    if tuple(weight.shape) != tuple(W.shape) or v.numel() != cin * h * w or record.dtype != torch.float64 or record.numel() != 3 \
+            or not record.is_contiguous() or record.device != W.device:
+        raise DeqsciHipError(f"realsn_power: weight must have W's shape {tuple(W.shape)}, v {cin * h * w} elements, record 3 float64 on W's device")
+    _p(v, "v")
     with _dev(W):
         _check(load().deqsci_realsn_power_f32(_p(W, "W"), _p(u, "u"), v.data_ptr(), _p(weight, "weight"), record.data_ptr(), int(n_iters),
                                               float(sigma), float(eps), cin, cout, h, w, ws.data_ptr(), _stream()), "realsn_power")
@@ -1807,6 +1814,50 @@ def realsn_grad(G, W, u, v, record, sigma=1.0, workspace=None):
         _check(load().deqsci_realsn_grad_f32(_p(G, "G"), _p(W, "W"), _p(u, "u"), _p(v, "v"), record.data_ptr(), _p(dW, "dW"), float(sigma),
                                              cin, cout, h, w, ws.data_ptr(), _stream()), "realsn_grad")
     return dW
+
+
+# the shapes of the host packers' outputs: pack_winograd_weights, pack_winograd44_weights, pack_c1_to_64_weights, pack_c64_to_1_weights
+_PACK_F22, _PACK_F44, _PACK_WIDE, _PACK_NARROW = (8, 16, 2, 4, 16, 2, 2), (8, 3, 6, 2, 2, 4, 16, 2, 2), (9, 16, 4), (2, 9, 32)
+
+
+def realsn_pack_shapes(cin, cout):
+    """{"pack", "pack44", "pack_t"} -> the shape of each pack realsn_pack writes for a (cout, cin, 3, 3) weight (pack44: None for an
+    edge layer) - the shapes of the host packers' own outputs."""
+    if (cin, cout) == (64, 64):
+        return {"pack": _PACK_F22, "pack44": _PACK_F44, "pack_t": _PACK_F22}
+    if (cin, cout) == (1, 64):
+        return {"pack": _PACK_WIDE, "pack44": None, "pack_t": _PACK_NARROW}
+    if (cin, cout) == (64, 1):
+        return {"pack": _PACK_NARROW, "pack44": None, "pack_t": _PACK_WIDE}
+    raise DeqsciHipError(f"realsn_pack: no kernel for a ({cout},{cin},3,3) weight: (C_in, C_out) must be (1,64), (64,64) or (64,1)")
+
+
+def realsn_pack_buffers(cin, cout, device, pack=True, pack44=True, pack_t=True):
+    """(pack, pack44, pack_t): the caller-owned buffers of realsn_pack for a (cout, cin, 3, 3) weight, uninitialised; None for a pack that
+    is not wanted or does not exist."""
+    shapes = realsn_pack_shapes(cin, cout)
+    return tuple(torch.empty(shapes[k], device=device, dtype=torch.float32) if want and shapes[k] is not None else None
+                 for k, want in (("pack", pack), ("pack44", pack44), ("pack_t", pack_t)))
+
+
+def realsn_pack(weight, pack=None, pack44=None, pack_t=None):
+    """R3 of csrc/realsn.hip: the (cout, cin, 3, 3) weight realsn_power wrote -> the packs the convolution kernels read, written into the
+    caller's buffers (realsn_pack_buffers; None: not wanted) by ONE launch with no host synchronisation, host -> device copy or allocation.
+    (64,64): pack = pack_winograd_weights(w), pack44 = pack_winograd44_weights(w), pack_t = pack_winograd_weights(vjp._transposed(w)) - U =
+    G g G^T in float64 in the one order include/deqsci_hip.h states, rounded once, so equal to the host packers up to that last rounding.
+    (1,64): pack = pack_c1_to_64_weights(w), pack_t = pack_c64_to_1_weights(_transposed(w)); (64,1): pack = pack_c64_to_1_weights(w),
+    pack_t = pack_c1_to_64_weights(_transposed(w)) - bit for bit.  -> (pack, pack44, pack_t)."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise DeqsciHipError(f"realsn_pack: weight must be (C_out, C_in, 3, 3), got {tuple(weight.shape)}")
+    cout, cin = int(weight.shape[0]), int(weight.shape[1])
+    shapes = realsn_pack_shapes(cin, cout)
+    for name, t in (("pack", pack), ("pack44", pack44), ("pack_t", pack_t)):
+        if t is not None and (shapes[name] is None or t.numel() != math.prod(shapes[name]) or t.device != weight.device):
+            raise DeqsciHipError(f"realsn_pack: {name} must hold {shapes[name]} floats on the weight's device, got {tuple(t.shape)} on {t.device}")
+    with _dev(weight):
+        _check(load().deqsci_realsn_pack_f32(_p(weight, "weight"), _p(pack, "pack", True), _p(pack44, "pack44", True), _p(pack_t, "pack_t", True),
+                                             cin, cout, _stream()), "realsn_pack")
+    return pack, pack44, pack_t
 
 
 # ----------------------------------------------------------------------------- Broyden (csrc/broyden.hip)

@@ -11,6 +11,11 @@
 //      T1 cgrad_kernel            C[o,i,ky,kx] = sum_p u[o,p] v[i, p + (ky-1, kx-1)], one wave per (o, i); its first workgroups form the
 //                                 float64 chunk sums of G * W instead
 //      T2 grad_final_kernel       dW = (sigma_t / cur_sigma) * (G - (sum(G W) / cur_sigma) * C)
+//   R3 deqsci_realsn_pack_f32, one launch: the weight R1 wrote -> the packs the convolution kernels read, so that a weight that changes at
+//      every f-call never goes through the host packers (a dozen torch operations and a host -> device copy of G each)
+//      pack64_kernel              (64,64): U = G g G^T of F(2x2,3x3) and of F(4x4,3x3) in the MFMA-lane order of csrc/winograd.hip /
+//                                 csrc/winograd44.hip, and the F(2x2,3x3) pack of the transposed weight; float64, one rounding to fp32
+//      pack_edge_kernel           (1,64) / (64,1): the two stencil packs (csrc/ffdnet_edges.hip) of the layer and of its transpose, permutations
 //
 // A norm gates the stage behind it, so a stage boundary is a launch boundary: every workgroup of the next launch folds the partial sums
 // itself, in the same order (rows::wave_fold), and gets the same bits.  No atomics, no counters: bit-equal run to run.
@@ -246,6 +251,90 @@ __global__ __launch_bounds__(TB) void grad_final_kernel(const float* __restrict_
     store4(dW, e, N, true, f4(a) * (load4(G, e, N, true) - sc));
 }
 
+// ---- R3: the weight R1 wrote -> the packs the convolution kernels read
+// The Winograd weight transforms, the constants of _hip.pack_winograd_weights / pack_winograd44_weights as doubles
+__constant__ double G22[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+__constant__ double G44[6][3] = {{1.0 / 4.0, 0.0, 0.0},
+                                 {-1.0 / 6.0, -1.0 / 6.0, -1.0 / 6.0},
+                                 {-1.0 / 6.0, 1.0 / 6.0, -1.0 / 6.0},
+                                 {1.0 / 24.0, 1.0 / 12.0, 1.0 / 6.0},
+                                 {1.0 / 24.0, -1.0 / 12.0, 1.0 / 6.0},
+                                 {0.0, 0.0, 1.0}};
+constexpr int PACK_LANES = 256;                           // the (q, i, j, s) positions of one (cin chunk, cout half): contiguous in both packs
+constexpr int64_t PACK22 = 64 * 64 * 16, PACK44 = 64 * 64 * 36, PACK_EDGE = 64 * 9;
+static_assert(PACK_LANES == TB, "one thread per (q, i, j, s) position");
+
+// U[a][b] = sum_k (sum_j G[a][j] g[j][k]) G[b][k] in float64: T = G g first, then T G^T; every sum left to right from its first product (the
+// zero entries of G are multiplied and added like the others), every product and sum rounded by itself; one rounding to fp32 at the store
+template <int R>
+__device__ __forceinline__ void transform(const double (&G)[R][3], const double (&g)[3][3], double (&T)[R][3]) {
+#pragma unroll
+    for (int a = 0; a < R; ++a) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            T[a][k] = __dadd_rn(__dadd_rn(__dmul_rn(G[a][0], g[0][k]), __dmul_rn(G[a][1], g[1][k])), __dmul_rn(G[a][2], g[2][k]));
+    }
+}
+template <int R>
+__device__ __forceinline__ float transformed(const double (&G)[R][3], const double (&T)[R][3], int a, int b) {
+    return (float)__dadd_rn(__dadd_rn(__dmul_rn(T[a][0], G[b][0]), __dmul_rn(T[a][1], G[b][1])), __dmul_rn(T[a][2], G[b][2]));
+}
+
+// (64,64,3,3) weight -> blockIdx.y = 0: the F(2x2,3x3) pack, 1: the F(4x4,3x3) pack, 2: the F(2x2,3x3) pack of the transposed weight
+// (wt[co, ci, ky, kx] = w[ci, co, 2 - ky, 2 - kx]).  blockIdx.x = 2 c + wn; thread = (q, i, j, s): cout = 32 wn + 16 j + i, cin = 8 c + 2 q + s,
+// so that every store of a workgroup is 256 consecutive floats.  A NULL pack's workgroups return at once.
+__global__ __launch_bounds__(TB) void pack64_kernel(const float* __restrict__ w, float* __restrict__ u22, float* __restrict__ u44,
+                                                    float* __restrict__ t22) {
+    const int kind = (int)blockIdx.y;
+    float* out = kind == 0 ? u22 : kind == 1 ? u44 : t22;
+    if (!out) return;
+    const int t = (int)threadIdx.x, c = (int)blockIdx.x >> 1, wn = (int)blockIdx.x & 1;
+    const int s = t & 1, j = (t >> 1) & 1, i = (t >> 2) & 15, q = t >> 6;
+    const int cout = 32 * wn + 16 * j + i, cin = 8 * c + 2 * q + s;
+    double g[3][3];
+    const float* src = kind == 2 ? w + (cin * 64 + cout) * 9 : w + (cout * 64 + cin) * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) g[k / 3][k % 3] = (double)src[kind == 2 ? 8 - k : k];
+    if (kind == 1) {
+        double T[6][3];
+        transform<6>(G44, g, T);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+#pragma unroll
+            for (int b = 0; b < 6; ++b)       // [c][s = 6 (a % 3) + b][rg = a / 3][cgp = wn][q][i][j][ks]
+                out[(((c * 18 + (a % 3) * 6 + b) * 2 + a / 3) * 2 + wn) * PACK_LANES + t] = transformed<6>(G44, T, a, b);
+        }
+    } else {
+        double T[4][3];
+        transform<4>(G22, g, T);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b)       // [c][xi = 4 a + b][wn][q][i][j][s]
+                out[((c * 16 + a * 4 + b) * 2 + wn) * PACK_LANES + t] = transformed<4>(G22, T, a, b);
+        }
+    }
+}
+
+// An edge layer's 64 x 9 weight w[ch * 9 + k] (ch the layer's 64-channel side) -> the two stencil packs, pure permutations:
+//   wide[k * 64 + ch]                        = w[ch * 9 + k']     (_hip.pack_c1_to_64_weights: [tap][cout / 4][cout % 4])
+//   narrow[((ch / 32) * 9 + k) * 32 + ch % 32] = w[ch * 9 + k']   (_hip.pack_c64_to_1_weights: [half][tap][cin % 32])
+// k' = k for the layer's own pack, 8 - k for the pack of its transpose (vjp._transposed: the other layout).  C_in = 1: wide is the layer's
+// own, narrow the transposed; C_in = 64: the other way round.
+__global__ __launch_bounds__(TB) void pack_edge_kernel(const float* __restrict__ w, float* __restrict__ wide, float* __restrict__ narrow,
+                                                       int flip_wide) {
+    const int e = (int)(blockIdx.x * TB + threadIdx.x);
+    if (e >= (int)PACK_EDGE) return;
+    if (wide) {
+        const int k = e / 64, ch = e % 64;
+        wide[e] = w[ch * 9 + (flip_wide ? 8 - k : k)];
+    }
+    if (narrow) {
+        const int half = e / 288, k = (e / 32) % 9, ch = half * 32 + e % 32;
+        narrow[e] = w[ch * 9 + (flip_wide ? k : 8 - k)];
+    }
+}
+
 // the sizes of a layer and the layout of its workspace: float64 partials first, then t1, t2 and C (every piece 16-byte aligned)
 struct Plan {
     int CI, CO, h, w, tiles, cot_fwd, cot_adj;
@@ -361,6 +450,30 @@ int deqsci_realsn_grad_f32(const float* G, const float* W, const float* u, const
                        p.w, p.NWT, (int)p.n_gw);
     if (int e = launch_status()) return e;
     hipLaunchKernelGGL(realsn::grad_final_kernel, dim3((unsigned)ceil_div(p.NWT, TB * 4)), dim3(TB), 0, st, G, C, gw, (int)p.n_gw, record, sigma_t, dW, p.NWT);
+    return launch_status();
+}
+
+int deqsci_realsn_pack_f32(const float* weight, float* pack, float* pack44, float* pack_t, int64_t C_in, int64_t C_out, deqsci_stream_t stream) {
+    if (!weight || (!pack && !pack44 && !pack_t)) return DEQSCI_ERR_NULL;
+    const bool mid = C_in == realsn::CMAX && C_out == realsn::CMAX;
+    const bool edge = (C_in == 1 && C_out == realsn::CMAX) || (C_in == realsn::CMAX && C_out == 1);
+    if (!mid && !edge) return DEQSCI_ERR_UNSUPPORTED;
+    if (edge && pack44) return DEQSCI_ERR_UNSUPPORTED;      // an edge layer has no F(4x4,3x3) pack
+    if (!aligned16(weight) || !aligned16(pack) || !aligned16(pack44) || !aligned16(pack_t)) return DEQSCI_ERR_ALIGN;
+    const void* ptr[4] = {weight, pack, pack44, pack_t};
+    const int64_t len[4] = {C_in * C_out * 9 * 4, (mid ? realsn::PACK22 : realsn::PACK_EDGE) * 4, realsn::PACK44 * 4,
+                            (mid ? realsn::PACK22 : realsn::PACK_EDGE) * 4};
+    for (int a = 0; a < 4; ++a)
+        for (int b = a + 1; b < 4; ++b)
+            if (overlaps(ptr[a], len[a], ptr[b], len[b])) return DEQSCI_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (mid) {
+        hipLaunchKernelGGL(realsn::pack64_kernel, dim3(16, 3), dim3(TB), 0, st, weight, pack, pack44, pack_t);
+    } else {
+        const bool first = C_in == 1;                      // 1 -> 64: the layer's own pack is the wide one, its transpose's the narrow one
+        hipLaunchKernelGGL(realsn::pack_edge_kernel, dim3((unsigned)ceil_div(realsn::PACK_EDGE, TB)), dim3(TB), 0, st, weight,
+                           first ? pack : pack_t, first ? pack_t : pack, first ? 0 : 1);
+    }
     return launch_status();
 }
 

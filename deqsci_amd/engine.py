@@ -31,7 +31,9 @@ backward hook) is skipped unless `extra_call=True` - or the denoiser has a train
 whose every call advances module state (weight_u, weight): such a net gets all max_iter + 2 calls and
 runs eagerly, never as a captured graph.  The same holds for a net whose train-mode BatchNorms run on
 the device (train_bn="device": csrc/bn_train.hip moves running_mean / running_var /
-num_batches_tracked at every f-call, as the module's own forward does).
+num_batches_tracked at every f-call, as the module's own forward does).  train_realsn="device" puts the
+f-calls of a train-mode RealSN_SimpleCNN on the HIP kernels too: the power step in place in the module's
+buffers, csrc/realsn.hip's R3 from the new weight to the packs, the fp32 kernels (path "train realsn per layer").
 """
 import math
 import numpy as np
@@ -133,9 +135,17 @@ class _Denoiser:
     solvers/equilibrium_solvers_yaping.py:402-425."""
 
     def __init__(self, net, fold_bn=True, channels_last=None, fused_epilogue=True, fused_edges=True, winograd=True, conv64="fast",
-                 act_range="data", blk32=True, stack=True, stack_kernel="w16", train_bn="module"):
+                 act_range="data", blk32=True, stack=True, stack_kernel="w16", train_bn="module", train_realsn="module"):
         from .networks import FFDNet
         self.net = net
+        # train_realsn: what runs an f-call of a net with RealSNConv2d layers in TRAIN mode (one power step per layer and call) - "module"
+        # (default): the plugin's own forward (the power step on csrc/realsn.hip, the convolutions on MIOpen); "device": per layer R1 in place
+        # in the module's weight_u / weight buffers, R3 into pack buffers allocated once here, then the fp32 kernels on those packs, for a net
+        # vjp.param_eligibility(net, train_realsn=True) accepts.  A net it cannot serve keeps "module"; train_why says why.
+        if train_realsn not in ("module", "device"):
+            raise ValueError(f"train_realsn={train_realsn!r}: expected 'module' or 'device'")
+        self.train_realsn = train_realsn
+        self.rsn = None
         # train_bn: what runs an f-call of a net whose BatchNorm2d layers are in TRAIN mode (batch statistics; the reference trains FFDNet so) -
         # "module" (default): the plugin's own forward (MIOpen); "device": head kernel -> per layer [fp32 Winograd raw convolution -> T1
         # statistics + buffer update -> T2 normalise + ReLU] -> tail kernel (csrc/bn_train.hip), for a net vjp.param_eligibility(net,
@@ -213,9 +223,11 @@ class _Denoiser:
         self.fast = None
         self.wino = None
         self.edges = e = _Edges(2 if isinstance(net, FFDNet) else 1)
-        self.train, self.train_why = None, None
+        self.train, self.train_why, self.rsn = None, None, None
         if self.train_bn == "device" and isinstance(net, torch.nn.Module) and net.training:
             self._refresh_train_bn(e)
+        if self.train is None and self.train_realsn == "device" and isinstance(net, torch.nn.Module) and net.training:
+            self._refresh_train_realsn(e)
         seq = None
         if isinstance(net, FFDNet) and not net.training and net.num_input_channels == 1 and self.fold_bn:
             seq = net.intermediate_dncnn.itermediate_dncnn
@@ -287,6 +299,50 @@ class _Denoiser:
             h = _hip.bn_train_apply(c, rec, bn.weight.detach(), bn.bias.detach(), bn.eps, relu=True, out=c)
         return e.tail(h)
 
+    def _refresh_train_realsn(self, e):
+        """train_realsn="device": self.rsn = (per layer (conv, is RealSN, pack, pack44, v, record), R1's workspace, the 64->64 layers'
+        Conv64Weights over those packs) with every buffer allocated HERE, once - an f-call allocates none of them and their addresses do
+        not move - or train_why, the reason the net stays on its module.  A plain Conv2d's packs are made now (its weight does not move
+        between f-calls); a RealSNConv2d's at every call, behind its power step."""
+        from . import vjp
+        from .networks.simplecnn import RealSNConv2d
+        ok, why = vjp.param_eligibility(self.net, train_realsn=True)
+        if ok and not all(t.is_cuda and t.dtype == torch.float32 for t in list(self.net.parameters()) + list(self.net.buffers()) if t.is_floating_point()):
+            ok, why = False, "the net's parameters and buffers are not fp32 tensors on the GPU"
+        if not ok:
+            self.train_why = self.train_why or why
+            return
+        stack = vjp.realsn_stack(self.net)[0]
+        dev = stack[0][0].weight.device
+        layers = []
+        for conv, _, _ in stack:
+            cout, cin = conv.weight.shape[:2]
+            is_rsn = isinstance(conv, RealSNConv2d)
+            pack, pack44, _ = _hip.realsn_pack_buffers(cin, cout, dev, pack_t=False)
+            v = torch.empty((1, cin) + tuple(conv.weight_u.shape[2:]), device=dev, dtype=torch.float32) if is_rsn else None
+            record = torch.empty(3, device=dev, dtype=torch.float64) if is_rsn else None
+            if not is_rsn:
+                _hip.realsn_pack(_hip.f32c(conv.weight.detach()), pack, pack44, None)
+            layers.append((conv, is_rsn, pack, pack44, v, record))
+        mids = [_hip.Conv64Weights(conv.weight, s16=False, f22=pack, f44=pack44) for conv, _, pack, pack44, _, _ in layers[1:-1]]
+        e.head_w, e.tail_w, e.relu = layers[0][2], layers[-1][2], True
+        self.rsn = (layers, vjp._realsn_workspace(stack, dev), mids)
+
+    def _train_realsn_call(self, x):
+        """One f-call with every RealSNConv2d renormalised first: R1 moves the module's weight_u and weight in place (the module's own
+        kernels: its bits), R3 turns the weight into the packs, and the first-layer stencil, the fp32 64->64 kernels and the last-layer
+        kernel run on them.  No host synchronisation, no host -> device copy."""
+        from . import vjp
+        layers, ws, mids = self.rsn
+        for conv, is_rsn, pack, pack44, v, record in layers:
+            if is_rsn:
+                vjp.realsn_power_in_place(conv, ws, v, record)
+                _hip.realsn_pack(conv.weight, pack, pack44, None)
+        h = self.edges.head(x, None)
+        for weights in mids:
+            h = _hip.conv3x3_c64(h, weights, None, True, policy="fast32")
+        return self.edges.tail(h)
+
     def _run_stack(self, h, skip_last=False, skip_first=False, defer_last_epilogue=False, native_out=False):
         """defer_last_epilogue: leave the bias+ReLU of the last executed layer to the consumer (the fused
         FFDNet tail applies it while staging its input) and return (raw conv output, bias) - only when that
@@ -317,6 +373,7 @@ class _Denoiser:
     # train_bn="device": the unfolded layers of a net whose train-mode BatchNorms run on csrc/bn_train.hip (_refresh_train_bn), else None
     # and, where the option was asked for and the net is in train mode, the reason
     train, train_why = None, None
+    rsn = None                                                      # train_realsn="device": _refresh_train_realsn's layers, else None
 
     def _stack_for(self, idx, device, w16=False):
         """The Split16Stack (w16: Wino16Stack) of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a
@@ -344,6 +401,8 @@ class _Denoiser:
         they are NOW: tests and tools set them between calls, and the engine turns `stack` off and `per_layer_w16` on behind a time-out."""
         if self.train is not None and self.tag in ("ffdnet", "denoiser") and torch.device(device).type == "cuda":
             return "train bn per layer"
+        if self.rsn is not None and self.tag == "denoiser" and torch.device(device).type == "cuda":
+            return "train realsn per layer"
         if self.fast is None or self.tag not in ("ffdnet", "denoiser"):
             return "module"
         e, cuda = self.edges, torch.device(device).type == "cuda"
@@ -497,6 +556,9 @@ class _Denoiser:
             if path == "train bn per layer":
                 self.last_path = path
                 out = self._train_bn_call(x, sg)
+            elif path == "train realsn per layer":
+                self.last_path = path
+                out = self._train_realsn_call(x)
             elif path == "module":
                 out = self.net(x) if sg is None else self.net(x, sg.expand(bsz * B))
             elif path == "layers":
@@ -604,7 +666,7 @@ class DEQSCIEngine:
     def __init__(self, denoiser, iterator="anderson", m=5, beta=1.0, lam=1e-2, max_iter=180, tol=1e-5,
                  fold_bn=True, extra_call=False, poll_residual=True, channels_last=None, fused_epilogue=True,
                  fused_edges=True, winograd=True, use_graph="auto", conv64="auto", conv64_f22_calls=None, act_range="data", blk32=True, anderson_arith="reference",
-                 stack=True, stack_kernel="w16", groups=1, train_bn="module"):
+                 stack=True, stack_kernel="w16", groups=1, train_bn="module", train_realsn="module"):
         if iterator not in ("anderson", "picard"):
             raise ValueError(iterator)
         if not (groups == "auto" or (isinstance(groups, int) and 1 <= groups <= 2)):
@@ -622,7 +684,7 @@ class DEQSCIEngine:
         self._ctor = dict(iterator=iterator, m=m, beta=beta, lam=lam, max_iter=max_iter, tol=tol, fold_bn=fold_bn, extra_call=extra_call,
                           channels_last=channels_last, fused_epilogue=fused_epilogue, fused_edges=fused_edges, winograd=winograd, conv64=conv64,
                           conv64_f22_calls=conv64_f22_calls, act_range=act_range, blk32=blk32, anderson_arith=anderson_arith, stack=stack,
-                          stack_kernel=stack_kernel, train_bn=train_bn)
+                          stack_kernel=stack_kernel, train_bn=train_bn, train_realsn=train_realsn)
         self._net = denoiser
         self._kids, self._gate, self._grouped = None, None, False
         if anderson_arith not in ("float64", "reference"):
@@ -660,8 +722,9 @@ class DEQSCIEngine:
         # scale-free; fp16 pieces are not); "fixed" = 2^8 throughout, the round-3 behaviour (activations of a few units).
         self.den = _Denoiser(denoiser, fold_bn=fold_bn, channels_last=channels_last, fused_epilogue=fused_epilogue,
                              fused_edges=fused_edges, winograd=winograd, conv64=self.conv64_policy, act_range=act_range, blk32=blk32, stack=stack,
-                             stack_kernel=stack_kernel, train_bn=train_bn)
+                             stack_kernel=stack_kernel, train_bn=train_bn, train_realsn=train_realsn)
         self.train_bn = train_bn
+        self.train_realsn = train_realsn
         self._solve_only = False
         self.den.f22_calls = self.conv64_f22_calls
         self.iterator = iterator
@@ -816,6 +879,12 @@ class DEQSCIEngine:
                 self.last_info["train_bn"] = "device" if served else "module"
                 self.last_info["train_bn_reason"] = None if served else (
                     self.den.train_why or "the denoiser is not in train mode (net.eval(): its BatchNorm is folded into the convolutions)")
+            if self.train_realsn == "device":
+                # what the option did for this call: "device" where the f-calls ran R1 / R3 and the fp32 kernels, else "module" and why
+                served = self._train_realsn_device()
+                self.last_info["train_realsn"] = "device" if served else "module"
+                self.last_info["train_realsn_reason"] = None if served else (
+                    self.den.train_why or "the denoiser is not in train mode (net.eval(): a RealSNConv2d uses its stored weight)")
             fallback = None
             if self.conv64 == "auto" and not math.isfinite(self.last_info["res"]) and bool(torch.isfinite(y).all()):
                 # conv64="auto" promises the reference's fp32 range: a non-finite residual under the split-fp16 layers (already warned
@@ -888,7 +957,7 @@ class DEQSCIEngine:
             graph = False
         self._grouped = False
         extras = self._snaps is not None or self._trace
-        plan = None if (graph or extras or self._solve_only or self._train_bn_device()) else self._group_plan(bsz, H, W, B, y.device)
+        plan = None if (graph or extras or self._solve_only or self._train_bn_device() or self._train_realsn_device()) else self._group_plan(bsz, H, W, B, y.device)
         if plan is not None:
             rec = self._reconstruct_grouped(plan, y, Phi4, Phi_sum, initial_point)
             if rec is not None:
@@ -913,6 +982,10 @@ class DEQSCIEngine:
     def _train_bn_device(self):
         """True where the f-calls run train-mode BatchNorms on the device (train_bn="device" and a net it serves): each moves the running buffers."""
         return self.den.train is not None
+
+    def _train_realsn_device(self):
+        """True where the f-calls renormalise train-mode RealSNConv2d layers on the device path (train_realsn="device" and a net it serves)."""
+        return self.den.rsn is not None
 
     @torch.no_grad()
     def solve(self, y, Phi, Phi_sum=None, initial_point=None):

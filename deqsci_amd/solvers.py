@@ -91,14 +91,20 @@ class EquilibriumProxGradSCI(nn.Module):
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
-    def _param_mode(self, frozen_bn, train_bn):
-        """(mode, reason): which DenoiserParamGrads serves the denoiser - "plain", "frozen_bn", "train_bn" - or (None, why not)."""
+    def _param_mode(self, frozen_bn, train_bn, train_realsn=False):
+        """(mode, reason): which DenoiserParamGrads serves the denoiser - "plain", "frozen_bn", "train_bn", "train_realsn" - or (None, why not)."""
         op = self.nonlinear_op
         if not (self.A is A_torch_ and self.At is At_torch_):
             return None, "custom A / At: the device call uses the HIP GAP projection"
         ok, why = _vjp.param_eligibility(op)
         if ok:
             return "plain", why
+        if train_realsn:
+            # everything "device" serves, plus a train-mode net vjp.realsn_stack accepts; its verdict where the net has a train-mode RealSNConv2d
+            ok, why_rsn = _vjp.param_eligibility(op, train_realsn=True)
+            if ok:
+                return "train_realsn", why_rsn
+            return None, why_rsn if "RealSNConv2d" in why else why
         if not (frozen_bn or train_bn):
             return None, why
         ffdnet_tag = isinstance(op, _vjp._modules()[1]) and getattr(op, "tag", None) != "ffdnet"
@@ -113,20 +119,22 @@ class EquilibriumProxGradSCI(nn.Module):
             return (None, wrong_tag) if ffdnet_tag else ("train_bn", why_train)
         return None, why if "BatchNorm2d in eval mode" in why_train else why_train
 
-    def device_param_eligibility(self, frozen_bn=False, train_bn=False):
+    def device_param_eligibility(self, frozen_bn=False, train_bn=False, train_realsn=False):
         """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility;
         frozen_bn=True: also a frozen-BatchNorm stack and tag 'ffdnet', vjp.param_eligibility(net, frozen_bn=True); train_bn=True: all of
         that and the same nets with their BatchNorms in train mode, vjp.param_eligibility(net, train_bn=True))."""
-        mode, why = self._param_mode(frozen_bn, train_bn)
+        mode, why = self._param_mode(frozen_bn, train_bn, train_realsn)
         return mode is not None, why
 
-    def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False, train_bn=False):
+    def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False, train_bn=False, train_realsn=False):
         """The taped call f(z) = z1 - D(z1) whose backward forms the denoiser's weight gradients on the HIP kernels: gap_update ->
         autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called.  frozen_bn=True serves
         what device_param_eligibility(frozen_bn=True) accepts; FFDNet with _forward_taped's sigma bookkeeping.  train_bn=True serves what
         device_param_eligibility(train_bn=True) accepts: a train-mode BatchNorm normalises by the batch on csrc/bn_train.hip, and the call
-        moves its running buffers once, as the module's own forward would."""
-        mode, why = self._param_mode(frozen_bn, train_bn)
+        moves its running buffers once, as the module's own forward would.  train_realsn=True serves what
+        device_param_eligibility(train_realsn=True) accepts: every RealSNConv2d takes its power step in the module's buffers, once
+        (csrc/realsn.hip), and the gradients go to weight_orig."""
+        mode, why = self._param_mode(frozen_bn, train_bn, train_realsn)
         if mode is None:
             raise ValueError(f"forward_param_device: {why}")
         bsz, w, h, c = z.shape
@@ -138,25 +146,26 @@ class EquilibriumProxGradSCI(nn.Module):
         if mode != "plain" and isinstance(op, _vjp._modules()[1]):
             sigma = self._sigma(y, bsz * c)
             self._taped = (self._taped[0], sigma)
-        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, mode == "frozen_bn", mode == "train_bn")
+        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, mode == "frozen_bn", mode == "train_bn", mode == "train_realsn")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
-    def device_vjp_eligibility(self):
-        """(ok, reason): whether device_vjp can serve this map (HIP GAP operators and a denoiser deqsci_amd.vjp.eligibility accepts)."""
+    def device_vjp_eligibility(self, train_realsn=False):
+        """(ok, reason): whether device_vjp can serve this map (HIP GAP operators and a denoiser deqsci_amd.vjp.eligibility accepts;
+        train_realsn=True: also a train-mode RealSN net, vjp.eligibility(net, train_realsn=True))."""
         if not (self.A is A_torch_ and self.At is At_torch_):
             return False, "custom A / At: the device map uses the HIP GAP projection"
-        return _vjp.eligibility(self.nonlinear_op)
+        return _vjp.eligibility(self.nonlinear_op, train_realsn)
 
-    def device_vjp(self, Phi, Phi_sum):
+    def device_vjp(self, Phi, Phi_sum, train_realsn=False):
         """The map v -> J_f(z0)^T v = P (v - J_D(z1)^T v) of the LAST taped call f(z0) (its z1 and sigma: no further call of f, the
         sigma state stays where that call left it), on the HIP kernels: v and the result (bsz,H,W,B) fp32 on the GPU, no host sync."""
         if self._taped is None:
             raise RuntimeError("device_vjp: no taped call of this map to linearise at")
-        ok, why = self.device_vjp_eligibility()
+        ok, why = self.device_vjp_eligibility(train_realsn)
         if not ok:
             raise ValueError(f"device_vjp: {why}")
         z1p, sigma = self._taped
-        jd = _vjp.DenoiserVJP(self.nonlinear_op, z1p, sigma)
+        jd = _vjp.DenoiserVJP(self.nonlinear_op, z1p, sigma, train_realsn)
         Phi, Phi_sum = _hip.f32c(Phi), _hip.f32c(Phi_sum)
         zero_y = None
 
@@ -365,20 +374,23 @@ class DEQFixedPoint(nn.Module):
         return self._engine[1]
 
     def _train_bn_engine(self):
-        """The engine that runs a training step's no-tape solve: engine_options["train_bn"] == "device", f on the engine's path (not a
+        """The engine that runs a training step's no-tape solve: engine_options["train_bn"] or ["train_realsn"] == "device", f on the engine's path (not a
         DataParallel) and a denoiser in train mode that the option serves - else None, and the solve takes the solver as it always did."""
-        if self.engine_options.get("train_bn") != "device" or isinstance(self.f, nn.DataParallel):
+        if ((self.engine_options.get("train_bn") != "device" and self.engine_options.get("train_realsn") != "device")
+                or isinstance(self.f, nn.DataParallel)):
             return None
         eng = self._engine_for()
         if eng is None:
             return None
         eng.den._refresh()
-        return eng if eng.den.train is not None else None
+        return eng if (eng.den.train is not None or eng.den.rsn is not None) else None
 
     def _device_map(self, Phi, Phi_sum):
         """implicit_backward = "device": the device map of the taped call just made, or None (autograd) with the reason recorded."""
-        if self.implicit_backward not in ("autograd", "device"):
-            raise ValueError(f"implicit_backward={self.implicit_backward!r}: expected 'autograd' or 'device'")
+        if self.implicit_backward not in ("autograd", "device", "device+realsn"):
+            raise ValueError(f"implicit_backward={self.implicit_backward!r}: expected 'autograd' or 'device' - or 'device+realsn', which adds "
+                             "RealSNConv2d in train mode")
+        realsn = self.implicit_backward == "device+realsn"
         self.backward_fallback_reason = None
         if self.implicit_backward == "autograd":
             return None
@@ -389,32 +401,33 @@ class DEQFixedPoint(nn.Module):
         if not isinstance(f, EquilibriumProxGradSCI):
             self.backward_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
             return None
-        ok, why = f.device_vjp_eligibility()
+        ok, why = f.device_vjp_eligibility(realsn)
         if not ok:
             self.backward_fallback_reason = why
             return None
-        return f.device_vjp(Phi, Phi_sum)
+        return f.device_vjp(Phi, Phi_sum, realsn)
 
     def _taped_call(self, z, x, Phi, Phi_sum):
         """The taped call z = f(z*) (:268): on the device's weight-gradient path where parameter_backward asks for it and it is served."""
-        if self.parameter_backward not in ("autograd", "device", "device+bn", "device+bn-train"):
+        if self.parameter_backward not in ("autograd", "device", "device+bn", "device+bn-train", "device+realsn"):
             raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd', 'device' or 'device+bn' - or 'device+bn-train', "
-                             "which adds BatchNorm2d in train mode")
+                             "which adds BatchNorm2d in train mode, or 'device+realsn', which adds RealSNConv2d in train mode")
         self.parameter_fallback_reason = None
         self.last_parameter_path = "autograd"
         if self.parameter_backward != "autograd":
             train_bn = self.parameter_backward == "device+bn-train"
             frozen_bn = train_bn or self.parameter_backward == "device+bn"
+            realsn = self.parameter_backward == "device+realsn"
             f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
             if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
                 self.parameter_fallback_reason = "DataParallel over several devices (the taped call runs on replicas)"
             elif not isinstance(f, EquilibriumProxGradSCI):
                 self.parameter_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
             else:
-                ok, why = f.device_param_eligibility(frozen_bn, train_bn)
+                ok, why = f.device_param_eligibility(frozen_bn, train_bn, realsn)
                 if ok:
                     self.last_parameter_path = "device"
-                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn, train_bn)
+                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn, train_bn, realsn)
                 self.parameter_fallback_reason = why
         return self.f(z, x, Phi, Phi_sum)
 

@@ -53,6 +53,13 @@ the mean and the biased variance of c = conv(x, W) over the batch's P = n H W pi
 
 (csrc/bn_train.hip: T1 statistics and the running buffers' update, T2 apply + mask, T3 the two sums, T4 dc; dc goes down through the UNFOLDED
 transposed weight).  The statistic terms reach the pixels the ReLU masked too.
+
+Spectral normalisation in TRAIN mode - RealSN_SimpleCNN as the reference trains it; parameter_backward / implicit_backward =
+"device+realsn", the engine's train_realsn="device", param_eligibility(net, train_realsn=True); realsn_stack says which nets qualify - the
+layer's parameter is weight_orig and its weight = weight_orig / cur_sigma * sigma changes at every call (csrc/realsn.hip R1).  The packs the
+kernels read are therefore made on the device, by R3 of the same file, from the weight R1 just wrote; the walk above then runs on the
+normalised weights, and R2 turns each layer's gradient G into weight_orig's, (sigma / cur_sigma) (G - (sum(G W) / cur_sigma) C).  The
+implicit backward reads J_D at the weights the last call f0 = f(z0) left in the modules, as the reference's hook does.
 """
 import torch
 import torch.nn.functional as F
@@ -107,9 +114,17 @@ def _plugin_refusal(net, what):
     return None
 
 
-def eligibility(net):
-    """(ok, reason): whether DenoiserVJP (and DEQFixedPoint.implicit_backward = "device") can differentiate through `net`.  CPU-safe."""
+def eligibility(net, train_realsn=False):
+    """(ok, reason): whether DenoiserVJP (and DEQFixedPoint.implicit_backward = "device") can differentiate through `net`.  train_realsn=True
+    (implicit_backward = "device+realsn"): all of that, and a net with a train-mode RealSNConv2d that realsn_stack accepts - such a net is
+    answered by realsn_stack's verdict.  CPU-safe."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
+    if train_realsn:
+        ok, why = eligibility(net)
+        if ok or not (isinstance(net, torch.nn.Module) and any(isinstance(m, RealSNConv2d) and m.training for m in net.modules())):
+            return ok, why
+        stack, why = realsn_stack(net)
+        return (True, _REALSN_OK) if stack is not None else (False, why)
     if isinstance(net, FFDNet):
         if net.num_input_channels != 1:
             return False, _FFDNET_COLOUR
@@ -369,6 +384,64 @@ def bn_stack(net, train):
     return (stack, ffdnet, None) if why is None else (None, None, why)
 
 
+_REALSN_OK = "train-mode RealSN conv + ReLU stack"
+
+
+def realsn_stack(net):
+    """(stack, reason): the layers [(conv, None, relu)] of a net whose TRAIN-mode f-call, implicit backward and weight gradients run on the
+    device with the spectral normalisation in it (engine train_realsn="device", implicit_backward / parameter_backward = "device+realsn") -
+    or (None, why not).  A DnCNN plugin in train mode; every convolution a RealSNConv2d (its parameter is weight_orig, renormalised by one
+    power step per call: csrc/realsn.hip) or a plain bias-free Conv2d; no BatchNorm; 1 -> 64 -> ... -> 64 -> 1 with a ReLU behind every
+    layer but the last; fp32.  Decided here and nowhere else.  CPU-safe."""
+    from .layers import _conv_ok
+    DnCNN, FFDNet, RealSNConv2d = _modules()
+    if isinstance(net, FFDNet):
+        return None, "FFDNet: it has no spectrally normalised convolution, and its BatchNorm2d layers belong to train_bn"
+    why = _plugin_refusal(net, "a train-mode RealSN device path")
+    if why is not None:
+        return None, why
+    if not net.training:
+        return None, "the net is in eval mode (a RealSNConv2d uses its stored weight there: the plain device paths serve it)"
+    mods, stack, i = list(net.dncnn), [], 0
+    if any(isinstance(m, torch.nn.BatchNorm2d) for m in mods):
+        return None, "BatchNorm2d next to RealSNConv2d (RealSN_DnCNN: the spectral normalisation of a BatchNorm has no device kernel)"
+    while i < len(mods):
+        conv = mods[i]
+        if isinstance(conv, RealSNConv2d):
+            u = conv.weight_u
+            if int(conv.n_power_iterations) < 1:
+                return None, f"RealSNConv2d with n_power_iterations = {conv.n_power_iterations}"
+            if u.dim() != 4 or u.shape[0] != 1 or u.shape[1] != conv.weight_orig.shape[0] or u.shape[2] * u.shape[3] > (1 << 20):
+                return None, f"RealSNConv2d whose weight_u {tuple(u.shape)} is not a (1, C_out, h, w) map of at most 2^20 pixels"
+            if not isinstance(conv.weight_orig, torch.nn.Parameter):
+                return None, "a weight_orig that is not an nn.Parameter"
+        elif isinstance(conv, torch.nn.Conv2d):
+            if not _conv_ok(conv):
+                return None, "Conv2d other than 3x3, stride 1, padding 1"
+            if conv.bias is not None:
+                return None, "Conv2d with a bias"
+            if not isinstance(conv.weight, torch.nn.Parameter):
+                return None, "a conv weight that is not an nn.Parameter"
+        else:
+            return None, f"unknown module {type(conv).__name__} where a convolution was expected"
+        i += 1
+        relu = i < len(mods) and isinstance(mods[i], torch.nn.ReLU)
+        if relu:
+            i += 1
+        elif i < len(mods) and not isinstance(mods[i], (torch.nn.Conv2d, RealSNConv2d)):
+            return None, f"unknown module {type(mods[i]).__name__}"
+        stack.append((conv, None, relu))
+    why = _structure_refusal(stack, False)
+    if why is None and not all(t.dtype == torch.float32 for t in list(net.parameters()) + list(net.buffers()) if t.is_floating_point()):
+        why = "parameters or buffers that are not fp32"
+    return (stack, None) if why is None else (None, why)
+
+
+def _realsn_weight_of(conv):
+    """The parameter of a layer of realsn_stack: a RealSNConv2d's weight_orig, a Conv2d's weight."""
+    return conv.weight_orig if isinstance(conv, _modules()[2]) else conv.weight
+
+
 _TRAIN_BN_OK, _TRAIN_FFDNET_OK = "bias-free conv [+ train-mode BN] + ReLU stack", "FFDNet with its BatchNorm in train mode"
 
 
@@ -382,14 +455,21 @@ def _bn_mode(who, frozen_bn, train_bn):
     return True if train_bn else (False if frozen_bn else None)
 
 
-def param_eligibility(net, frozen_bn=False, train_bn=False):
+def param_eligibility(net, frozen_bn=False, train_bn=False, train_realsn=False):
     """(ok, reason): whether DenoiserParamGrads (and DEQFixedPoint.parameter_backward = "device") can form the weight gradients of `net`:
     a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0,
     no_bn=True) of any depth >= 2.  frozen_bn=True (parameter_backward = "device+bn") accepts in addition an eval-mode affine BatchNorm2d
     with running statistics behind every 64 -> 64 conv - DnCNN(..., no_bn=False).eval() - and the grayscale FFDNet with its BatchNorms in
     eval mode.  train_bn=True (parameter_backward = "device+bn-train") accepts those two families with their BatchNorms in TRAIN mode -
     affine, with running statistics and a float momentum (csrc/bn_train.hip) - and refuses an eval-mode BatchNorm.  bn_stack decides.
-    CPU-safe."""
+    train_realsn=True (parameter_backward = "device+realsn", the engine's train_realsn="device") is a family of its own: a DnCNN in TRAIN
+    mode whose convolutions are RealSNConv2d or plain bias-free Conv2d, without BatchNorm - RealSN_SimpleCNN as the reference trains it;
+    realsn_stack decides.  CPU-safe."""
+    if train_realsn:
+        if frozen_bn or train_bn:
+            raise ValueError("param_eligibility: train_realsn excludes frozen_bn and train_bn")
+        stack, why = realsn_stack(net)
+        return (False, why) if stack is None else (True, _REALSN_OK)
     mode = _bn_mode("param_eligibility", frozen_bn, train_bn)
     stack, ffdnet, why = bn_stack(net, mode)
     return (False, why) if stack is None else (True, _PARAM_OK[mode][ffdnet])
@@ -400,10 +480,16 @@ def conv_weights(net):
     return [m.weight for m in net.dncnn if isinstance(m, torch.nn.Conv2d)]
 
 
-def grad_parameters(net, train_bn=False):
+def grad_parameters(net, train_bn=False, train_realsn=False):
     """The nn.Parameters of a net param_eligibility(net, frozen_bn=True) accepts, in module order - per layer the conv weight, then its
     BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for.  train_bn=True:
-    the same for a net param_eligibility(net, train_bn=True) accepts."""
+    the same for a net param_eligibility(net, train_bn=True) accepts.  train_realsn=True: one per layer of a net param_eligibility(net,
+    train_realsn=True) accepts - the weight_orig of a RealSNConv2d, the weight of a plain Conv2d."""
+    if train_realsn:
+        stack, why = realsn_stack(net)
+        if stack is None:
+            raise ValueError(f"grad_parameters: {why}")
+        return [_realsn_weight_of(conv) for conv, _, _ in stack]
     stack, _, why = bn_stack(net, bool(train_bn))
     if stack is None:
         raise ValueError(f"grad_parameters: {why}")
@@ -469,6 +555,38 @@ def plan_param_grads_train_bn(net, x, v, sigma=None, masks=None, input_grad=Fals
     input)."""
     out = _net_param_grads("plan_param_grads_train_bn", net, True, x, v, sigma, masks, input_grad)
     return out if input_grad else out[:2]
+
+
+def plan_param_grads_realsn(net, x, v, masks=None, input_grad=False, update=False):
+    """(dD/dtheta)^T v of a net param_eligibility(net, train_realsn=True) accepts, at x, in x's dtype - the host statement of what
+    DenoiserParamGrads(..., train_realsn=True).grads runs: per RealSNConv2d one call of realsn.power_iteration from the module's weight_u
+    (weight = weight_orig / cur_sigma * sigma; u, v constants), plan_param_grads' walk on the normalised weights, and realsn.weight_grad
+    turning each layer's gradient G_i into that of weight_orig; a plain Conv2d's G_i is its gradient.  update=True writes the new weight_u and
+    weight into the module as its own forward would; otherwise the module is left alone.  masks: those of another forward pass.  Returns
+    (gradients in grad_parameters(net, train_realsn=True) order, masks) - with input_grad=True (gradients, masks, J_D(x)^T v)."""
+    from . import realsn
+    RealSNConv2d = _modules()[2]
+    stack, why = realsn_stack(net)
+    if stack is None:
+        raise ValueError(f"plan_param_grads_realsn: {why}")
+    steps, rules = [], []
+    with torch.no_grad():
+        for conv, _, _ in stack:
+            if isinstance(conv, RealSNConv2d):
+                W = conv.weight_orig.detach()
+                weight, u, vr, cs = realsn.power_iteration(W, conv.weight_u, conv.sigma, conv.n_power_iterations, conv.eps)
+                if update:
+                    conv.weight_u.copy_(u)
+                    conv.weight.copy_(weight)
+                steps.append((W, u, vr, cs, conv.sigma))
+            else:
+                weight = conv.weight.detach()
+                steps.append(None)
+            rules.append(_PlainRule(weight.to(x)))
+        tape, used = _taped_forward(rules, [relu for _, _, relu in stack], x, masks)
+        Gs, gx = _walk_back(rules, tape, used, v, PLAIN_EDGES, input_grad)
+        grads = [G if st is None else realsn.weight_grad(G.to(st[0]), *st).to(x) for G, st in zip(Gs, steps)]
+    return (grads, used, gx) if input_grad else (grads, used)
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
@@ -550,16 +668,20 @@ class _MaskedStack:
     place of _Conv64 of `layers`' own.  through_input=False (FFDNet under DenoiserParamGrads: its input is detached, nothing is carried
     through the first layer) builds no head_f / head_t."""
 
-    def __init__(self, layers, x, sigma=None, keep=False, rules=None, through_input=True):
+    def __init__(self, layers, x, sigma=None, keep=False, rules=None, through_input=True, edges=None):
         x = _hip.f32c(x.detach())
         f32 = lambda t: t.to(x.device, torch.float32)
         self.ffdnet = sigma is not None
         pack_in, pack_out, self._first, self._last = _FFDNET_KERNELS if self.ffdnet else _PLAIN_KERNELS
         with torch.no_grad():
-            w0, wt = f32(layers[0][0]), f32(layers[-1][0])
-            win = w0[:, 1:5] if self.ffdnet else w0                 # (FFDNet's channel 0 is sigma's: it carries no tangent)
-            self.head_f, self.head_t = (pack_in(win.contiguous()), pack_out(_transposed(win))) if through_input else (None, None)
-            self.tail_f, self.tail_t = pack_out(wt), pack_in(_transposed(wt))
+            if edges is not None:           # (a plain stack whose packs csrc/realsn.hip's R3 made on the device: layers is not read)
+                self.head_f, self.head_t, self.tail_f, self.tail_t = edges
+                w0 = None
+            else:
+                w0, wt = f32(layers[0][0]), f32(layers[-1][0])
+                win = w0[:, 1:5] if self.ffdnet else w0                 # (FFDNet's channel 0 is sigma's: it carries no tangent)
+                self.head_f, self.head_t = (pack_in(win.contiguous()), pack_out(_transposed(win))) if through_input else (None, None)
+                self.tail_f, self.tail_t = pack_out(wt), pack_in(_transposed(wt))
             self.rules = [_Conv64(f32(w), b) for w, b, _ in layers[1:-1]] if rules is None else rules
             h = _hip.ffdnet_head(x, _hip.pack_head_weights(w0), sigma) if self.ffdnet else _hip.conv3x3_c1_to_64(x, self.head_f, relu=True)
             self.masks = [_hip.relu_mask_pack(h)]
@@ -670,6 +792,79 @@ class _Train64(_Conv64):
         self.c = None
 
 
+class _RealSN64(_Conv64):
+    """A 64 -> 64 layer of a realsn_stack: its two F(2x2,3x3) packs come from csrc/realsn.hip's R3 on the device (no host packer: the weight
+    changes at every call); step = (W, u, v, record, sigma) of the power step that made the weight - W0's G is then the gradient of the
+    NORMALISED weight and R2 turns it into weight_orig's - or None for a plain Conv2d, whose G is its gradient.  rws: R1 / R2's workspace."""
+
+    def __init__(self, u, ut, step, rws):
+        self.u, self.ut, self.ws, self.bias, self.step, self.rws = u, ut, None, None, step, rws
+
+    def backward(self, inp, g, need):
+        if not need[0]:
+            return [None], g
+        G = _hip.wgrad_c64_c64(inp, g, self.ws)
+        return [G if self.step is None else _realsn_grad(G, self.step, self.rws)], g
+
+
+def _realsn_grad(G, step, rws):
+    W, u, v, record, sigma = step
+    return _hip.realsn_grad(G, W, u, v, record, sigma, workspace=rws)
+
+
+def realsn_power_in_place(conv, workspace=None, v=None, record=None):
+    """One train-mode call's power step of a RealSNConv2d on the device, R1 writing weight_u and weight IN PLACE into the module's own
+    buffers (the kernels of the module's own forward: the same bits).  -> (W = weight_orig as R1 read it, weight, u, v, record)."""
+    W, u, weight = _hip.f32c(conv.weight_orig.detach()), conv.weight_u, conv.weight
+    if not (u.is_contiguous() and weight.is_contiguous() and u.dtype == weight.dtype == torch.float32):
+        raise _hip.DeqsciHipError("RealSNConv2d: weight_u and weight must be contiguous fp32 buffers to be updated in place")
+    weight, u, v, record = _hip.realsn_power(W, u, conv.n_power_iterations, conv.sigma, conv.eps, workspace=workspace, weight=weight, v=v, record=record)
+    return W, weight, u, v, record
+
+
+def _realsn_workspace(stack, device):
+    """One workspace for R1 / R2 of every RealSNConv2d of the stack (the largest asked for), or None without one."""
+    RealSNConv2d = _modules()[2]
+    sizes = [_hip.load().deqsci_realsn_workspace_bytes(c.weight_orig.shape[1], c.weight_orig.shape[0], c.weight_u.shape[2], c.weight_u.shape[3])
+             for c, _, _ in stack if isinstance(c, RealSNConv2d)]
+    if not sizes:
+        return None
+    if min(sizes) == 0:
+        raise _hip.DeqsciHipError("realsn: a RealSNConv2d whose sizes the kernels refuse")
+    return _hip._partials(max(sizes), device)
+
+
+def _realsn_device_stack(stack, x, keep, step):
+    """_MaskedStack of a realsn_stack at x with every pack made by R3.  step=True: each RealSNConv2d first takes its power step (R1, in
+    place in the module) and the steps are kept for the way back; False: the `weight` buffers are packed as they stand (what the last
+    call left behind).  -> (the _MaskedStack, [per layer (W, u, v, record, sigma) or None], R1 / R2's workspace or None)."""
+    RealSNConv2d = _modules()[2]
+    dev = x.device
+    rws = _realsn_workspace(stack, dev) if step else None
+    steps, packs = [], []
+    with torch.no_grad():
+        for conv, _, _ in stack:
+            if isinstance(conv, RealSNConv2d):
+                if step:
+                    W, weight, u, v, record = realsn_power_in_place(conv, rws)
+                    steps.append((W, u.clone(), v, record, float(conv.sigma)))      # (weight_u moves again with the next call)
+                else:
+                    weight = conv.weight
+                    steps.append(None)
+            else:
+                weight = conv.weight.detach()
+                steps.append(None)
+            weight = _hip.f32c(weight)
+            if weight.device != dev:
+                raise _hip.DeqsciHipError(f"realsn: the net's weights are on {weight.device}, the image on {dev}")
+            cout, cin = weight.shape[:2]
+            pack, _, pack_t = _hip.realsn_pack(weight, *_hip.realsn_pack_buffers(cin, cout, dev, pack44=False))
+            packs.append((pack, pack_t))
+    rules = [_RealSN64(p, pt, st, rws) for (p, pt), st in zip(packs[1:-1], steps[1:-1])]
+    edges = (packs[0][0], packs[0][1], packs[-1][0], packs[-1][1])
+    return _MaskedStack(None, x, keep=keep, rules=rules, edges=edges), steps, rws
+
+
 _RELEASED = "DenoiserParamGrads.grads: the activations were released"
 
 
@@ -722,15 +917,20 @@ class DenoiserVJP:
     """v -> J_D(x)^T v for a (n,1,H,W) fp32 GPU image x and v of its shape: _MaskedStack.vjp, k-1 masked transposed layers and the 64 -> 1
     stencil per call, enqueued on the current stream with no host synchronisation (safe to capture).  sigma: FFDNet's noise level (unused:
     its input is detached, the product is zero - no launches, no masks).  Raises ValueError with eligibility()'s reason for a net it
-    cannot differentiate."""
+    cannot differentiate.  train_realsn=True (implicit_backward = "device+realsn") serves in addition a net in train mode that
+    param_eligibility(net, train_realsn=True) accepts: J_D is read at the `weight` buffers as the LAST call left them (the reference's hook
+    differentiates that call's graph), packed here by csrc/realsn.hip's R3 into buffers of this object's own, which no later call changes."""
 
-    def __init__(self, net, x, sigma=None):
-        ok, why = eligibility(net)
+    def __init__(self, net, x, sigma=None, train_realsn=False):
+        ok, why = eligibility(net, train_realsn)
         if not ok:
             raise ValueError(f"DenoiserVJP: {why}")
         self.shape = _image("DenoiserVJP", x)[0]
         self.zero = why == _FFDNET_OK
-        self._stack = None if self.zero else _MaskedStack(host_plan(net)[0], x)
+        if why == _REALSN_OK:
+            self._stack = _realsn_device_stack(realsn_stack(net)[0], _hip.f32c(x.detach()), False, False)[0]
+        else:
+            self._stack = None if self.zero else _MaskedStack(host_plan(net)[0], x)
         self.masks = [] if self.zero else self._stack.masks
 
     def __call__(self, v):
@@ -760,9 +960,16 @@ class DenoiserParamGrads:
     running_mean / running_var / num_batches_tracked IN PLACE on the device, exactly once per construction, and the layer keeps its
     convolution output c beside the post-ReLU activation: (2 (k-2) + 1) n 64 H W 4 bytes for k layers (FFDNet: 27 activations at half
     resolution), twice the frozen mode's.  T3 and T4 run wherever the walk passes, asked for or not: dc is what goes down, through the
-    plain (unfolded) transposed weight, so .vjp(v) is the true input product, the statistic terms included (FFDNet: zero)."""
+    plain (unfolded) transposed weight, so .vjp(v) is the true input product, the statistic terms included (FFDNet: zero).
 
-    def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False):
+    train_realsn=True: the nets param_eligibility(net, train_realsn=True) accepts and grad_parameters(net, train_realsn=True) - see
+    _init_realsn.  The construction takes every RealSNConv2d's power step IN PLACE in the module, exactly once."""
+
+    def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False, train_realsn=False):
+        self._steps = None
+        if train_realsn:
+            self._init_realsn(net, x, frozen_bn or train_bn)
+            return
         train = _bn_mode("DenoiserParamGrads", frozen_bn, train_bn)
         stack, self.ffdnet, why = bn_stack(net, train)
         if stack is None:
@@ -788,6 +995,27 @@ class DenoiserParamGrads:
         for rule in rules:
             rule.ws = self._ws_bn if rule.bn_workspace else self._ws
 
+    def _init_realsn(self, net, x, other_mode):
+        """train_realsn=True: the nets param_eligibility(net, train_realsn=True) accepts, answering for grad_parameters(net,
+        train_realsn=True).  Forward: per RealSNConv2d R1 (the module's weight_u and weight move IN PLACE, once, as its own forward moves
+        them; W, the new u, v and the record are kept as autograd._RealSNWeight keeps them), R3 (the forward and transposed packs, on the
+        device), then the masked stack with every activation kept.  Back: W0 / W1 give G_i, the gradient of the NORMALISED weight, and R2
+        (_hip.realsn_grad) turns it into weight_orig's; a plain Conv2d's G_i is its gradient.  No atomics, no host synchronisation."""
+        if other_mode:
+            raise ValueError("DenoiserParamGrads: train_realsn excludes frozen_bn and train_bn")
+        stack, why = realsn_stack(net)
+        if stack is None:
+            raise ValueError(f"DenoiserParamGrads: {why}")
+        self.ffdnet, self._sigma, self._ws_bn = False, None, None
+        self.shape = _image("DenoiserParamGrads", x)[0]
+        self._x = _hip.f32c(x.detach())
+        self._stack, self._steps, self._rws = _realsn_device_stack(stack, self._x, True, True)
+        self._counts = [1] * len(stack)
+        self.masks, self.noise = self._stack.masks, self._stack.noise
+        self._ws = _hip.wgrad_workspace(self.shape[0], self.shape[2], self.shape[3], x.device)
+        for rule in self._stack.rules:
+            rule.ws = self._ws
+
     def _v(self, v, what):
         if tuple(v.shape) != self.shape:
             raise _hip.DeqsciHipError(f"DenoiserParamGrads.{what}: v must have the shape {self.shape} of x, got {tuple(v.shape)}")
@@ -797,7 +1025,9 @@ class DenoiserParamGrads:
         """The weight gradient of the first (which = 0) or the last (1) layer from the image side img and the 64-channel side t."""
         if self.ffdnet:
             return _hip.wgrad_shuffle(img, t, which, None if which else self._sigma, self._ws_bn)
-        return _hip.wgrad_c1_c64(img, t, which, self._ws)
+        G = _hip.wgrad_c1_c64(img, t, which, self._ws)
+        step = None if self._steps is None else self._steps[-1 if which else 0]
+        return G if step is None else _realsn_grad(G, step, self._rws)
 
     def _walk(self, v, need, want_input):
         """The walk back from the gradient v of the noise.  -> (one gradient per parameter - None where `need` is false -, J_D(x)^T v if

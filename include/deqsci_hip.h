@@ -579,6 +579,21 @@ int deqsci_realsn_power_f32(const float* W, float* u, float* v, float* weight, d
                             int64_t C_in, int64_t C_out, int64_t h, int64_t w, void* workspace, deqsci_stream_t stream);
 int deqsci_realsn_grad_f32(const float* G, const float* W, const float* u, const float* v, const double* record, float* dW, float sigma_t,
                            int64_t C_in, int64_t C_out, int64_t h, int64_t w, void* workspace, deqsci_stream_t stream);
+/* R3 pack    the normalised weight (C_out, C_in, 3, 3) R1 wrote -> the packs the convolution kernels read, in ONE launch: no host
+ *            synchronisation, no host -> device copy, no allocation.  Every output may be NULL (not wanted); the caller owns the buffers.
+ *            (64,64): pack = the F(2x2,3x3) pack (64*64*16 floats, the layout of csrc/winograd.hip), pack44 = the F(4x4,3x3) pack
+ *                     (64*64*36 floats, csrc/winograd44.hip), pack_t = the F(2x2,3x3) pack of the transposed weight
+ *                     wt[co, ci, ky, kx] = weight[ci, co, 2 - ky, 2 - kx], through which a gradient goes down.
+ *            (1,64):  pack = the 1 -> 64 stencil's [tap][cout] (576 floats), pack_t = the 64 -> 1 stencil's [half][tap][cin % 32] of wt.
+ *            (64,1):  pack = the 64 -> 1 stencil's pack, pack_t = the 1 -> 64 stencil's pack of wt.  pack44 must be NULL for both.
+ *            Arithmetic of the Winograd packs: U = G g G^T in float64 from the fp32 weight, G the transform's constants as doubles
+ *            (F(2x2,3x3): 1, 1/2; F(4x4,3x3): 1/4, 1/6, 1/12, 1/24, each the double nearest the quotient).  ONE order: first
+ *            T[a][k] = (G[a][0] g[0][k] + G[a][1] g[1][k]) + G[a][2] g[2][k], then U[a][b] = (T[a][0] G[b][0] + T[a][1] G[b][1]) + T[a][2] G[b][2];
+ *            every product and every sum is rounded by itself (no fused multiply-add), the zero entries of G take part like the others,
+ *            and U is rounded to fp32 once.  The edge packs are permutations.  Bit-equal run to run.
+ *            NULL weight or all three outputs NULL -> -1; another (C_in, C_out), pack44 for an edge layer -> -4; a pointer not 16-byte
+ *            aligned -> -3; an output overlapping the weight or another output -> -4.  All checked before the launch. */
+int deqsci_realsn_pack_f32(const float* weight, float* pack, float* pack44, float* pack_t, int64_t C_in, int64_t C_out, deqsci_stream_t stream);
 
 /* ---- BatchNorm2d in TRAIN mode behind a 64 -> 64 convolution (csrc/bn_train.hip): batch statistics, normalisation and their backward on the
  * fp32 channels_last activation (P, 64), P = n H W pixels.  A workgroup owns a fixed run of pixels (DEQSCI_BN_TRAIN_CHUNK, or

@@ -6,7 +6,17 @@ none).  And the gradient of the four normalised weights for a given upstream gra
 last two lines of the step against R2 (2 launches per layer).  HIP events after warm-up, the median of the repeats; every repeat starts
 from the same weight_u.  Prints one line per measurement and a JSON line.
 
-    python tools/realsn_bench.py [--reps 50] [--warmup 5]
+Then the train-mode device paths at 256 x 256 x 8 with 1 and 8 measurements per call (a second JSON line):
+
+  packs       R3 alone per layer shape (every pack of the layer, one launch) against the host packers making the same packs
+  f-call      one train-mode f-call of the engine's denoiser: the module (power step on csrc/realsn.hip, convolutions on MIOpen) against
+              train_realsn="device" (R1 in place, R3, first-layer stencil, fp32 64->64 kernels, last-layer kernel)
+  taped call  the taped call and its backward for a seeded upstream gradient: the module on autograd's tape against
+              autograd.denoiser_noise(train_realsn=True) (parameter_backward = "device+realsn")
+
+No threshold: the defaults stay "module" / "autograd"; the numbers go to profiles/realsn.md with the board they were measured on.
+
+    python tools/realsn_bench.py [--reps 50] [--warmup 5] [--train-reps 10]
 """
 import argparse
 import json
@@ -20,9 +30,13 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from deqsci_amd import _hip, checkpoint  # noqa: E402
+from deqsci_amd import _hip, autograd as ag, checkpoint, vjp  # noqa: E402
 from deqsci_amd.cli import build_pipeline  # noqa: E402
+from deqsci_amd.engine import _Denoiser  # noqa: E402
 from deqsci_amd.networks.simplecnn import RealSNConv2d  # noqa: E402
+
+H = W = 256
+B = 8
 
 
 def timed(fn, reps, warmup, before=None):
@@ -56,10 +70,74 @@ def composed_step(W, u, sigma, eps=1e-12):
     return W / cur_sigma * sigma, u, v, cur_sigma
 
 
+def train_net():
+    net = build_pipeline("RealSN_SimpleCNN", checkpoint.shipped("rsn_cnn"), 10)[0].nonlinear_op.train()
+    for p in net.parameters():
+        p.requires_grad_(True)
+    return net
+
+
+def fcall_and_taped(bsz, reps, warmup, out):
+    """One train-mode f-call of the engine's denoiser, module against train_realsn="device", and the taped call with its backward,
+    autograd against autograd.denoiser_noise(train_realsn=True), on bsz measurements of 256 x 256 x 8.  Every path runs its own copy of
+    the net (each call advances weight_u)."""
+    n = bsz * B
+    gen = torch.Generator(device="cuda").manual_seed(bsz)
+    z1 = torch.rand(bsz, B, H, W, device="cuda", generator=gen)
+    v = torch.randn(n, 1, H, W, device="cuda", generator=gen)
+    dens = {mode: _Denoiser(train_net(), train_realsn=mode) for mode in ("module", "device")}
+    for den in dens.values():
+        den.prepare(4, "cuda", n_img=n)
+    assert dens["device"]._route(n, H, W, "cuda", "fast", False) == "train realsn per layer" and dens["module"]._route(n, H, W, "cuda", "fast", False) == "module"
+    with torch.no_grad():
+        for mode, den in dens.items():
+            out[f"fcall_{mode}_ms_bsz{bsz}"] = timed(lambda _, den=den: den.run(z1, 1), reps, warmup)
+        nets = [train_net(), train_net()]
+        d = _Denoiser(nets[0], train_realsn="device").run(z1, 1)[0]
+        m = _Denoiser(nets[1], train_realsn="module").run(z1, 1)[0]
+        out[f"fcall_rel_l2_bsz{bsz}"] = float((d - m).norm() / m.norm())
+    x = z1.view(n, 1, H, W)
+    net_a, net_d = train_net(), train_net()
+
+    def taped_module(_):
+        return torch.autograd.grad(net_a(x), vjp.grad_parameters(net_a, train_realsn=True), v)
+
+    def taped_device(_):
+        return torch.autograd.grad(ag.denoiser_noise(net_d, x, train_realsn=True), vjp.grad_parameters(net_d, train_realsn=True), v)
+
+    out[f"taped_autograd_ms_bsz{bsz}"] = timed(taped_module, reps, warmup)
+    out[f"taped_device_ms_bsz{bsz}"] = timed(taped_device, reps, warmup)
+    net_a, net_d = train_net(), train_net()
+    out[f"taped_grad_rel_l2_bsz{bsz}"] = max(float((p - q).norm() / q.norm()) for p, q in zip(taped_device(None), taped_module(None)))
+    print(f"bsz {bsz} ({n} images of {H} x {W}): train-mode f-call module {out[f'fcall_module_ms_bsz{bsz}']:.3f} ms, train_realsn='device' "
+          f"{out[f'fcall_device_ms_bsz{bsz}']:.3f} ms (rel L2 {out[f'fcall_rel_l2_bsz{bsz}']:.1e});  taped call + backward autograd "
+          f"{out[f'taped_autograd_ms_bsz{bsz}']:.3f} ms, 'device+realsn' {out[f'taped_device_ms_bsz{bsz}']:.3f} ms "
+          f"(gradients rel L2 {out[f'taped_grad_rel_l2_bsz{bsz}']:.1e})")
+
+
+def packs(reps, warmup, out):
+    """R3 alone per layer shape - every pack of the layer in one launch - against the host packers making the same packs."""
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for cin, cout in ((1, 64), (64, 64), (64, 1)):
+        w = torch.randn(cout, cin, 3, 3, device="cuda", generator=gen)
+        bufs = _hip.realsn_pack_buffers(cin, cout, "cuda")
+        if (cin, cout) == (64, 64):
+            host = lambda _: (_hip.pack_winograd_weights(w), _hip.pack_winograd44_weights(w), _hip.pack_winograd_weights(vjp._transposed(w)))
+        elif cin == 1:
+            host = lambda _: (_hip.pack_c1_to_64_weights(w), _hip.pack_c64_to_1_weights(vjp._transposed(w)))
+        else:
+            host = lambda _: (_hip.pack_c64_to_1_weights(w), _hip.pack_c1_to_64_weights(vjp._transposed(w)))
+        tag = f"{cin}x{cout}"
+        out[f"pack_host_ms_{tag}"] = timed(host, reps, warmup)
+        out[f"pack_r3_ms_{tag}"] = timed(lambda _: _hip.realsn_pack(w, *bufs), reps, warmup)
+        print(f"packs of a ({cout},{cin},3,3) weight: host packers {out[f'pack_host_ms_{tag}'] * 1e3:.1f} us, R3 {out[f'pack_r3_ms_{tag}'] * 1e3:.1f} us (one launch)")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--train-reps", type=int, default=10, help="repeats of the 256 x 256 x 8 f-call and taped-call measurements (0: skip them)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "realsn_bench needs a GPU"
     solver, _ = build_pipeline("RealSN_SimpleCNN", checkpoint.shipped("rsn_cnn"), 10)
@@ -109,6 +187,13 @@ def main():
           f"({out['grad_device_launches']} launches)   x{out['grad_autograd_ms'] / out['grad_device_ms']:.1f}   "
           f"(relative L2 between them {out['grad_rel_l2_device_vs_autograd']:.2e})")
     print(json.dumps(out))
+    if a.train_reps > 0:
+        # the train-mode device paths (train_realsn="device", "device+realsn") at 256 x 256 x 8 with 1 and 8 measurements, and R3 alone
+        out = {"device": torch.cuda.get_device_name(0), "shape": [H, W, B], "reps": a.train_reps}
+        packs(a.reps, a.warmup, out)
+        for bsz in (1, 8):
+            fcall_and_taped(bsz, a.train_reps, 3, out)
+        print(json.dumps(out))
 
 
 if __name__ == "__main__":
