@@ -10,5 +10,9 @@ from .broyden import broyden, broyden_fixed_point  # noqa: F401
 from .epsilon2 import epsilon2  # noqa: F401
 from .engine import DEQSCIEngine, sigma_schedule  # noqa: F401
 from .networks import FFDNet, DnCNN  # noqa: F401
+from .autograd import mse_loss_stats  # noqa: F401
+from .optim import DeviceAdam  # noqa: F401
+from .training import (SCITrainingDatasetSubset, TrainStep, TrainingConfig, configure_training, load_mat,  # noqa: F401
+                       train_solver_sci)
 
 __version__ = "0.1.0"

@@ -96,6 +96,8 @@ SIGNATURES = {
     "deqsci_bn_train_apply_f32": [_ptr, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _int, _i64, _ptr],
     "deqsci_bn_train_grad_stats_f32": [_ptr, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr],
     "deqsci_bn_train_grad_apply_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _ptr, _i64, _ptr],
+    "deqsci_mse_stats_grad_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _f32, _ptr, _ptr],
+    "deqsci_adam_step_f32": [_ptr, _int, _f32, _f32, _f32, _f32, _f32, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -105,7 +107,7 @@ OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunk
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
                  "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
                  "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes", "deqsci_realsn_workspace_bytes",
-                 "deqsci_bn_train_workspace_bytes")
+                 "deqsci_bn_train_workspace_bytes", "deqsci_mse_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -163,6 +165,8 @@ def load():
     lib.deqsci_realsn_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_bn_train_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_bn_train_workspace_bytes.argtypes = [_i64]
+    lib.deqsci_mse_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_mse_workspace_bytes.argtypes = [_i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -2001,6 +2005,97 @@ def tv_chambolle(image, weight=0.1, eps=2e-4, n_iter_max=200, tau=0.25, return_s
                                               float(tau), None if stop is None else stop.data_ptr(), ws.data_ptr(), _stream()),
                "tv_chambolle")
     return (out, stop) if return_stop else out
+
+
+# ----------------------------------------------------------------------------- the training step's glue (csrc/train.hip)
+TRAIN_CHUNK = 4096           # DEQSCI_TRAIN_CHUNK: the elements of a workgroup of csrc/train.hip
+ADAM_MAX_TENSORS = 64        # DEQSCI_ADAM_MAX_TENSORS: the tensors of one deqsci_adam_step_f32 launch
+
+
+class AdamEntry(ctypes.Structure):
+    """deqsci_adam_entry"""
+    _fields_ = [("param", _ptr), ("grad", _ptr), ("exp_avg", _ptr), ("exp_avg_sq", _ptr), ("numel", _i64), ("bc2s", _f32), ("step_size", _f32)]
+
+
+def mse_workspace(total, device):
+    """The caller-owned workspace of mse_stats_grad for `total` elements (float64 words; no initialisation needed)."""
+    return _partials(load().deqsci_mse_workspace_bytes(total), device)
+
+
+def mse_stats_grad(rec, gt, workspace=None, grad=None, stats=None):
+    """L1: the loss gradient and the statistics of a training step in one pass -> (grad, stats).  rec, gt: fp32 tensors of one shape on
+    the device, dense in the same layout (contiguous; a view into a larger buffer will do - 4-byte alignment is enough).  grad =
+    (rec - gt) * (float)(2 / total) in rec's shape; stats (3,) float64 on the device: sum (rec - gt)^2, sum (clamp(rec, 0, 1) - gt)^2 (squares
+    in fp32, sums in float64, csrc/rows.hpp's order: deterministic), the number of non-finite differences.  The loss is stats[0] / total,
+    the batch PSNR 10 log10(total / stats[1]).  No host synchronisation; workspace / grad / stats: given by a caller that must not allocate."""
+    for name, t in (("rec", rec), ("gt", gt)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            raise DeqsciHipError(f"mse_stats_grad: {name} must be a float32 tensor on a HIP device; deqsci_amd has no CPU path")
+    if tuple(rec.shape) != tuple(gt.shape) or not rec.is_contiguous() or not gt.is_contiguous() or rec.device != gt.device:
+        raise DeqsciHipError(f"mse_stats_grad: rec {tuple(rec.shape)} and gt {tuple(gt.shape)} must be contiguous, of one shape, on one device")
+    total = rec.numel()
+    if total == 0:
+        raise DeqsciHipError("mse_stats_grad: empty tensors have no mean squared error")
+    if grad is None:
+        grad = torch.empty_like(rec)
+    elif grad.dtype != torch.float32 or tuple(grad.shape) != tuple(rec.shape) or not grad.is_contiguous() or grad.device != rec.device:
+        raise DeqsciHipError("mse_stats_grad: grad must be a contiguous float32 tensor of rec's shape on rec's device")
+    if stats is None:
+        stats = torch.empty((3,), device=rec.device, dtype=torch.float64)
+    elif stats.dtype != torch.float64 or stats.numel() != 3 or not stats.is_contiguous() or stats.device != rec.device:
+        raise DeqsciHipError("mse_stats_grad: stats must be 3 contiguous float64 values on rec's device")
+    workspace = _partials(load().deqsci_mse_workspace_bytes(total), rec.device, workspace,
+                          "mse_stats_grad: workspace too small (mse_workspace(total, device))")
+    with _dev(rec):
+        _check(load().deqsci_mse_stats_grad_f32(rec.data_ptr(), gt.data_ptr(), grad.data_ptr(), stats.data_ptr(), total,
+                                                ctypes.c_float(2.0 / total), workspace.data_ptr(), _stream()), "mse_stats_grad")
+    return grad, stats
+
+
+def adam_scalars(step, lr, betas):
+    """(bc2s, step_size) of step `step` >= 1 as L2 takes them: sqrt(1 - beta2^t) and lr / (1 - beta1^t), in double."""
+    b1, b2 = betas
+    return math.sqrt(1.0 - b2 ** step), lr / (1.0 - b1 ** step)
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps):
+    """L2: one Adam step (torch-1.9 F.adam, no weight decay, no amsgrad) of the listed tensors, ADAM_MAX_TENSORS per launch -> the number of
+    launches.  params, exp_avgs, exp_avg_sqs are updated IN PLACE through raw pointers (the caller bumps the parameters' version
+    counters); all fp32 on one device, dense (contiguous; views into a flat buffer will do).  step: the step count being taken (>= 1),
+    one int or one per tensor.  Builds the table on the host each call: no device allocation, no synchronisation."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
+        raise DeqsciHipError("adam_step: params, grads, exp_avgs and exp_avg_sqs must have one length")
+    if n == 0:
+        return 0
+    steps = [int(step)] * n if not isinstance(step, (list, tuple)) else [int(s) for s in step]
+    if len(steps) != n or min(steps) < 1:
+        raise DeqsciHipError("adam_step: step must be >= 1, one value or one per tensor")
+    dev = params[0].device
+    for i, quad in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        for name, t in zip(("param", "grad", "exp_avg", "exp_avg_sq"), quad):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
+                    and t.numel() == quad[0].numel() and t.numel() > 0):
+                raise DeqsciHipError(f"adam_step: {name} {i} must be a non-empty contiguous float32 tensor of the parameter's size on {dev}")
+    b1, b2 = float(betas[0]), float(betas[1])
+    lib, launches = load(), 0
+    scalars = {}
+    with _dev(params[0]):
+        st = _stream()
+        for lo in range(0, n, ADAM_MAX_TENSORS):
+            hi = min(n, lo + ADAM_MAX_TENSORS)
+            table = (AdamEntry * (hi - lo))()
+            for j in range(lo, hi):
+                t = steps[j]
+                if t not in scalars:
+                    scalars[t] = adam_scalars(t, float(lr), (b1, b2))
+                e = table[j - lo]
+                e.param, e.grad, e.exp_avg, e.exp_avg_sq = params[j].data_ptr(), grads[j].data_ptr(), exp_avgs[j].data_ptr(), exp_avg_sqs[j].data_ptr()
+                e.numel = params[j].numel()
+                e.bc2s, e.step_size = scalars[t]
+            _check(lib.deqsci_adam_step_f32(ctypes.cast(table, _ptr), hi - lo, b1, 1.0 - b1, b2, 1.0 - b2, float(eps), st), "adam_step")
+            launches += 1
+    return launches
 
 
 # ----------------------------------------------------------------------------- measurement helpers (bench.py)

@@ -29,6 +29,12 @@ A spectrally normalised convolution in train mode (networks.simplecnn.RealSNConv
     weight, u' = realsn(W, u)          one power-iteration step and weight = W / cur_sigma * sigma (csrc/realsn.hip R1; u', v constants)
                                        grad_W = (sigma / cur_sigma) (g - (sum(g W) / cur_sigma) C),  C = d cur_sigma / dW   (R2)
 
+The training loop's loss (deqsci_amd.training, loss_function="device"):
+
+    loss, stats = mse_loss_stats(rec, gt)   loss = sum (rec - gt)^2 / total with grad_rec = grad_loss 2 (rec - gt) / total formed in the forward's
+                                       pass, which also sums the clamped squared error (the batch PSNR) and counts non-finite differences
+                                       (csrc/train.hip L1; CPU tensors: the same arithmetic in torch)
+
 With no mask gradient asked for, every backward makes the launches it always made.  The backwards are once-differentiable.
 (bsz,H,W,B) layout, fp32, GPU - like the forward kernels; there is no CPU path, except for realsn_weight (deqsci_amd.realsn's restatement).
 """
@@ -188,6 +194,39 @@ def denoiser_noise(net, x, sigma=None, frozen_bn=False, train_bn=False, train_re
     params = (vjp.grad_parameters(net, train_realsn=True) if train_realsn else vjp.grad_parameters(net, train_bn=True) if train_bn
               else vjp.grad_parameters(net) if frozen_bn else vjp.conv_weights(net))
     return _DenoiserNoise.apply(net, x, sigma, bool(frozen_bn), bool(train_bn), bool(train_realsn), *params)
+
+
+class _MSELossStats(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rec, gt):
+        total = rec.numel()
+        if rec.is_cuda:
+            grad, stats = _hip.mse_stats_grad(_hip.f32c(rec), _hip.f32c(gt))
+        else:
+            # the same arithmetic in torch, in the tensors' own dtype (sums in float64, in torch's order)
+            d = rec - gt
+            grad = d * torch.tensor(2.0 / total, dtype=rec.dtype)
+            dc = rec.clamp(0, 1) - gt
+            stats = torch.stack([(d * d).double().sum(), (dc * dc).double().sum(), (~torch.isfinite(d)).sum().double()])
+        ctx.grad, ctx.stats = grad, stats
+        ctx.mark_non_differentiable(stats)
+        return (stats[0] / total).to(rec.dtype), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _g_stats):
+        return (g_loss * ctx.grad).view(ctx.grad.shape), None
+
+
+def mse_loss_stats(rec, gt):
+    """-> (loss, stats): the mean squared error of rec against gt as a 0-d tensor of rec's dtype, differentiable in rec, and - detached -
+    stats (3,) float64: sum (rec - gt)^2, sum (clamp(rec, 0, 1) - gt)^2, the number of non-finite differences.  One read-back of stats gives
+    the loss (stats[0] / total), the NaN check (stats[2], or the loss itself) and the batch PSNR, 10 log10(total / stats[1]).  Device
+    tensors (fp32): csrc/train.hip L1, which forms the gradient 2 (rec - gt) / total in the same pass - backward is one multiplication
+    by the incoming gradient; no host synchronisation.  CPU tensors: the same arithmetic in torch.  gt gets no gradient."""
+    if tuple(rec.shape) != tuple(gt.shape) or rec.dtype != gt.dtype or rec.device != gt.device:
+        raise ValueError(f"mse_loss_stats: rec {tuple(rec.shape)} {rec.dtype} on {rec.device} and gt {tuple(gt.shape)} {gt.dtype} on {gt.device} differ")
+    return _MSELossStats.apply(rec, gt.detach())
 
 
 def taping(*tensors):

@@ -57,6 +57,32 @@ def load_solver(solver, path):
     return epoch
 
 
+def save_training(path, solver, epoch, optimizer, scheduler=None):
+    """The reference's training checkpoint (training/sci_equilibrium_training.py:126-130, :143-147): a pickle of {'solver_state_dict',
+    'epoch', 'optimizer_state_dict', 'scheduler_state_dict'} - the solver's parameters AND buffers (BatchNorm's running statistics, a
+    RealSNConv2d's weight_u), which load_solver reads back.  scheduler=None stores None."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save({'solver_state_dict': solver.state_dict(),
+                'epoch': epoch,
+                'optimizer_state_dict': optimizer.state_dict(),
+                'scheduler_state_dict': None if scheduler is None else scheduler.state_dict()}, path)
+
+
+def load_training(path, solver, optimizer=None, scheduler=None):
+    """Resume from a save_training checkpoint (or one of the reference's): the solver as load_solver loads it and, where given and
+    stored, the optimizer's and the scheduler's state -> the stored epoch (resume at epoch + 1, video_sci_proxgrad.py:216)."""
+    epoch = load_solver(solver, path)
+    if optimizer is None and scheduler is None:
+        return epoch
+    obj = torch.load(path, map_location="cpu", weights_only=False)
+    for what, key in ((optimizer, 'optimizer_state_dict'), (scheduler, 'scheduler_state_dict')):
+        if what is not None:
+            if not isinstance(obj, dict) or obj.get(key) is None:
+                raise KeyError(f"checkpoint {path!r} holds no {key!r}")
+            what.load_state_dict(obj[key])
+    return epoch
+
+
 def shipped(name):
     """Path of a shipped archive: 'cnn', 'rsn_cnn' (reference models/*.ckpt) or 'ffdnet_gray'
     (networks/ffdnet/models/net_gray.pth - substitute for the reference's missing ffdnet.ckpt)."""

@@ -1,11 +1,17 @@
-"""Command-line driver with the reference's flags (video_sci_proxgrad.py:23-49), inference only.
+"""Command-line driver with the reference's flags (video_sci_proxgrad.py:23-49): inference, and training with `--inference False`.
 
     python -m deqsci_amd.cli --denoiser ffdnet --loadpath deqsci_amd/weights/ffdnet_gray.npz \\
         --testpath data/test_gray/ --and_maxiters 180 --inference True [--gpu_ids 0,1,2,3]
 
-Every flag of the reference parses (so its test_*.sh command lines run unchanged); the training-only ones
-(--n_epochs --batch_size --lr --lr_gamma --sched_step --trainpath --print_every_n_steps --save_every_n_steps --etainit
---sigma) are accepted and ignored, and `--inference False` is refused: training is outside this build.
+Every flag of the reference parses (so its test_*.sh and train_*.sh command lines run unchanged); --etainit and --sigma are accepted and
+ignored.  `--inference False` trains (deqsci_amd.training.train_solver_sci, the reference's loop): --trainpath DIR/ holds mask.mat, gt/ and
+measurement/; --n_epochs --batch_size --lr --lr_gamma --sched_step --print_every_n_steps --save_every_n_steps as in the reference; resumed
+from --loadpath (a missing file is an error; without the flag: random weights), checkpoints under --savepath + 'model/'.  Single device.  `--train_backend device|autograd`,
+`--seed` and `--max_steps` are this build's ("Training").
+
+    python -m deqsci_amd.cli --inference False --denoiser SimpleCNN --loadpath deqsci_amd/weights/cnn.npz --trainpath data/train/ \\
+        --savepath save/cnn/ --and_maxiters 30 --batch_size 8 --lr 1e-4 --n_epochs 80
+
 `--gpu_ids a,b,..` with more than one id is this build's addition: one process per listed GPU, every clip's
 measurements sharded over them (deqsci_amd.distributed), rank 0 prints and writes the PNGs.
 `--ssim` (also this build's) adds the per-clip SSIM and a 'Total Average SSIM' line (window 11, `--ssim_mode same|valid`).
@@ -44,6 +50,8 @@ from .epsilon2 import epsilon2
 from .solvers import DEQFixedPoint, EquilibriumProxGradSCI, andersonexp, forward_iteration
 
 SHIPPED = {'ffdnet': 'ffdnet_gray', 'SimpleCNN': 'cnn', 'RealSN_SimpleCNN': 'rsn_cnn'}
+# --train_backend's default: decided by the measurement in profiles/train.md (tools/train_bench.py)
+TRAIN_BACKEND_DEFAULT = 'device'
 # denoisers the reference's command line names and has weights for, but none trained for SCI: no shipped default, --loadpath names the checkpoint
 NO_DEFAULT = {'DnCNN': "the Provable-PnP DnCNN of 17 layers (a Gaussian denoiser: networks/provable/Pretrained_models/DnCNN_noise{5,15,40}.pth of the "
                        "reference, or tests/golden/dncnn_noise15.npz of this repository)"}
@@ -112,7 +120,7 @@ def write_trace(path, results):
 
 
 def parser():
-    p = argparse.ArgumentParser(description="DEQ-SCI inference on MI355X")
+    p = argparse.ArgumentParser(description="DEQ-SCI inference and training on MI355X")
     p.add_argument('--gpu_ids', default='0')
     p.add_argument('--and_maxiters', default=100, type=int)
     p.add_argument('--and_beta', type=float, default=1.0)
@@ -170,18 +178,71 @@ def parser():
                    help="(this build) --solver epsilon2: the regulariser added to |d2|^2 in the extrapolation's denominator")
     p.add_argument('--jacobian_json', default=None, metavar='FILE',
                    help="(this build) write the per-measurement Jacobian values and the histories of their iterations to FILE.  Implies --jacobian")
-    ignored = p.add_argument_group("accepted for command-line compatibility, unused by inference")
-    ignored.add_argument('--n_epochs', default=80)
-    ignored.add_argument('--batch_size', type=int, default=1)
-    ignored.add_argument('--lr', type=float, default=0.0001)
+    train = p.add_argument_group("training (--inference False)")
+    train.add_argument('--n_epochs', type=int, default=80)
+    train.add_argument('--batch_size', type=int, default=1)
+    train.add_argument('--lr', type=float, default=0.0001)
+    train.add_argument('--lr_gamma', type=float, default=0.9)
+    train.add_argument('--sched_step', type=int, default=10)
+    train.add_argument('--trainpath', default="", help="directory with mask.mat, gt/ and measurement/ (joined as strings: end it in '/')")
+    train.add_argument('--print_every_n_steps', type=int, default=1)
+    train.add_argument('--save_every_n_steps', type=int, default=50)
+    train.add_argument('--train_backend', default=TRAIN_BACKEND_DEFAULT, choices=['device', 'autograd'],
+                       help="(this build) device = the backward, the loss / PSNR / NaN glue and Adam on the HIP kernels, as far as the denoiser "
+                            "is served (training.configure_training prints what it chose); autograd = torch's, as the reference")
+    train.add_argument('--seed', type=int, default=None, help="(this build) torch.manual_seed before the data loader is built (the shuffle)")
+    train.add_argument('--max_steps', type=int, default=None, help="(this build) stop after this many training steps in all")
+    ignored = p.add_argument_group("accepted for command-line compatibility, unused")
     ignored.add_argument('--etainit', type=float, default=0.9)
-    ignored.add_argument('--lr_gamma', type=float, default=0.9)
-    ignored.add_argument('--sched_step', type=int, default=10)
-    ignored.add_argument('--trainpath', default="")
-    ignored.add_argument('--print_every_n_steps', type=int, default=1)
-    ignored.add_argument('--save_every_n_steps', type=int, default=50)
     ignored.add_argument('--sigma', type=int, default=0)
     return p
+
+
+def train(args):
+    """--inference False (video_sci_proxgrad.py:98-135, 193-202, 241-270): the denoiser in train mode, Adam + StepLR, MSELoss, a shuffled
+    DataLoader over --trainpath, resumed from --loadpath, checkpoints under --savepath + 'model/'."""
+    from . import training
+    from .optim import DeviceAdam
+    _, _, _, dev = distributed.init_from_env("nccl")
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    dataset = training.SCITrainingDatasetSubset(args.trainpath + 'gt/', args.trainpath + 'measurement/', args.trainpath + 'mask.mat')
+    dataloader = torch.utils.data.DataLoader(dataset=dataset, batch_size=args.batch_size, shuffle=True, drop_last=True, pin_memory=True)
+    test_dataset = SCITestDataset(args.testpath) if args.testpath and os.path.isdir(args.testpath) else None
+    solver, deq = build_pipeline(args.denoiser, None, args.and_maxiters, args.and_m, args.and_beta, device=dev)
+    solver.nonlinear_op.train()
+    for p in solver.parameters():
+        p.requires_grad_(True)
+    device = args.train_backend == 'device'
+    optimizer = (DeviceAdam if device else torch.optim.Adam)(params=solver.parameters(), lr=args.lr)
+    scheduler = torch.optim.lr_scheduler.StepLR(optimizer=optimizer, step_size=args.sched_step, gamma=args.lr_gamma)
+    start_epoch = 0
+    if args.loadpath:
+        epoch = checkpoint.load_solver(solver, args.loadpath)         # (the solver alone, as the reference: optimizer and scheduler start afresh)
+        start_epoch = 0 if epoch is None else int(epoch) + 1
+        print('loaded dict!')
+        if start_epoch:
+            print(f"the checkpoint's epoch is {epoch}: training continues at epoch {start_epoch} of --n_epochs {args.n_epochs}"
+                  + (" - nothing left to do" if start_epoch >= args.n_epochs else ""))
+    opts = {}
+    if args.conv64 != 'auto':
+        opts["conv64"] = args.conv64
+    if args.anderson_arith != 'reference':
+        opts["anderson_arith"] = args.anderson_arith
+    deq.engine_options = opts
+    cfg = training.configure_training(deq, args.train_backend)
+    print(f"train backend {cfg.backend}: implicit_backward={cfg.implicit_backward} parameter_backward={cfg.parameter_backward} "
+          f"engine_options={cfg.engine_options}" + "".join(f"\n  {k} stays on autograd: {v}" for k, v in cfg.reasons.items()))
+    save_model_path = args.savepath + 'model/'
+    for path in (save_model_path, args.savepath + 'img/train/', args.savepath + 'img/test/'):
+        os.makedirs(path, exist_ok=True)
+    return training.train_solver_sci(
+        single_iterate_solver=solver, train_dataloader=dataloader, optimizer=optimizer, save_model_path=save_model_path,
+        loss_function="device" if device else torch.nn.MSELoss(reduction='mean'), n_epochs=args.n_epochs, deep_eq_module=deq,
+        use_dataparallel=False, scheduler=scheduler, print_every_n_steps=args.print_every_n_steps,
+        save_every_n_steps=args.save_every_n_steps, start_epoch=start_epoch, test_dataloader=test_dataset,
+        train_img_path=args.savepath + 'img/train/', test_img_path=args.savepath + 'img/test/', best_img_path=args.savepath + 'img/best/',
+        tflog_path=args.savepath, max_steps=args.max_steps)
 
 
 def run(args):
@@ -257,11 +318,22 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.solver in ('broyden', 'epsilon2') and (args.snapshots is not None or args.trace):
         p.error(f"--snapshots / --trace come out of the engine's Anderson / Picard loop: not available with --solver {args.solver}")
-    if str(args.inference).lower() in ('false', '0', ''):
-        sys.exit("deqsci_amd is the inference hot path only: --inference False (training) is out of scope")
     if args.denoiser not in SHIPPED and args.denoiser not in NO_DEFAULT:
         raise NotImplementedError('unknown denoiser!')
-    if args.baseline is None:
+    training = str(args.inference).lower() in ('false', '0', '')
+    if training:
+        if not args.trainpath:
+            sys.exit("--inference False trains: --trainpath DIR/ (with mask.mat, gt/ and measurement/) is needed")
+        ids = [int(v) for v in str(args.gpu_ids).split(',') if v != '']
+        if len(ids) > 1:
+            sys.exit(f"--gpu_ids {args.gpu_ids}: training is single-device in this build (data-parallel training is out of scope)")
+        if args.loadpath and not os.path.exists(args.loadpath):
+            sys.exit(f"--loadpath {args.loadpath}: no such file (the reference would silently train from random weights; omit the flag for that)")
+        if args.solver != 'anderson' or args.baseline is not None or args.snapshots is not None or args.trace or args.jacobian is not None \
+                or args.jacobian_json or args.init_point != 'At':
+            sys.exit("--inference False trains the DEQ with Anderson acceleration from At(y, Phi), as the reference: --solver, --baseline, "
+                     "--init_point, --snapshots, --trace and --jacobian are inference's")
+    if args.baseline is None and not training:                        # (training looks up no shipped default: --loadpath '' starts from random weights, as the reference)
         try:
             default_loadpath(args.denoiser, args.loadpath)
         except ValueError as e:
@@ -284,7 +356,7 @@ def main(argv=None):
         sys.exit("deqsci_amd needs an MI355X: there is no CPU path")
     if len(ids) == 1 and "LOCAL_RANK" not in os.environ:
         os.environ["LOCAL_RANK"] = str(ids[0])
-    return run(args)
+    return train(args) if training else run(args)
 
 
 if __name__ == "__main__":

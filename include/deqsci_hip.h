@@ -632,6 +632,46 @@ int deqsci_bn_train_grad_stats_f32(const float* gy, const float* c, const double
 int deqsci_bn_train_grad_apply_f32(const float* gy, const float* c, const double* record, const double* grad_record, const float* gamma,
                                    double eps, float* dc, int64_t P, deqsci_stream_t stream);
 
+/* ---- the training step's glue (csrc/train.hip): loss, PSNR, NaN check and loss gradient in one pass; Adam for many tensors in one launch ----
+ * L1  rec, gt: flat fp32 of `total` elements in the same layout (the batch as ONE row), 4-byte aligned.  Per element, in fp32:
+ *     d = rec - gt, grad = d * scale (the caller passes scale = (float)(2.0 / total): the gradient of the mean squared error),
+ *     dc = clamp(rec, 0, 1) - gt (NaN kept).  stats[0] = sum d * d, stats[1] = sum dc * dc (squares in fp32, sums in float64),
+ *     stats[2] = the number of non-finite d.  A NaN or Inf in d is counted, enters stats[0] as it is, and the gradient is written all
+ *     the same.  The loss is stats[0] / total and the batch PSNR 10 log10(total / stats[1]) (harness.psnr's arithmetic).
+ *     Deterministic: the two-stage order of csrc/rows.hpp over chunks of DEQSCI_TRAIN_CHUNK elements, stage 2 by one workgroup, no
+ *     atomics; the sums do not depend on the pointers' alignment (rec, gt and grad all 16-byte aligned: read as float4).
+ *     grad (total) fp32 must not overlap rec or gt; stats: 3 float64, 8-byte aligned; workspace = deqsci_mse_workspace_bytes(total)
+ *     bytes (0 for invalid sizes), 8-byte aligned, no initialisation needed; overlaps among the outputs: -4.  total = 0: -2.
+ *     Two launches on `stream`; no allocation, no host synchronisation, graph-capturable. */
+#define DEQSCI_TRAIN_CHUNK 4096
+size_t deqsci_mse_workspace_bytes(int64_t total);
+int deqsci_mse_stats_grad_f32(const float* rec, const float* gt, float* grad, double* stats, int64_t total, float scale, void* workspace,
+                              deqsci_stream_t stream);
+
+/* L2  one Adam step (torch-1.9 F.adam: no weight decay, no amsgrad) of n_tensors <= DEQSCI_ADAM_MAX_TENSORS tensors in ONE launch.
+ *     entries: n_tensors records in HOST memory, read before the call returns (the table travels by value in the kernel's arguments:
+ *     64 x 48 bytes + the chunk prefix sums fit the 4096 bytes a HIP kernel's arguments may take, so no device buffer is staged, nothing
+ *     allocated and nothing synchronised).  Per element, in fp32, each operation rounded separately, in this order:
+ *         m = m * beta1 + g * one_minus_beta1;  v = v * beta2 + (g * g) * one_minus_beta2;
+ *         den = sqrtf(v) / bc2s + eps;  p = p - step_size * (m / den)
+ *     with bc2s = sqrt(1 - beta2^t) and step_size = lr / (1 - beta1^t) of the entry (t = the tensor's own step count), computed by the
+ *     caller in double and passed as floats; division and square root correctly rounded.  param, exp_avg, exp_avg_sq are updated in
+ *     place.  Pointers 4-byte aligned (a tensor whose four pointers are 16-byte aligned is walked as float4 with a scalar tail, any
+ *     other element by element: the same values); the four ranges of an entry must not overlap (-4).  numel >= 1.  n_tensors = 0:
+ *     nothing is launched; more than DEQSCI_ADAM_MAX_TENSORS: -4 (the caller launches once per table). */
+#define DEQSCI_ADAM_MAX_TENSORS 64
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    float bc2s;
+    float step_size;
+} deqsci_adam_entry;
+int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
+                         float one_minus_beta2, float eps, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
