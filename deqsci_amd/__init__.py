@@ -16,3 +16,14 @@ from .training import (SCITrainingDatasetSubset, TrainStep, TrainingConfig, conf
                        train_solver_sci)
 
 __version__ = "0.1.0"
+
+# deqsci_amd.synth's names, resolved on first use: the module is also a program (`python -m deqsci_amd.synth write ...`), and runpy
+# warns about a module the package has already imported when it starts
+_SYNTH_EXPORTS = ("PatchSpec", "SynthTrainLoader", "VideoPool", "load_video", "sample_specs", "synthesize", "write_training_directory")
+
+
+def __getattr__(name):
+    if name in _SYNTH_EXPORTS:
+        from . import synth
+        return getattr(synth, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -98,6 +98,8 @@ SIGNATURES = {
     "deqsci_bn_train_grad_apply_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _ptr, _i64, _ptr],
     "deqsci_mse_stats_grad_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _f32, _ptr, _ptr],
     "deqsci_adam_step_f32": [_ptr, _int, _f32, _f32, _f32, _f32, _f32, _ptr],
+    "deqsci_synth_batch_u8": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
+    "deqsci_rgb_to_gray_u8": [_ptr, _ptr, _i64, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -2096,6 +2098,54 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps):
             _check(lib.deqsci_adam_step_f32(ctypes.cast(table, _ptr), hi - lo, b1, 1.0 - b1, b2, 1.0 - b2, float(eps), st), "adam_step")
             launches += 1
     return launches
+
+
+# ----------------------------------------------------------------------------- training batches out of raw video (csrc/synth.hip)
+SYNTH_ROW_WORDS, SYNTH_MAX_ROWS, SYNTH_MAX_FRAMES = 10, 64, 64     # DEQSCI_SYNTH_ROW_WORDS, DEQSCI_SYNTH_MAX_ROWS, DEQSCI_SYNTH_MAX_FRAMES
+SYNTH_FLIP_H, SYNTH_FLIP_V, SYNTH_TRANSPOSE = 1, 2, 4              # DEQSCI_SYNTH_FLIP_H, DEQSCI_SYNTH_FLIP_V, DEQSCI_SYNTH_TRANSPOSE
+
+
+def synth_batch(pool, table, mask, H, W, B, gt=None, meas=None):
+    """Y1: a training batch out of a pool of uint8 frames -> (gt (bsz,H,W,B), meas (bsz,H,W)), fp32 on the pool's device.  pool: a
+    contiguous uint8 tensor on the device, every video a (T,Hv,Wv) block; table: bsz rows {video_offset, T, Hv, Wv, t0, dt, y0, x0, ds,
+    flags} of int64 on the HOST (anything numpy turns into a (bsz, 10) int64 array); mask: fp32 (H,W,B), one for all samples, or
+    (bsz,H,W,B).  The library checks every row against its video and the pool before it launches anything (a row that leaves them:
+    DeqsciHipError, code -2).  No host synchronisation; gt / meas: given by a caller that must not allocate."""
+    import numpy as np
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous()):
+        raise DeqsciHipError("synth_batch: pool must be a contiguous uint8 tensor on a HIP device; deqsci_amd has no CPU path")
+    rows = np.ascontiguousarray(np.asarray(table, dtype=np.int64))
+    if rows.ndim != 2 or rows.shape[1] != SYNTH_ROW_WORDS:
+        raise DeqsciHipError(f"synth_batch: the table must be (bsz, {SYNTH_ROW_WORDS}) integers, got {rows.shape}")
+    bsz, H, W, B = rows.shape[0], int(H), int(W), int(B)
+    if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.float32 and mask.is_contiguous() and mask.device == pool.device
+            and tuple(mask.shape) in ((H, W, B), (bsz, H, W, B))):
+        raise DeqsciHipError(f"synth_batch: mask must be a contiguous float32 tensor of shape ({H},{W},{B}) or ({bsz},{H},{W},{B}) on the pool's device")
+    shapes = {"gt": (bsz, H, W, B), "meas": (bsz, H, W)}
+    outs = {"gt": gt, "meas": meas}
+    for name, t in outs.items():
+        if t is None:
+            outs[name] = torch.empty(shapes[name], device=pool.device, dtype=torch.float32)
+        elif t.dtype != torch.float32 or tuple(t.shape) != shapes[name] or not t.is_contiguous() or t.device != pool.device:
+            raise DeqsciHipError(f"synth_batch: {name} must be a contiguous float32 tensor of shape {shapes[name]} on the pool's device")
+    stride = H * W * B if mask.dim() == 4 else 0
+    with _dev(pool):
+        _check(load().deqsci_synth_batch_u8(pool.data_ptr(), pool.numel(), rows.ctypes.data, bsz, mask.data_ptr(), stride, outs["gt"].data_ptr(),
+                                            outs["meas"].data_ptr(), H, W, B, _stream()), "synth_batch")
+    return outs["gt"], outs["meas"]
+
+
+def rgb_to_gray(rgb, out=None):
+    """Y0: (..., 3) uint8 RGB on the device -> (...) uint8, (77 R + 150 G + 29 B + 128) >> 8 in integers."""
+    if not (isinstance(rgb, torch.Tensor) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.is_contiguous() and rgb.dim() >= 1 and rgb.shape[-1] == 3):
+        raise DeqsciHipError("rgb_to_gray: a contiguous uint8 tensor (..., 3) on a HIP device; deqsci_amd has no CPU path")
+    if out is None:
+        out = torch.empty(rgb.shape[:-1], device=rgb.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(rgb.shape[:-1]) or not out.is_contiguous() or out.device != rgb.device:
+        raise DeqsciHipError("rgb_to_gray: out must be a contiguous uint8 tensor of rgb's leading shape on rgb's device")
+    with _dev(rgb):
+        _check(load().deqsci_rgb_to_gray_u8(rgb.data_ptr(), out.data_ptr(), out.numel(), _stream()), "rgb_to_gray")
+    return out
 
 
 # ----------------------------------------------------------------------------- measurement helpers (bench.py)

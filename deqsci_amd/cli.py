@@ -8,6 +8,8 @@ ignored.  `--inference False` trains (deqsci_amd.training.train_solver_sci, the 
 measurement/; --n_epochs --batch_size --lr --lr_gamma --sched_step --print_every_n_steps --save_every_n_steps as in the reference; resumed
 from --loadpath (a missing file is an error; without the flag: random weights), checkpoints under --savepath + 'model/'.  Single device.  `--train_backend device|autograd`,
 `--seed` and `--max_steps` are this build's ("Training").
+`--trainvideos DIR --trainmask FILE` (this build's) train from raw video in place of --trainpath: patches of --patch_size x --patch_size x
+--frames are cut out of the videos, turned (--augment) and measured on the device, --patches_per_epoch per epoch (deqsci_amd.synth).
 
     python -m deqsci_amd.cli --inference False --denoiser SimpleCNN --loadpath deqsci_amd/weights/cnn.npz --trainpath data/train/ \\
         --savepath save/cnn/ --and_maxiters 30 --batch_size 8 --lr 1e-4 --n_epochs 80
@@ -185,6 +187,16 @@ def parser():
     train.add_argument('--lr_gamma', type=float, default=0.9)
     train.add_argument('--sched_step', type=int, default=10)
     train.add_argument('--trainpath', default="", help="directory with mask.mat, gt/ and measurement/ (joined as strings: end it in '/')")
+    train.add_argument('--trainvideos', default="", metavar='DIR',
+                       help="(this build) train from raw video instead of --trainpath: a directory of .npy ((T,H,W) or (T,H,W,3) uint8) / .mat (key "
+                            "'orig') videos; patches are cut, turned and measured on the device, per batch (deqsci_amd.synth)")
+    train.add_argument('--trainmask', default="", metavar='FILE',
+                       help="(this build) with --trainvideos: a .mat with key 'mask' (a test clip will do); its leading --patch_size x --patch_size x --frames corner is used")
+    train.add_argument('--patches_per_epoch', type=int, default=1024, help="(this build) with --trainvideos: the samples drawn per epoch")
+    train.add_argument('--patch_size', type=int, default=256, help="(this build) with --trainvideos: the side of a patch")
+    train.add_argument('--frames', type=int, default=8, help="(this build) with --trainvideos: the frames of a measurement")
+    train.add_argument('--augment', default='flip,transpose,reverse',
+                       help="(this build) with --trainvideos: a comma-separated choice of flip, transpose, reverse (the clip played backwards), or none")
     train.add_argument('--print_every_n_steps', type=int, default=1)
     train.add_argument('--save_every_n_steps', type=int, default=50)
     train.add_argument('--train_backend', default=TRAIN_BACKEND_DEFAULT, choices=['device', 'autograd'],
@@ -206,8 +218,11 @@ def train(args):
     _, _, _, dev = distributed.init_from_env("nccl")
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    dataset = training.SCITrainingDatasetSubset(args.trainpath + 'gt/', args.trainpath + 'measurement/', args.trainpath + 'mask.mat')
-    dataloader = torch.utils.data.DataLoader(dataset=dataset, batch_size=args.batch_size, shuffle=True, drop_last=True, pin_memory=True)
+    if args.trainvideos:
+        dataloader = None                                             # (built below: its first epoch is the one the checkpoint continues at)
+    else:
+        dataset = training.SCITrainingDatasetSubset(args.trainpath + 'gt/', args.trainpath + 'measurement/', args.trainpath + 'mask.mat')
+        dataloader = torch.utils.data.DataLoader(dataset=dataset, batch_size=args.batch_size, shuffle=True, drop_last=True, pin_memory=True)
     test_dataset = SCITestDataset(args.testpath) if args.testpath and os.path.isdir(args.testpath) else None
     solver, deq = build_pipeline(args.denoiser, None, args.and_maxiters, args.and_m, args.and_beta, device=dev)
     solver.nonlinear_op.train()
@@ -224,6 +239,14 @@ def train(args):
         if start_epoch:
             print(f"the checkpoint's epoch is {epoch}: training continues at epoch {start_epoch} of --n_epochs {args.n_epochs}"
                   + (" - nothing left to do" if start_epoch >= args.n_epochs else ""))
+    if dataloader is None:
+        from . import synth
+        pool = synth.VideoPool(synth.list_videos(args.trainvideos), dev)
+        mask = synth.load_mask(args.trainmask, args.patch_size, args.patch_size, args.frames)
+        dataloader = synth.SynthTrainLoader(pool, mask, args.batch_size, args.patches_per_epoch, args.patch_size, args.patch_size, args.frames,
+                                            seed=0 if args.seed is None else args.seed, start_epoch=start_epoch, augment=synth.parse_augment(args.augment))
+        print(f"training from {len(pool)} videos ({pool.nbytes / 1e6:.1f} MB on {dev}): {len(dataloader)} batches of {args.batch_size} patches "
+              f"{args.patch_size}x{args.patch_size}x{args.frames} per epoch")
     opts = {}
     if args.conv64 != 'auto':
         opts["conv64"] = args.conv64
@@ -322,8 +345,20 @@ def main(argv=None):
         raise NotImplementedError('unknown denoiser!')
     training = str(args.inference).lower() in ('false', '0', '')
     if training:
-        if not args.trainpath:
-            sys.exit("--inference False trains: --trainpath DIR/ (with mask.mat, gt/ and measurement/) is needed")
+        if args.trainvideos and args.trainpath:
+            p.error("--trainvideos and --trainpath exclude one another: one source of training samples")
+        if args.trainvideos:
+            if not args.trainmask:
+                p.error("--trainvideos needs --trainmask FILE (a .mat with key 'mask')")
+            from .synth import parse_augment
+            try:
+                parse_augment(args.augment)
+            except ValueError as e:
+                p.error(f"--{e}")
+            if args.patches_per_epoch < args.batch_size:
+                p.error(f"--patches_per_epoch {args.patches_per_epoch} is less than one batch (--batch_size {args.batch_size})")
+        elif not args.trainpath:
+            sys.exit("--inference False trains: --trainpath DIR/ (with mask.mat, gt/ and measurement/) or --trainvideos DIR with --trainmask FILE is needed")
         ids = [int(v) for v in str(args.gpu_ids).split(',') if v != '']
         if len(ids) > 1:
             sys.exit(f"--gpu_ids {args.gpu_ids}: training is single-device in this build (data-parallel training is out of scope)")

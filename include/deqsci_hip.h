@@ -672,6 +672,37 @@ typedef struct {
 int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
                          float one_minus_beta2, float eps, deqsci_stream_t stream);
 
+/* ---- training batches out of raw video (csrc/synth.hip): crop, augment and snapshot synthesis in one launch per 64 samples ----
+ * Y1  pool: `pool_bytes` bytes of uint8 frames on the device, every video a contiguous (T,Hv,Wv) block.  table: bsz rows of
+ *     DEQSCI_SYNTH_ROW_WORDS int64 in HOST memory, read before the call returns (the rows travel by value in the kernel's arguments,
+ *     DEQSCI_SYNTH_MAX_ROWS per launch: nothing staged, nothing allocated, nothing synchronised, no atomics):
+ *         {video_offset, T, Hv, Wv, t0, dt, y0, x0, ds, flags}
+ *     video_offset = the video's first byte in the pool; dt = the signed, non-zero step in frames (negative: the clip played backwards);
+ *     ds >= 1 = the step in pixels; flags = DEQSCI_SYNTH_FLIP_H | _FLIP_V | _TRANSPOSE.  Output pixel (i,j), frame b of a sample:
+ *         (Hc,Wc) = transpose ? (W,H) : (H,W);  (r,c) = transpose ? (j,i) : (i,j);  flip_v: r = Hc-1-r;  flip_h: c = Wc-1-c
+ *         u = video[t0 + dt b, y0 + ds r, x0 + ds c]
+ *         gt[i,j,b] = (float)u / 255.0f;   s = 0, then s = s + mask[i,j,b] * (float)u for b = 0..B-1;   meas[i,j] = s / 255.0f
+ *     in fp32, the product and the sum rounded separately, both divisions correctly rounded.  With a mask of zeros and ones and
+ *     B <= 64 the sums are integers below 2^24, so gt and meas are the floats nearest u / 255 and sum / 255: what a loader of the
+ *     reference's training directory (uint8 patches, float64 sums, / 255 in double) returns.
+ *     gt (bsz,H,W,B), meas (bsz,H,W), mask (H,W,B) fp32, 4-byte aligned (float4 accesses where B % 4 == 0 and gt, mask and mask_stride
+ *     allow them: the same values); mask_stride = elements from one sample's mask to the next (>= H W B), 0 = one mask for all.
+ *     1 <= B <= DEQSCI_SYNTH_MAX_FRAMES, H, W >= 1 (any value).  EVERY row is checked on the host before the first launch: all B source
+ *     frames and the four corners of the crop inside the video, the video inside the pool - DEQSCI_ERR_SHAPE otherwise, so the kernel
+ *     never reads out of bounds; unknown flag bits, or an output overlapping another buffer: DEQSCI_ERR_UNSUPPORTED.  bsz = 0: nothing
+ *     is launched. */
+#define DEQSCI_SYNTH_ROW_WORDS 10
+#define DEQSCI_SYNTH_MAX_ROWS 64
+#define DEQSCI_SYNTH_MAX_FRAMES 64
+#define DEQSCI_SYNTH_FLIP_H 1
+#define DEQSCI_SYNTH_FLIP_V 2
+#define DEQSCI_SYNTH_TRANSPOSE 4
+int deqsci_synth_batch_u8(const uint8_t* pool, int64_t pool_bytes, const int64_t* table, int64_t bsz, const float* mask, int64_t mask_stride,
+                          float* gt, float* meas, int64_t H, int64_t W, int64_t B, deqsci_stream_t stream);
+/* Y0  (n,3) uint8 RGB -> (n) uint8 luma, (77 R + 150 G + 29 B + 128) >> 8 in integer arithmetic (exact); gray must not overlap rgb (-4);
+ *     n = 0: nothing is launched. */
+int deqsci_rgb_to_gray_u8(const uint8_t* rgb, uint8_t* gray, int64_t n, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */
