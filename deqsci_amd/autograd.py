@@ -126,10 +126,12 @@ class _DenoiserNoise(torch.autograd.Function):
     inputs so that autograd routes their gradients; the forward reads them from `net` (the same tensors).  sigma: FFDNet's noise levels
     (data: no gradient); FFDNet detaches its input, so it returns no input gradient either."""
 
+    FIXED = 4                      # the inputs in front of *params: net, x, sigma, mode
+
     @staticmethod
-    def forward(ctx, net, x, sigma, frozen_bn, train_bn, train_realsn, *params):
+    def forward(ctx, net, x, sigma, mode, *params):
         from . import vjp
-        ctx.pg = vjp.DenoiserParamGrads(net, x, sigma, frozen_bn, train_bn, train_realsn)
+        ctx.pg = vjp.DenoiserParamGrads(net, x, sigma, mode=mode)
         return ctx.pg.noise
 
     @staticmethod
@@ -138,11 +140,11 @@ class _DenoiserNoise(torch.autograd.Function):
         if pg is None:
             raise RuntimeError("denoiser_noise: backward ran already (the kept activations are freed after the first)")
         try:
-            dws = pg.grads(gv, need=ctx.needs_input_grad[6:])
+            dws = pg.grads(gv, need=ctx.needs_input_grad[_DenoiserNoise.FIXED:])
             gx = pg.vjp(gv) if ctx.needs_input_grad[1] and not pg.ffdnet else None
         finally:
             pg.release()
-        return (None, gx, None, None, None, None) + tuple(dws)
+        return (None, gx) + (None,) * (_DenoiserNoise.FIXED - 2) + tuple(dws)
 
 
 class _RealSNWeight(torch.autograd.Function):
@@ -182,18 +184,15 @@ def realsn_weight(weight_orig, u, sigma=1.0, n_power_iterations=1, eps=1e-12):
     return _RealSNWeight.apply(weight_orig, u, float(sigma), int(n_power_iterations), float(eps))
 
 
-def denoiser_noise(net, x, sigma=None, frozen_bn=False, train_bn=False, train_realsn=False):
+def denoiser_noise(net, x, sigma=None, frozen_bn=False, train_bn=False, train_realsn=False, *, mode=None):
     """net(x) - net(x, sigma) for FFDNet - with the weight gradients (and the input gradient, where x requires one and the net does not
-    detach it) formed on the device.  frozen_bn=True: the nets vjp.param_eligibility(net, frozen_bn=True) accepts; the gradients go to
-    vjp.grad_parameters(net), the BatchNorm's gamma and beta among them.  train_bn=True: the nets vjp.param_eligibility(net, train_bn=True)
-    accepts, normalised by the batch (csrc/bn_train.hip); the call moves the BatchNorms' running buffers as the module's own forward would.
-    train_realsn=True: the nets vjp.param_eligibility(net, train_realsn=True) accepts - RealSN_SimpleCNN in train mode; the call takes every
-    RealSNConv2d's power step in the module's weight_u / weight buffers as its own forward would (csrc/realsn.hip R1, R3), and the gradients
-    go to the layers' weight_orig (R2)."""
+    detach it) formed on the device, in the mode of vjp.GRAD_MODES the keywords name: the nets vjp.param_eligibility accepts under the same
+    keywords, the gradients going to the mode's parameters (vjp.grad_parameters).  The train modes move the module's buffers as its own
+    forward would: train_bn the BatchNorms' running statistics, train_realsn every RealSNConv2d's weight_u / weight.  mode: a caller's
+    vjp.GradMode in hand, in place of the keywords."""
     from . import vjp
-    params = (vjp.grad_parameters(net, train_realsn=True) if train_realsn else vjp.grad_parameters(net, train_bn=True) if train_bn
-              else vjp.grad_parameters(net) if frozen_bn else vjp.conv_weights(net))
-    return _DenoiserNoise.apply(net, x, sigma, bool(frozen_bn), bool(train_bn), bool(train_realsn), *params)
+    mode = mode or vjp.grad_mode("denoiser_noise", frozen_bn, train_bn, train_realsn)
+    return _DenoiserNoise.apply(net, x, sigma, mode, *mode.parameters(net))
 
 
 class _MSELossStats(torch.autograd.Function):

@@ -138,22 +138,17 @@ class _Denoiser:
                  act_range="data", blk32=True, stack=True, stack_kernel="w16", train_bn="module", train_realsn="module"):
         from .networks import FFDNet
         self.net = net
-        # train_realsn: what runs an f-call of a net with RealSNConv2d layers in TRAIN mode (one power step per layer and call) - "module"
-        # (default): the plugin's own forward (the power step on csrc/realsn.hip, the convolutions on MIOpen); "device": per layer R1 in place
-        # in the module's weight_u / weight buffers, R3 into pack buffers allocated once here, then the fp32 kernels on those packs, for a net
-        # vjp.param_eligibility(net, train_realsn=True) accepts.  A net it cannot serve keeps "module"; train_why says why.
-        if train_realsn not in ("module", "device"):
-            raise ValueError(f"train_realsn={train_realsn!r}: expected 'module' or 'device'")
-        self.train_realsn = train_realsn
-        self.rsn = None
-        # train_bn: what runs an f-call of a net whose BatchNorm2d layers are in TRAIN mode (batch statistics; the reference trains FFDNet so) -
-        # "module" (default): the plugin's own forward (MIOpen); "device": head kernel -> per layer [fp32 Winograd raw convolution -> T1
-        # statistics + buffer update -> T2 normalise + ReLU] -> tail kernel (csrc/bn_train.hip), for a net vjp.param_eligibility(net,
-        # train_bn=True) accepts.  A net it cannot serve keeps "module"; train_why says why.
-        if train_bn not in ("module", "device"):
-            raise ValueError(f"train_bn={train_bn!r}: expected 'module' or 'device'")
-        self.train_bn = train_bn
-        self.train, self.train_why, self._bn_ws = None, None, {}
+        # what runs an f-call of a net in TRAIN mode - "module" (default): the plugin's own forward (MIOpen); "device": the kernels, for a net the
+        # option's mode of vjp.GRAD_MODES serves (_refresh_train).  A net it cannot serve keeps "module"; train_why says why.
+        #   train_bn (batch statistics; the reference trains FFDNet so): head kernel -> per layer [fp32 Winograd raw convolution -> T1 statistics
+        #     + buffer update -> T2 normalise + ReLU] -> tail kernel (csrc/bn_train.hip)
+        #   train_realsn (one power step per RealSNConv2d and call): per layer R1 in place in the module's weight_u / weight buffers, R3 into
+        #     pack buffers allocated once here, then the fp32 kernels on those packs (csrc/realsn.hip)
+        for option, value in (("train_bn", train_bn), ("train_realsn", train_realsn)):
+            if value not in ("module", "device"):
+                raise ValueError(f"{option}={value!r}: expected 'module' or 'device'")
+            setattr(self, option, value)
+        self._bn_ws = {}
         # stack_kernel: which kernel a stack launch of FFDNet's run runs - "w16" (default): the split-fp16 arithmetic under Winograd F(2,3) x
         # direct (csrc/conv_w16.hip: a third fewer matrix-core products, p32 activations between FFDNet's first and last layer); "s16": the
         # split-fp16 direct convolution (csrc/conv_s16.hip).  The measuring f-call keeps the direct kernel; SimpleCNN's two middle layers (a run
@@ -223,11 +218,7 @@ class _Denoiser:
         self.fast = None
         self.wino = None
         self.edges = e = _Edges(2 if isinstance(net, FFDNet) else 1)
-        self.train, self.train_why, self.rsn = None, None, None
-        if self.train_bn == "device" and isinstance(net, torch.nn.Module) and net.training:
-            self._refresh_train_bn(e)
-        if self.train is None and self.train_realsn == "device" and isinstance(net, torch.nn.Module) and net.training:
-            self._refresh_train_realsn(e)
+        self._refresh_train(e)
         seq = None
         if isinstance(net, FFDNet) and not net.training and net.num_input_channels == 1 and self.fold_bn:
             seq = net.intermediate_dncnn.itermediate_dncnn
@@ -262,17 +253,34 @@ class _Denoiser:
                 elif not e.ffdnet and tuple(w0.shape) == (64, 1, 3, 3):
                     e.head_w = e.head_w16 = _hip.pack_c1_to_64_weights(w0)      # (one stencil kernel, three output layouts)
 
-    def _refresh_train_bn(self, e):
-        """train_bn="device": the UNFOLDED layers of a net in train mode - self.train = [(Conv64Weights, BatchNorm2d or None)] for the 64->64
-        layers, the edge kernels' packs in e - or train_why, the reason the net stays on its module."""
+    # option (the name of its mode in vjp.GRAD_MODES, whose stack says which nets it serves) -> (the path of an f-call it serves, what packs the
+    # net's layers, the f-call, what an option that is not served says of a net in eval mode), in the order the options are tried
+    TRAIN_OPTIONS = {"train_bn": ("train bn per layer", "_pack_train_bn", "_train_bn_call", "its BatchNorm is folded into the convolutions"),
+                     "train_realsn": ("train realsn per layer", "_pack_train_realsn", "_train_realsn_call", "a RealSNConv2d uses its stored weight")}
+
+    def _refresh_train(self, e):
+        """train_mode = the first option asked for ("device") whose mode serves the net as it stands, with the net's layers packed for it
+        (self.train or self.rsn, the edge kernels' packs in e) - or None and train_why, the first reason a net in train mode stays on its module."""
         from . import vjp
-        ok, why = vjp.param_eligibility(self.net, train_bn=True)
-        if ok and not all(t.is_cuda and t.dtype == torch.float32 for t in list(self.net.parameters()) + list(self.net.buffers()) if t.is_floating_point()):
-            ok, why = False, "the net's parameters and buffers are not fp32 tensors on the GPU"
-        if not ok:
-            self.train_why = why
+        net = self.net
+        self.train, self.rsn, self.train_why, self.train_mode = None, None, None, None
+        if not (isinstance(net, torch.nn.Module) and net.training):
             return
-        stack = vjp.bn_stack(self.net, True)[0]
+        for option, (_, pack, _, _) in self.TRAIN_OPTIONS.items():
+            if getattr(self, option) != "device":
+                continue
+            stack, _, why = vjp.GRAD_MODE[option].stack(net)
+            if stack is not None and not all(t.is_cuda and t.dtype == torch.float32 for t in list(net.parameters()) + list(net.buffers()) if t.is_floating_point()):
+                stack, why = None, "the net's parameters and buffers are not fp32 tensors on the GPU"
+            if stack is not None:
+                getattr(self, pack)(e, stack)
+                self.train_mode = option
+                return
+            self.train_why = self.train_why or why
+
+    def _pack_train_bn(self, e, stack):
+        """train_bn="device": the UNFOLDED layers of a net in train mode - self.train = [(Conv64Weights, BatchNorm2d or None)] for the 64->64
+        layers, the edge kernels' packs in e."""
         w0, wl = stack[0][0].weight.detach(), stack[-1][0].weight.detach()
         if e.ffdnet:
             e.head_w, e.tail_w = _hip.pack_head_weights(w0), _hip.pack_tail_weights(wl)
@@ -299,20 +307,13 @@ class _Denoiser:
             h = _hip.bn_train_apply(c, rec, bn.weight.detach(), bn.bias.detach(), bn.eps, relu=True, out=c)
         return e.tail(h)
 
-    def _refresh_train_realsn(self, e):
+    def _pack_train_realsn(self, e, stack):
         """train_realsn="device": self.rsn = (per layer (conv, is RealSN, pack, pack44, v, record), R1's workspace, the 64->64 layers'
         Conv64Weights over those packs) with every buffer allocated HERE, once - an f-call allocates none of them and their addresses do
-        not move - or train_why, the reason the net stays on its module.  A plain Conv2d's packs are made now (its weight does not move
-        between f-calls); a RealSNConv2d's at every call, behind its power step."""
+        not move.  A plain Conv2d's packs are made now (its weight does not move between f-calls); a RealSNConv2d's at every call, behind
+        its power step."""
         from . import vjp
         from .networks.simplecnn import RealSNConv2d
-        ok, why = vjp.param_eligibility(self.net, train_realsn=True)
-        if ok and not all(t.is_cuda and t.dtype == torch.float32 for t in list(self.net.parameters()) + list(self.net.buffers()) if t.is_floating_point()):
-            ok, why = False, "the net's parameters and buffers are not fp32 tensors on the GPU"
-        if not ok:
-            self.train_why = self.train_why or why
-            return
-        stack = vjp.realsn_stack(self.net)[0]
         dev = stack[0][0].weight.device
         layers = []
         for conv, _, _ in stack:
@@ -328,7 +329,7 @@ class _Denoiser:
         e.head_w, e.tail_w, e.relu = layers[0][2], layers[-1][2], True
         self.rsn = (layers, vjp._realsn_workspace(stack, dev), mids)
 
-    def _train_realsn_call(self, x):
+    def _train_realsn_call(self, x, sg=None):
         """One f-call with every RealSNConv2d renormalised first: R1 moves the module's weight_u and weight in place (the module's own
         kernels: its bits), R3 turns the weight into the packs, and the first-layer stencil, the fp32 64->64 kernels and the last-layer
         kernel run on them.  No host synchronisation, no host -> device copy."""
@@ -370,10 +371,9 @@ class _Denoiser:
     # 1->64 layer -> the run as ONE stack launch -> 64->1 layer (_sliced).  Set on the instance by a prepare() that is told the f-call's
     # batch (n_img=: the engine's own); a bare prepare(n_calls, device) + run() keeps the launch per layer of the kernels' own tests and tools.
     plain_sliced = False
-    # train_bn="device": the unfolded layers of a net whose train-mode BatchNorms run on csrc/bn_train.hip (_refresh_train_bn), else None
-    # and, where the option was asked for and the net is in train mode, the reason
-    train, train_why = None, None
-    rsn = None                                                      # train_realsn="device": _refresh_train_realsn's layers, else None
+    # _refresh_train's: the option that serves the net's train-mode f-calls on the device, or None and, where one was asked for and the net is in
+    # train mode, the reason; train: _pack_train_bn's layers (train_bn="device"), rsn: _pack_train_realsn's (train_realsn="device"), else None
+    train_mode = train_why = train = rsn = None
 
     def _stack_for(self, idx, device, w16=False):
         """The Split16Stack (w16: Wino16Stack) of the run of layers idx (an H2D copy of its table: built by prepare(), never inside a
@@ -399,10 +399,8 @@ class _Denoiser:
     def _route(self, n, H, W, device, policy, cal):
         """The path (_run_gen) of an f-call on n images of H x W under the conv64 `policy`, calibrating (cal) or not, from the attributes as
         they are NOW: tests and tools set them between calls, and the engine turns `stack` off and `per_layer_w16` on behind a time-out."""
-        if self.train is not None and self.tag in ("ffdnet", "denoiser") and torch.device(device).type == "cuda":
-            return "train bn per layer"
-        if self.rsn is not None and self.tag == "denoiser" and torch.device(device).type == "cuda":
-            return "train realsn per layer"
+        if self.train_mode is not None and self.tag in ("ffdnet", "denoiser") and torch.device(device).type == "cuda":
+            return self.TRAIN_OPTIONS[self.train_mode][0]
         if self.fast is None or self.tag not in ("ffdnet", "denoiser"):
             return "module"
         e, cuda = self.edges, torch.device(device).type == "cuda"
@@ -553,12 +551,9 @@ class _Denoiser:
         path = self._route(bsz * B, H, W, x.device, self._policy, cal)
         if self.tag in ("ffdnet", "denoiser"):
             sg = self.sigma_table[call:call + 1] if self.tag == "ffdnet" else None      # (a plain network takes no sigma)
-            if path == "train bn per layer":
+            if self.train_mode is not None and path == self.TRAIN_OPTIONS[self.train_mode][0]:
                 self.last_path = path
-                out = self._train_bn_call(x, sg)
-            elif path == "train realsn per layer":
-                self.last_path = path
-                out = self._train_realsn_call(x)
+                out = getattr(self, self.TRAIN_OPTIONS[self.train_mode][2])(x, sg)
             elif path == "module":
                 out = self.net(x) if sg is None else self.net(x, sg.expand(bsz * B))
             elif path == "layers":
@@ -873,18 +868,12 @@ class DEQSCIEngine:
             self.last_info["stack_timeouts"] = timed_out     # 1: a stack launch of THIS call timed out (the result below is the per-layer redo)
             # what the run of 64->64 layers of the LAST f-call went out as (the kernel actually used, for every call)
             self.last_info["denoiser_path"] = (self._kids[0].den.last_path if (self._grouped and self._kids) else self.den.last_path)
-            if self.train_bn == "device":
-                # what the option did for this call: "device" where the f-calls ran csrc/bn_train.hip, else "module" and why
-                served = self._train_bn_device()
-                self.last_info["train_bn"] = "device" if served else "module"
-                self.last_info["train_bn_reason"] = None if served else (
-                    self.den.train_why or "the denoiser is not in train mode (net.eval(): its BatchNorm is folded into the convolutions)")
-            if self.train_realsn == "device":
-                # what the option did for this call: "device" where the f-calls ran R1 / R3 and the fp32 kernels, else "module" and why
-                served = self._train_realsn_device()
-                self.last_info["train_realsn"] = "device" if served else "module"
-                self.last_info["train_realsn_reason"] = None if served else (
-                    self.den.train_why or "the denoiser is not in train mode (net.eval(): a RealSNConv2d uses its stored weight)")
+            for option, (_, _, _, in_eval) in _Denoiser.TRAIN_OPTIONS.items():
+                if getattr(self, option) == "device":
+                    # what the option did for this call: "device" where the f-calls ran its kernels, else "module" and why
+                    served = self.train_mode_on_device() == option
+                    self.last_info[option] = "device" if served else "module"
+                    self.last_info[option + "_reason"] = None if served else (self.den.train_why or f"the denoiser is not in train mode (net.eval(): {in_eval})")
             fallback = None
             if self.conv64 == "auto" and not math.isfinite(self.last_info["res"]) and bool(torch.isfinite(y).all()):
                 # conv64="auto" promises the reference's fp32 range: a non-finite residual under the split-fp16 layers (already warned
@@ -942,22 +931,19 @@ class DEQSCIEngine:
             initial_point = _hip.f32c(initial_point)
         graph = self.use_graph if self.use_graph != "auto" else bsz * H * W <= self.GRAPH_AUTO_PIXELS
         self.den._refresh()
-        if self._train_bn_device():
-            # every f-call moves the BatchNorms' running buffers, and the batch statistics are those of the WHOLE f-call's batch
-            if self.use_graph is True:
-                raise ValueError("use_graph=True: train_bn='device' runs the denoiser's train-mode BatchNorm2d layers on the device, and every "
-                                 "f-call moves their running_mean / running_var / num_batches_tracked; such a net runs eagerly "
-                                 "(use_graph='auto' or False, or net.eval())")
-            graph = False
-        if self._train_mode_realsn():
-            # every f-call advances weight_u and rewrites weight: module state a replayed graph would not carry from call to call
-            if self.use_graph is True:
-                raise ValueError("use_graph=True: the denoiser has a train-mode RealSNConv2d, whose every call runs a power-iteration step on "
-                                 "its weight_u and weight buffers; such a net runs eagerly (use_graph='auto' or False, or net.eval())")
-            graph = False
+        # an f-call that moves module state - the BatchNorms' running buffers (and the batch statistics are those of the WHOLE f-call's batch),
+        # a RealSNConv2d's weight_u and weight - is not replayed from a graph, which would not carry that state from call to call
+        for moves, what in ((self.train_mode_on_device() == "train_bn", "train_bn='device' runs the denoiser's train-mode BatchNorm2d layers on the device, "
+                             "and every f-call moves their running_mean / running_var / num_batches_tracked; such a net runs eagerly "
+                             "(use_graph='auto' or False, or net.eval())"),
+                            (self._train_mode_realsn(), "the denoiser has a train-mode RealSNConv2d, whose every call runs a power-iteration step on "
+                             "its weight_u and weight buffers; such a net runs eagerly (use_graph='auto' or False, or net.eval())")):
+            if moves and self.use_graph is True:
+                raise ValueError("use_graph=True: " + what)
+            graph = graph and not moves
         self._grouped = False
         extras = self._snaps is not None or self._trace
-        plan = None if (graph or extras or self._solve_only or self._train_bn_device() or self._train_realsn_device()) else self._group_plan(bsz, H, W, B, y.device)
+        plan = None if (graph or extras or self._solve_only or self.train_mode_on_device()) else self._group_plan(bsz, H, W, B, y.device)
         if plan is not None:
             rec = self._reconstruct_grouped(plan, y, Phi4, Phi_sum, initial_point)
             if rec is not None:
@@ -979,13 +965,10 @@ class DEQSCIEngine:
         self._warn_if_not_finite()
         return rec
 
-    def _train_bn_device(self):
-        """True where the f-calls run train-mode BatchNorms on the device (train_bn="device" and a net it serves): each moves the running buffers."""
-        return self.den.train is not None
-
-    def _train_realsn_device(self):
-        """True where the f-calls renormalise train-mode RealSNConv2d layers on the device path (train_realsn="device" and a net it serves)."""
-        return self.den.rsn is not None
+    def train_mode_on_device(self):
+        """The option ("train_bn", "train_realsn") under which the f-calls run a net in train mode on the device - each moves the module's
+        buffers, the BatchNorms' running statistics or the RealSNConv2ds' weight_u and weight - or None."""
+        return self.den.train_mode
 
     @torch.no_grad()
     def solve(self, y, Phi, Phi_sum=None, initial_point=None):
@@ -1188,7 +1171,7 @@ class DEQSCIEngine:
         rec = _hip.residual_out(ws.z1, out, LAYOUT_HWB) if is_noise else _hip.transpose(out, LAYOUT_HWB)
         call += 1
         # dead f0 = f(z) of :271-272 - not dead for a train-mode RealSNConv2d: the call advances weight_u, as it does in the reference
-        if self.extra_call or self._train_mode_realsn() or self._train_bn_device():
+        if self.extra_call or self._train_mode_realsn() or self.train_mode_on_device():
             yield "fcall"
             zt = _hip.transpose(rec, LAYOUT_BHW)
             _hip.gap_update(zt, phi, y, ps, LAYOUT_BHW, out=ws.z1)

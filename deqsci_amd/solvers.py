@@ -91,62 +91,63 @@ class EquilibriumProxGradSCI(nn.Module):
             raise UnboundLocalError("local variable 'z_tplus1' referenced before assignment")
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
-    def _param_mode(self, frozen_bn, train_bn, train_realsn=False):
-        """(mode, reason): which DenoiserParamGrads serves the denoiser - "plain", "frozen_bn", "train_bn", "train_realsn" - or (None, why not)."""
+    def _param_mode(self, modes):
+        """(mode, reason): the first of the vjp.GradModes `modes` (vjp.switch_modes: what a parameter_backward string serves, in order) whose
+        DenoiserParamGrads serves the denoiser - or (None, why not): a refusal may name the mode the net belongs to instead
+        (vjp._Refusal.other), and the reason is found by following those names from the first mode, until one names no mode tried or one passed already."""
         op = self.nonlinear_op
         if not (self.A is A_torch_ and self.At is At_torch_):
             return None, "custom A / At: the device call uses the HIP GAP projection"
-        ok, why = _vjp.param_eligibility(op)
-        if ok:
-            return "plain", why
-        if train_realsn:
-            # everything "device" serves, plus a train-mode net vjp.realsn_stack accepts; its verdict where the net has a train-mode RealSNConv2d
-            ok, why_rsn = _vjp.param_eligibility(op, train_realsn=True)
+        whys = {}
+        for mode in modes:
+            ok, why = mode.eligibility(op)
             if ok:
-                return "train_realsn", why_rsn
-            return None, why_rsn if "RealSNConv2d" in why else why
-        if not (frozen_bn or train_bn):
-            return None, why
-        ffdnet_tag = isinstance(op, _vjp._modules()[1]) and getattr(op, "tag", None) != "ffdnet"
-        wrong_tag = f"FFDNet under nonlinear_op tag {getattr(op, 'tag', None)!r}: it gets its noise level under 'ffdnet' only"
-        ok, why = _vjp.param_eligibility(op, frozen_bn=True)
-        if ok:
-            return (None, wrong_tag) if ffdnet_tag else ("frozen_bn", why)
-        if not train_bn:
-            return None, why
-        ok, why_train = _vjp.param_eligibility(op, train_bn=True)
-        if ok:
-            return (None, wrong_tag) if ffdnet_tag else ("train_bn", why_train)
-        return None, why if "BatchNorm2d in eval mode" in why_train else why_train
+                if isinstance(op, _vjp._modules()[1]) and getattr(op, "tag", None) != "ffdnet":
+                    return None, f"FFDNet under nonlinear_op tag {getattr(op, 'tag', None)!r}: it gets its noise level under 'ffdnet' only"
+                return mode, why
+            whys[mode.name] = why
+        name, passed = modes[0].name, []
+        while name not in passed:
+            passed.append(name)
+            other = getattr(whys[name], "other", None)
+            if other not in whys:
+                break
+            name = other
+        return None, whys[name]
+
+    @staticmethod
+    def _keyword_modes(who, frozen_bn, train_bn, train_realsn):
+        """The modes the keywords ask to try: those of the switch of the one they name - train_realsn before train_bn before frozen_bn."""
+        return _vjp.switch_modes(_vjp.grad_mode(who, frozen_bn and not (train_bn or train_realsn), train_bn and not train_realsn, train_realsn).switch)
 
     def device_param_eligibility(self, frozen_bn=False, train_bn=False, train_realsn=False):
-        """(ok, reason): whether forward_param_device can serve this map (HIP GAP operators, tag 'denoiser', vjp.param_eligibility;
-        frozen_bn=True: also a frozen-BatchNorm stack and tag 'ffdnet', vjp.param_eligibility(net, frozen_bn=True); train_bn=True: all of
-        that and the same nets with their BatchNorms in train mode, vjp.param_eligibility(net, train_bn=True))."""
-        mode, why = self._param_mode(frozen_bn, train_bn, train_realsn)
+        """(ok, reason): whether forward_param_device can serve this map under the same keywords: HIP GAP operators, and a denoiser one of the
+        modes the keyword's switch serves accepts (vjp.GRAD_MODES; FFDNet under tag 'ffdnet' only)."""
+        mode, why = self._param_mode(self._keyword_modes("device_param_eligibility", frozen_bn, train_bn, train_realsn))
         return mode is not None, why
 
     def forward_param_device(self, z, y, Phi, Phi_sum, frozen_bn=False, train_bn=False, train_realsn=False):
         """The taped call f(z) = z1 - D(z1) whose backward forms the denoiser's weight gradients on the HIP kernels: gap_update ->
-        autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called.  frozen_bn=True serves
-        what device_param_eligibility(frozen_bn=True) accepts; FFDNet with _forward_taped's sigma bookkeeping.  train_bn=True serves what
-        device_param_eligibility(train_bn=True) accepts: a train-mode BatchNorm normalises by the batch on csrc/bn_train.hip, and the call
-        moves its running buffers once, as the module's own forward would.  train_realsn=True serves what
-        device_param_eligibility(train_realsn=True) accepts: every RealSNConv2d takes its power step in the module's buffers, once
-        (csrc/realsn.hip), and the gradients go to weight_orig."""
-        mode, why = self._param_mode(frozen_bn, train_bn, train_realsn)
+        autograd.denoiser_noise (vjp.DenoiserParamGrads) -> z1 - noise.  The torch module itself is not called.  Serves what
+        device_param_eligibility accepts under the same keywords, in the first mode that does; FFDNet with _forward_taped's sigma
+        bookkeeping.  A train mode moves the module's buffers once, as its own forward would."""
+        mode, why = self._param_mode(self._keyword_modes("forward_param_device", frozen_bn, train_bn, train_realsn))
         if mode is None:
             raise ValueError(f"forward_param_device: {why}")
+        return self._forward_param(mode, z, y, Phi, Phi_sum)
+
+    def _forward_param(self, mode, z, y, Phi, Phi_sum):
+        """forward_param_device on the vjp.GradMode _param_mode answered."""
         bsz, w, h, c = z.shape
         op = self.nonlinear_op
         z1 = _ag.gap_update(z, y, Phi, Phi_sum)
         zp = z1.permute(0, 3, 1, 2).contiguous()
         self._taped = (zp.detach().view(bsz * c, 1, w, h), None)
         sigma = None
-        if mode != "plain" and isinstance(op, _vjp._modules()[1]):
+        if isinstance(op, _vjp._modules()[1]):
             sigma = self._sigma(y, bsz * c)
             self._taped = (self._taped[0], sigma)
-        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, mode == "frozen_bn", mode == "train_bn", mode == "train_realsn")
+        noise = _ag.denoiser_noise(op, zp.view(bsz * c, 1, w, h), sigma, mode=mode)
         return z1 - noise.view(bsz, c, w, h).permute(0, 2, 3, 1)
 
     def device_vjp_eligibility(self, train_realsn=False):
@@ -341,10 +342,8 @@ class DEQFixedPoint(nn.Module):
         self.last_backward_path = None
         self.backward_fallback_reason = None
         # how the taped call z = f(z*) forms the denoiser's weight gradients: "autograd" (the torch module on the tape: MIOpen backward) or
-        # "device" (EquilibriumProxGradSCI.forward_param_device: csrc/wgrad.hip, falling back to autograd where vjp.param_eligibility
-        # refuses), or "device+bn" (everything "device" serves plus a frozen BatchNorm - conv + BN-eval + ReLU DnCNN, FFDNet: csrc/wgrad_bn.hip,
-        # vjp.param_eligibility(net, frozen_bn=True)), or "device+bn-train" (everything "device+bn" serves plus the same nets with their
-        # BatchNorms in TRAIN mode, as the reference trains them: csrc/bn_train.hip, vjp.param_eligibility(net, train_bn=True)).
+        # the switch of a mode of vjp.GRAD_MODES - "device", "device+realsn", "device+bn", "device+bn-train" (EquilibriumProxGradSCI.forward_param_device
+        # in the first mode the switch serves that accepts the denoiser, falling back to autograd where all of them refuse).
         # last_parameter_path: the path of the last taped forward ("device" when served); parameter_fallback_reason: why not.
         # Independent of implicit_backward.
         self.parameter_backward = "autograd"
@@ -373,17 +372,17 @@ class DEQFixedPoint(nn.Module):
             self._engine = (key, DEQSCIEngine(f.nonlinear_op, **{**cfg, **self.engine_options}))
         return self._engine[1]
 
-    def _train_bn_engine(self):
-        """The engine that runs a training step's no-tape solve: engine_options["train_bn"] or ["train_realsn"] == "device", f on the engine's path (not a
-        DataParallel) and a denoiser in train mode that the option serves - else None, and the solve takes the solver as it always did."""
-        if ((self.engine_options.get("train_bn") != "device" and self.engine_options.get("train_realsn") != "device")
-                or isinstance(self.f, nn.DataParallel)):
+    def _train_solve_engine(self):
+        """The engine that runs a training step's no-tape solve: a vjp.GradMode.engine_option is set, f is on the engine's path (not a
+        DataParallel) and the denoiser is in train mode and served by that option - else None, and the solve takes the solver as it always did."""
+        asked = any(self.engine_options.get(m.engine_option[0]) == m.engine_option[1] for m in _vjp.GRAD_MODES if m.engine_option)
+        if not asked or isinstance(self.f, nn.DataParallel):
             return None
         eng = self._engine_for()
         if eng is None:
             return None
         eng.den._refresh()
-        return eng if (eng.den.train is not None or eng.den.rsn is not None) else None
+        return eng if eng.train_mode_on_device() else None
 
     def _device_map(self, Phi, Phi_sum):
         """implicit_backward = "device": the device map of the taped call just made, or None (autograd) with the reason recorded."""
@@ -409,25 +408,23 @@ class DEQFixedPoint(nn.Module):
 
     def _taped_call(self, z, x, Phi, Phi_sum):
         """The taped call z = f(z*) (:268): on the device's weight-gradient path where parameter_backward asks for it and it is served."""
-        if self.parameter_backward not in ("autograd", "device", "device+bn", "device+bn-train", "device+realsn"):
+        modes = None if self.parameter_backward == "autograd" else _vjp.switch_modes(self.parameter_backward)
+        if modes is None and self.parameter_backward != "autograd":
             raise ValueError(f"parameter_backward={self.parameter_backward!r}: expected 'autograd', 'device' or 'device+bn' - or 'device+bn-train', "
                              "which adds BatchNorm2d in train mode, or 'device+realsn', which adds RealSNConv2d in train mode")
         self.parameter_fallback_reason = None
         self.last_parameter_path = "autograd"
-        if self.parameter_backward != "autograd":
-            train_bn = self.parameter_backward == "device+bn-train"
-            frozen_bn = train_bn or self.parameter_backward == "device+bn"
-            realsn = self.parameter_backward == "device+realsn"
+        if modes is not None:
             f = self.f.module if isinstance(self.f, nn.DataParallel) else self.f
             if isinstance(self.f, nn.DataParallel) and len(self.f.device_ids or []) > 1:
                 self.parameter_fallback_reason = "DataParallel over several devices (the taped call runs on replicas)"
             elif not isinstance(f, EquilibriumProxGradSCI):
                 self.parameter_fallback_reason = f"f is a {type(f).__name__}, not this package's EquilibriumProxGradSCI"
             else:
-                ok, why = f.device_param_eligibility(frozen_bn, train_bn, realsn)
-                if ok:
+                mode, why = f._param_mode(modes)
+                if mode is not None:
                     self.last_parameter_path = "device"
-                    return f.forward_param_device(z, x, Phi, Phi_sum, frozen_bn, train_bn, realsn)
+                    return f._forward_param(mode, z, x, Phi, Phi_sum)
                 self.parameter_fallback_reason = why
         return self.f(z, x, Phi, Phi_sum)
 
@@ -474,10 +471,10 @@ class DEQFixedPoint(nn.Module):
             if extras:
                 raise NotImplementedError("snapshots / trace exist on the engine's inference path only: this is the taped training forward "
                                           "(pass train_flag=False or run under torch.no_grad())")
-            eng = self._train_bn_engine()
+            eng = self._train_solve_engine()
             if eng is not None:
-                # engine_options["train_bn"] = "device": the no-tape solve's f-calls on the engine's "train bn per layer" path
-                # (csrc/bn_train.hip; each moves the BatchNorms' buffers as the module's forward would), sigma from the engine's table
+                # the no-tape solve's f-calls on the engine's "train ... per layer" path (each moves the module's buffers as its own
+                # forward would), sigma from the engine's table
                 z = eng.solve(*_data(x, Phi, Phi_sum), initial_point=init_point.detach())
                 self.forward_res = eng.last_info["res"]
                 if eng.den.tag == "ffdnet":

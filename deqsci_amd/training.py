@@ -80,9 +80,6 @@ class SCITrainingDatasetSubset(torch.utils.data.Dataset):
 
 
 # ----------------------------------------------------------------------------- the backend switches
-# (parameter_backward, vjp.param_eligibility's keywords, the engine option that runs the solve's train-mode f-calls on the device)
-_PARAM_MODES = (("device", {}, {}), ("device+realsn", {"train_realsn": True}, {"train_realsn": "device"}),
-                ("device+bn", {"frozen_bn": True}, {}), ("device+bn-train", {"train_bn": True}, {"train_bn": "device"}))
 _CUSTOM_OPS = "custom A / At: the device paths use the HIP GAP projection"
 
 
@@ -90,13 +87,13 @@ def configure_training(deq, backend="device"):
     """Set deq.engine_options (its train_bn / train_realsn entries), deq.implicit_backward and deq.parameter_backward for a training run
     -> TrainingConfig(backend, engine_options, implicit_backward, parameter_backward, reasons).  backend="autograd": the defaults
     ("autograd" for both, the solve's f-calls on the torch module).  backend="device": per switch the first device mode that serves the
-    denoiser as it stands (its train / eval mode included) - the weight gradients by vjp.param_eligibility in the order "device",
-    "device+realsn", "device+bn", "device+bn-train", the implicit backward by vjp.eligibility in the order "device", "device+realsn" -
+    denoiser as it stands (its train / eval mode included) - the weight gradients by the modes of vjp.GRAD_MODES in its order ("device",
+    "device+realsn", "device+bn", "device+bn-train"), the implicit backward by vjp.eligibility in the order "device", "device+realsn" -
     with the engine's train-mode f-calls where the mode has them; a switch nothing serves stays "autograd" and reasons[switch] says why
     (reasons is empty when both run on the device)."""
     if backend not in ("device", "autograd"):
         raise ValueError(f"backend={backend!r}: expected 'device' or 'autograd'")
-    options = {k: v for k, v in dict(deq.engine_options).items() if k not in ("train_bn", "train_realsn")}
+    options = {k: v for k, v in dict(deq.engine_options).items() if k not in {m.engine_option[0] for m in _vjp.GRAD_MODES if m.engine_option}}
     implicit = parameter = "autograd"
     reasons = {}
     if backend == "device":
@@ -105,13 +102,13 @@ def configure_training(deq, backend="device"):
         custom = not (getattr(f, "A", None) is operators.A_torch_ and getattr(f, "At", None) is operators.At_torch_)
         tag = "ffdnet" if isinstance(net, _vjp._modules()[1]) else "denoiser"
         why = _CUSTOM_OPS if custom else None
-        for mode, flags, opts in (() if custom else _PARAM_MODES):
-            ok, why = _vjp.param_eligibility(net, **flags)
+        for mode in (() if custom else _vjp.GRAD_MODES):
+            ok, why = mode.eligibility(net)
             if ok and getattr(net, "tag", None) != tag:
                 ok, why = False, f"{type(net).__name__} under nonlinear_op tag {getattr(net, 'tag', None)!r}: the device call serves it under {tag!r} only"
             if ok:
-                parameter = mode
-                options.update(opts)
+                parameter = mode.switch
+                options.update([mode.engine_option] if mode.engine_option else [])
                 break
         if parameter == "autograd":
             reasons["parameter_backward"] = why

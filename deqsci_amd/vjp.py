@@ -22,14 +22,23 @@ The same masked kernels compute J_D(x) v (forward mode) when they are handed the
 the map the iteration applies, sigma a constant of the linearisation - on csrc/jacobian.hip's masked first layer and the existing last
 layer's kernel.  DenoiserVJP and eligibility are the training hook's and do not change.
 
-The weight gradients (dD/dtheta)^T v come from ONE walk in every BatchNorm mode, stated once on the host (_taped_forward, _walk_back) and
-once on the device (_MaskedStack's forward, DenoiserParamGrads._walk): a forward that keeps each layer's input, then the transposed masked
-layers carry v down and every layer forms its gradients from its input and the masked gradient gm behind it.  What a layer is - how it
-runs forward, what it forms, what it hands down and through which transposed weight - is its RULE, and there are three (_PlainRule,
-_FrozenRule, _TrainRule on the host; _Conv64, _Frozen64, _Train64 on the device); the edge layers, plain or FFDNet's, come from
-PLAIN_EDGES / FFDNET_EDGES.  bn_stack says which nets qualify and _structure_refusal what shape they must have; param_eligibility,
-grad_parameters, the host statements (plan_param_grads, plan_param_grads_frozen_bn, plan_forward_train_bn, plan_param_grads_train_bn) and
-DenoiserParamGrads are thin callers.
+The weight gradients (dD/dtheta)^T v come from ONE walk in every mode, stated once on the host (_taped_forward, _walk_back) and once on
+the device (_MaskedStack's forward, DenoiserParamGrads._walk): a forward that keeps each layer's input, then the transposed masked layers
+carry v down and every layer forms its gradients from its input and the masked gradient gm behind it.  What a layer is - how it runs
+forward, what it forms, what it hands down and through which transposed weight - is its RULE; the edge layers, plain or FFDNet's, come
+from PLAIN_EDGES / FFDNET_EDGES.
+
+There are four MODES, and GRAD_MODES states each of them once, as a GradMode:
+    name           parameter_backward     serves (in order)               engine option            nets (its stack)       host rule      device rule
+    plain          "device"               plain                           -                        bn_stack(net, None)    _PlainRule     _Conv64
+    train_realsn   "device+realsn"        plain, train_realsn             train_realsn="device"    realsn_stack(net)      _RealSNRule    _RealSN64
+    frozen_bn      "device+bn"            plain, frozen_bn                -                        bn_stack(net, False)   _FrozenRule    _Frozen64
+    train_bn       "device+bn-train"      plain, frozen_bn, train_bn      train_bn="device"        bn_stack(net, True)    _TrainRule     _Train64
+(a layer without a BatchNorm is _PlainRule / _Conv64 in every mode).  The name is the public keyword that asks for the mode: grad_mode
+resolves frozen_bn= / train_bn= / train_realsn= to one, once, at the first line of every public entry point, and switch_modes a
+parameter_backward string to the modes it serves.  Everything else - the solver's _param_mode, DEQFixedPoint._taped_call,
+training.configure_training, engine._Denoiser's train-mode f-calls, the host statements plan_* and DenoiserParamGrads - reads the record: a
+new mode is a new row.  _structure_refusal says what shape a mode's nets must have.  What the four compute:
 
 No BatchNorm - a bias-free conv + ReLU stack, DEQFixedPoint.parameter_backward = "device", param_eligibility(net): dW = wgrad(x, gm), the
 correlation of the layer's input with the masked gradient behind it (csrc/wgrad.hip: W0 for a 64 -> 64 layer, W1 for the two edge
@@ -61,6 +70,9 @@ kernels read are therefore made on the device, by R3 of the same file, from the 
 normalised weights, and R2 turns each layer's gradient G into weight_orig's, (sigma / cur_sigma) (G - (sum(G W) / cur_sigma) C).  The
 implicit backward reads J_D at the weights the last call f0 = f(z0) left in the modules, as the reference's hook does.
 """
+import functools
+import typing
+
 import torch
 import torch.nn.functional as F
 
@@ -123,8 +135,7 @@ def eligibility(net, train_realsn=False):
         ok, why = eligibility(net)
         if ok or not (isinstance(net, torch.nn.Module) and any(isinstance(m, RealSNConv2d) and m.training for m in net.modules())):
             return ok, why
-        stack, why = realsn_stack(net)
-        return (True, _REALSN_OK) if stack is not None else (False, why)
+        return GRAD_MODE["train_realsn"].eligibility(net)
     if isinstance(net, FFDNet):
         if net.num_input_channels != 1:
             return False, _FFDNET_COLOUR
@@ -203,10 +214,11 @@ def plan_jvp(layers, x, v, masks=None):
     return masked_jvp(layers, masks, v), masks
 
 
-# ----------------------------------------------------------------------------- the weight gradients: one walk, three layer rules
+# ----------------------------------------------------------------------------- the weight gradients: one walk, a layer rule per mode
 # A layer rule is what one convolution of the stack is on the host, in its weight W's dtype: .forward(h) -> (y in front of the ReLU, what
 # the way back needs of it), .backward(input, kept, gm) -> ([the gradients of the layer's parameters], the gradient behind the convolution)
 # for gm the gradient masked by the layer's ReLU, and .down, the weight whose transpose carries that gradient to the layer below.
+# A mode's rule (GradMode.host_rule) is made from the layer, Rule(conv, bn, like, update, who); a Conv2d without a BatchNorm is a _PlainRule.
 class _PlainRule:
     """y = conv(x, W) [+ bias]:  dW = wgrad(x, gm), gm goes down through W^T."""
 
@@ -224,8 +236,9 @@ class _FrozenRule:
     """y = s conv(x, W) + t of an eval-mode BatchNorm:  R = wgrad(x, gm), dW = s R, dgamma = (sum W R - mean dbeta) / sqrt(var + eps),
     dbeta = sum gm; gm goes down through (s W)^T."""
 
-    def __init__(self, W, bn):
-        self.W, (self.s, self.mean, self.inv) = W, _bn_scale(bn, W)
+    def __init__(self, conv, bn, like, update=False, who=None):
+        self.W = W = conv.weight.detach().to(like)
+        self.s, self.mean, self.inv = _bn_scale(bn, W)
         self.shift, self.down = bn.bias.detach().to(W) - self.mean * self.s, W * self.s.view(-1, 1, 1, 1)
 
     def forward(self, h):
@@ -242,8 +255,9 @@ class _TrainRule:
     dbeta = sum gm, dgamma = sum gm xhat, dc = gamma / sqrt(var + eps) (gm - dbeta / P - xhat dgamma / P), dW = wgrad(x, dc); dc goes down
     through W^T.  update: the forward moves the module's running buffers as torch does."""
 
-    def __init__(self, W, bn, update, who):
-        self.W, self.down, self.bn, self.update, self.who = W, W, bn, update, who
+    def __init__(self, conv, bn, like, update, who):
+        self.W = self.down = W = conv.weight.detach().to(like)
+        self.bn, self.update, self.who = bn, update, who
         self.gamma, self.beta = bn.weight.detach().to(W), bn.bias.detach().to(W)
 
     def forward(self, h):
@@ -267,6 +281,26 @@ class _TrainRule:
         dbeta, dgamma = gm.sum((0, 2, 3)), (gm * xhat).sum((0, 2, 3))
         dc = (self.gamma * inv).view(1, -1, 1, 1) * (gm - (dbeta / P).view(1, -1, 1, 1) - xhat * (dgamma / P).view(1, -1, 1, 1))
         return [torch.nn.grad.conv2d_weight(inp, self.W.shape, dc, padding=1), dgamma, dbeta], dc
+
+
+class _RealSNRule(_PlainRule):
+    """A RealSNConv2d in train mode: one realsn.power_iteration from the module's weight_u (weight = weight_orig / cur_sigma * sigma; u, v constants)
+    in front of _PlainRule on that weight, realsn.weight_grad turning its G into weight_orig's behind it.  update: the module gets the new weight_u and weight."""
+
+    def __init__(self, conv, bn, like, update, who=None):
+        from . import realsn
+        W = conv.weight_orig.detach()
+        weight, u, v, cur_sigma = realsn.power_iteration(W, conv.weight_u, conv.sigma, conv.n_power_iterations, conv.eps)
+        if update:
+            with torch.no_grad():
+                conv.weight_u.copy_(u)
+                conv.weight.copy_(weight)
+        super().__init__(weight.to(like))
+        self.grad_of, self.step = realsn.weight_grad, (W, u, v, cur_sigma, conv.sigma)
+
+    def backward(self, inp, kept, gm):
+        (G,), g = super().backward(inp, kept, gm)
+        return [self.grad_of(G.to(self.step[0]), *self.step).to(G)], g
 
 
 def _first_input(who, edges, x, sigma):
@@ -317,7 +351,13 @@ def plan_param_grads(layers, x, v, masks=None):
     return _walk_back(rules, tape, used, v, PLAIN_EDGES)[0], used
 
 
-_FROZEN_BN_OK, _FROZEN_FFDNET_OK = "bias-free conv [+ frozen BN] + ReLU stack", "FFDNet with its BatchNorm frozen"
+class _Refusal(str):
+    """Why a mode refuses a net, with .other the name of the mode the net belongs to instead, or None (EquilibriumProxGradSCI._param_mode)."""
+
+    def __new__(cls, text, other=None):
+        self = super().__new__(cls, text)
+        self.other = other
+        return self
 
 
 def _bn_refusal(mods):
@@ -325,9 +365,10 @@ def _bn_refusal(mods):
     for m in mods:
         if isinstance(m, torch.nn.BatchNorm2d):
             if not m.track_running_stats or m.running_mean is None or m.running_var is None:
-                return "BatchNorm2d without running statistics (track_running_stats=False: it normalises by the batch's)"
+                return _Refusal("BatchNorm2d without running statistics (track_running_stats=False: it normalises by the batch's)",
+                                "train_bn" if m.training else None)
             if m.training:
-                return "BatchNorm2d in train mode (batch statistics have no device kernel)"
+                return _Refusal("BatchNorm2d in train mode (batch statistics have no device kernel)", "train_bn")
             if not m.affine or m.weight is None or m.bias is None:
                 return "BatchNorm2d without affine parameters (affine=False)"
     return None
@@ -338,7 +379,7 @@ def _train_bn_refusal(mods):
     for m in mods:
         if isinstance(m, torch.nn.BatchNorm2d):
             if not m.training:
-                return 'BatchNorm2d in eval mode (frozen statistics: that is parameter_backward = "device+bn")'
+                return _Refusal('BatchNorm2d in eval mode (frozen statistics: that is parameter_backward = "device+bn")', "frozen_bn")
             if not m.affine or m.weight is None or m.bias is None:
                 return "BatchNorm2d without affine parameters (affine=False)"
             if not m.track_running_stats or m.running_mean is None or m.running_var is None or m.num_batches_tracked is None:
@@ -352,36 +393,37 @@ def _train_bn_refusal(mods):
 
 def _no_bn_refusal(mods):
     if any(isinstance(m, torch.nn.BatchNorm2d) for m in mods):
-        return "BatchNorm2d (its gamma / beta gradients, and the batch statistics in train mode, have no device kernel)"
+        return _Refusal("BatchNorm2d (its gamma / beta gradients, and the batch statistics in train mode, have no device kernel)", "frozen_bn")
     return None
 
 
-_BN_REFUSAL = {None: _no_bn_refusal, False: _bn_refusal, True: _train_bn_refusal}
-
-
-def bn_stack(net, train):
-    """(stack, ffdnet, reason): layers.conv_bn_stack of a net the device weight gradients serve - [(conv, bn or None, relu)] and whether its
-    edge layers are FFDNet's - or (None, None, why not).  train: False - every BatchNorm frozen (eval mode), True - every BatchNorm in train
-    mode, None - no BatchNorm at all (and no FFDNet: parameter_backward = "device").  Refusals in this order: the plugin's tag and type,
-    its modules (RealSN, the BatchNorms' state), layers.conv_bn_stack's own, _structure_refusal's, a weight that is no nn.Parameter."""
+def _bn_stack(net, bn_refusal, batch_stats=False, ffdnet_too=True):
+    """bn_stack for one mode: what it asks of the BatchNorms, whether they normalise by the batch, whether FFDNet is served."""
     DnCNN, FFDNet, RealSNConv2d = _modules()
     ffdnet = isinstance(net, FFDNet)
-    if ffdnet and train is None:
-        return None, None, "FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient"
+    if ffdnet and not ffdnet_too:
+        return None, None, _Refusal("FFDNet: its 5 -> 64 / 64 -> 4 edge layers and BatchNorm2d parameters have no device weight gradient", "frozen_bn")
     why = (_FFDNET_COLOUR if net.num_input_channels != 1 else None) if ffdnet else _plugin_refusal(net, "device weight gradients")
     if why is not None:
         return None, None, why
     mods = list(net.intermediate_dncnn.itermediate_dncnn if ffdnet else net.dncnn)
     if any(isinstance(m, RealSNConv2d) for m in mods):
-        return None, None, "RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)"
-    why = _BN_REFUSAL[train](mods)
+        return None, None, _Refusal("RealSNConv2d (its parameter is weight_orig behind the spectral normalisation)", "train_realsn")
+    why = bn_refusal(mods)
     if why is not None:
-        return None, None, ("FFDNet: " if ffdnet else "") + why
-    stack, why = conv_bn_stack(mods, train_bn=bool(train))
+        return None, None, _Refusal(("FFDNet: " if ffdnet else "") + why, getattr(why, "other", None))
+    stack, why = conv_bn_stack(mods, train_bn=batch_stats)
     why = _structure_refusal(stack, ffdnet) if stack is not None else why
     if why is None and not all(isinstance(c.weight, torch.nn.Parameter) for c, _, _ in stack):
         why = "a conv weight that is not an nn.Parameter"
     return (stack, ffdnet, None) if why is None else (None, None, why)
+
+
+def bn_stack(net, train):
+    """(stack, ffdnet, reason): layers.conv_bn_stack of a net the device weight gradients serve - [(conv, bn or None, relu)] and whether its
+    edge layers are FFDNet's - or (None, None, why not).  train: the stack of the mode frozen_bn (False: every BatchNorm in eval mode), train_bn
+    (True) or plain (None: no BatchNorm, no FFDNet).  Refused in this order: tag and type, RealSN, the BatchNorms' state, conv_bn_stack's, the shape."""
+    return GRAD_MODE[{None: "plain", False: "frozen_bn", True: "train_bn"}[train]].stack(net)
 
 
 _REALSN_OK = "train-mode RealSN conv + ReLU stack"
@@ -437,42 +479,9 @@ def realsn_stack(net):
     return (stack, None) if why is None else (None, why)
 
 
-def _realsn_weight_of(conv):
-    """The parameter of a layer of realsn_stack: a RealSNConv2d's weight_orig, a Conv2d's weight."""
-    return conv.weight_orig if isinstance(conv, _modules()[2]) else conv.weight
-
-
-_TRAIN_BN_OK, _TRAIN_FFDNET_OK = "bias-free conv [+ train-mode BN] + ReLU stack", "FFDNet with its BatchNorm in train mode"
-
-
-_PARAM_OK = {None: ("bias-free conv + ReLU stack", None), False: (_FROZEN_BN_OK, _FROZEN_FFDNET_OK), True: (_TRAIN_BN_OK, _TRAIN_FFDNET_OK)}
-
-
-def _bn_mode(who, frozen_bn, train_bn):
-    """The two keywords as bn_stack's `train`."""
-    if train_bn and frozen_bn:
-        raise ValueError(f"{who}: frozen_bn and train_bn exclude one another")
-    return True if train_bn else (False if frozen_bn else None)
-
-
-def param_eligibility(net, frozen_bn=False, train_bn=False, train_realsn=False):
-    """(ok, reason): whether DenoiserParamGrads (and DEQFixedPoint.parameter_backward = "device") can form the weight gradients of `net`:
-    a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0,
-    no_bn=True) of any depth >= 2.  frozen_bn=True (parameter_backward = "device+bn") accepts in addition an eval-mode affine BatchNorm2d
-    with running statistics behind every 64 -> 64 conv - DnCNN(..., no_bn=False).eval() - and the grayscale FFDNet with its BatchNorms in
-    eval mode.  train_bn=True (parameter_backward = "device+bn-train") accepts those two families with their BatchNorms in TRAIN mode -
-    affine, with running statistics and a float momentum (csrc/bn_train.hip) - and refuses an eval-mode BatchNorm.  bn_stack decides.
-    train_realsn=True (parameter_backward = "device+realsn", the engine's train_realsn="device") is a family of its own: a DnCNN in TRAIN
-    mode whose convolutions are RealSNConv2d or plain bias-free Conv2d, without BatchNorm - RealSN_SimpleCNN as the reference trains it;
-    realsn_stack decides.  CPU-safe."""
-    if train_realsn:
-        if frozen_bn or train_bn:
-            raise ValueError("param_eligibility: train_realsn excludes frozen_bn and train_bn")
-        stack, why = realsn_stack(net)
-        return (False, why) if stack is None else (True, _REALSN_OK)
-    mode = _bn_mode("param_eligibility", frozen_bn, train_bn)
-    stack, ffdnet, why = bn_stack(net, mode)
-    return (False, why) if stack is None else (True, _PARAM_OK[mode][ffdnet])
+def _realsn_mode_stack(net):                                    # (realsn_stack as a mode's stack function answers)
+    stack, why = realsn_stack(net)
+    return (None, None, why) if stack is None else (stack, False, None)
 
 
 def conv_weights(net):
@@ -480,25 +489,62 @@ def conv_weights(net):
     return [m.weight for m in net.dncnn if isinstance(m, torch.nn.Conv2d)]
 
 
-def grad_parameters(net, train_bn=False, train_realsn=False):
-    """The nn.Parameters of a net param_eligibility(net, frozen_bn=True) accepts, in module order - per layer the conv weight, then its
-    BatchNorm's weight (gamma) and bias (beta): the parameters DenoiserParamGrads(..., frozen_bn=True).grads answers for.  train_bn=True:
-    the same for a net param_eligibility(net, train_bn=True) accepts.  train_realsn=True: one per layer of a net param_eligibility(net,
-    train_realsn=True) accepts - the weight_orig of a RealSNConv2d, the weight of a plain Conv2d."""
-    if train_realsn:
-        stack, why = realsn_stack(net)
+class GradMode(typing.NamedTuple):
+    """One way to form the denoiser's weight gradients on the device: what differs between the ways, and nothing else (the module's docstring)."""
+    name: str                       # the public keyword that asks for it ("plain": none)
+    switch: str                     # the DEQFixedPoint.parameter_backward string that asks for it
+    serves: tuple                   # the names of the modes that switch serves, in the order tried
+    engine_option: typing.Any       # (DEQSCIEngine keyword, value) that moves the solve's train-mode f-calls to the device, or None
+    stack: typing.Callable          # net -> (stack [(conv, bn or None, relu)], ffdnet, None) of a net the mode serves, or (None, None, why not)
+    accepted: tuple                 # eligibility's reason for a net it serves: (a DnCNN plugin, FFDNet)
+    host_rule: type                 # the host rule of a layer that is more than a plain convolution
+    device_rule: type               # the device rule of a 64 -> 64 layer with a BatchNorm (Rule.build: DenoiserParamGrads' _MaskedStack)
+
+    def eligibility(self, net):
+        """(ok, reason): whether the mode serves `net`."""
+        stack, ffdnet, why = self.stack(net)
+        return (False, why) if stack is None else (True, self.accepted[bool(ffdnet)])
+
+    def parameters(self, net):
+        """The nn.Parameters of a net the mode serves that .grads answers for, in its order: per layer the conv weight - a RealSNConv2d's
+        weight_orig - then its BatchNorm's weight (gamma) and bias (beta)."""
+        stack, _, why = self.stack(net)
         if stack is None:
             raise ValueError(f"grad_parameters: {why}")
-        return [_realsn_weight_of(conv) for conv, _, _ in stack]
-    stack, _, why = bn_stack(net, bool(train_bn))
-    if stack is None:
-        raise ValueError(f"grad_parameters: {why}")
-    out = []
-    for conv, bn, _ in stack:
-        out.append(conv.weight)
-        if bn is not None:
-            out += [bn.weight, bn.bias]
-    return out
+        RealSNConv2d = _modules()[2]
+        return [p for conv, bn, _ in stack
+                for p in [conv.weight_orig if isinstance(conv, RealSNConv2d) else conv.weight] + ([] if bn is None else [bn.weight, bn.bias])]
+
+
+def grad_mode(who, frozen_bn=False, train_bn=False, train_realsn=False):
+    """The GradMode the three public keywords ask for; who: the entry point, for the error."""
+    if train_realsn and (frozen_bn or train_bn):
+        raise ValueError(f"{who}: train_realsn excludes frozen_bn and train_bn")
+    if train_bn and frozen_bn:
+        raise ValueError(f"{who}: frozen_bn and train_bn exclude one another")
+    asked = {"frozen_bn": frozen_bn, "train_bn": train_bn, "train_realsn": train_realsn}
+    return next((m for m in GRAD_MODES if asked.get(m.name)), GRAD_MODE["plain"])
+
+
+def switch_modes(parameter_backward):
+    """The GradModes a DEQFixedPoint.parameter_backward string serves, in the order tried - or None for a string that is no mode's switch."""
+    return next((tuple(GRAD_MODE[name] for name in m.serves) for m in GRAD_MODES if m.switch == parameter_backward), None)
+
+
+def param_eligibility(net, frozen_bn=False, train_bn=False, train_realsn=False):
+    """(ok, reason): whether DenoiserParamGrads can form the weight gradients of `net` in the mode the keywords name (GRAD_MODES; the
+    module's docstring says what each serves).  No keyword: a bias-free conv + ReLU stack 1 -> 64 -> ... -> 64 -> 1 whose conv weights are
+    nn.Parameters - SimpleCNN, DnCNN(..., lip=0.0, no_bn=True) of any depth >= 2.  frozen_bn / train_bn: in addition an affine BatchNorm2d
+    with running statistics behind every 64 -> 64 conv, in eval / in TRAIN mode (a float momentum; an eval-mode BatchNorm is refused), and
+    the grayscale FFDNet: bn_stack decides.  train_realsn: a DnCNN in TRAIN mode whose convolutions are RealSNConv2d or plain bias-free
+    Conv2d, without BatchNorm: realsn_stack decides.  CPU-safe."""
+    return grad_mode("param_eligibility", frozen_bn, train_bn, train_realsn).eligibility(net)
+
+
+def grad_parameters(net, train_bn=False, train_realsn=False):
+    """The nn.Parameters DenoiserParamGrads.grads answers for, in its order, for a net the mode accepts - frozen_bn without a keyword: per
+    layer the conv weight (a RealSNConv2d's weight_orig), then its BatchNorm's weight (gamma) and bias (beta)."""
+    return grad_mode("grad_parameters", not (train_bn or train_realsn), train_bn and not train_realsn, train_realsn).parameters(net)
 
 
 def _bn_scale(bn, like):
@@ -508,19 +554,19 @@ def _bn_scale(bn, like):
     return T(bn.weight) * inv, T(bn.running_mean), inv
 
 
-def _net_rules(who, net, train, like, update=False):
-    """bn_stack(net, train) as the host walk takes it, in like's dtype: (one rule per layer, the ReLU flags, the edges, ffdnet)."""
-    stack, ffdnet, why = bn_stack(net, train)
+def _net_rules(who, net, mode, like, update=False):
+    """mode.stack(net) as the host walk takes it, in like's dtype: (one rule per layer, the ReLU flags, the edges, ffdnet)."""
+    stack, ffdnet, why = mode.stack(net)
     if stack is None:
         raise ValueError(f"{who}: {why}")
-    W = lambda conv: conv.weight.detach().to(like)
-    rules = [_PlainRule(W(c)) if bn is None else _TrainRule(W(c), bn, update, who) if train else _FrozenRule(W(c), bn) for c, bn, _ in stack]
+    rules = [_PlainRule(conv.weight.detach().to(like)) if bn is None and isinstance(conv, torch.nn.Conv2d) else mode.host_rule(conv, bn, like, update, who)
+             for conv, bn, _ in stack]
     return rules, [relu for _, _, relu in stack], FFDNET_EDGES if ffdnet else PLAIN_EDGES, ffdnet
 
 
-def _net_param_grads(who, net, train, x, v, sigma, masks, want_input=False):
-    """The host walk of a net: -> (gradients in grad_parameters order, masks, J_D(x)^T v or None)."""
-    rules, relus, edges, ffdnet = _net_rules(who, net, train, x)
+def _net_param_grads(who, net, mode, x, v, sigma, masks, want_input=False, update=False):
+    """The host walk of a net: -> (gradients in mode.parameters' order, masks, J_D(x)^T v or None)."""
+    rules, relus, edges, ffdnet = _net_rules(who, net, mode, x, update)
     tape, used = _taped_forward(rules, relus, _first_input(who, edges, x, sigma), masks)
     grads, gx = _walk_back(rules, tape, used, v, edges, want_input and not ffdnet)          # (FFDNet detaches its input)
     return grads, used, gx
@@ -528,12 +574,10 @@ def _net_param_grads(who, net, train, x, v, sigma, masks, want_input=False):
 
 def plan_param_grads_frozen_bn(net, x, v, sigma=None, masks=None):
     """(dD/dtheta)^T v of a net param_eligibility(net, frozen_bn=True) accepts, at x, in x's dtype - the host statement of what
-    DenoiserParamGrads(..., frozen_bn=True).grads runs: plan_param_grads' walk with _FrozenRule where a layer has a BatchNorm - the
-    forward runs the unfolded layers y = relu(s conv(x, W) + t), the walk back carries gm with the folded transposed weights.  FFDNet goes
+    DenoiserParamGrads(..., frozen_bn=True).grads runs: plan_param_grads' walk with _FrozenRule where a layer has a BatchNorm.  FFDNet goes
     through FFDNET_EDGES at the noise level sigma (1 or n values; sigma's channel of the first weight included) and differentiates nothing
-    through its input.  masks: those of another forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters order,
-    masks)."""
-    return _net_param_grads("plan_param_grads_frozen_bn", net, False, x, v, sigma, masks)[:2]
+    through its input.  masks: those of another forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters order, masks)."""
+    return _net_param_grads("plan_param_grads_frozen_bn", net, GRAD_MODE["frozen_bn"], x, v, sigma, masks)[:2]
 
 
 def plan_forward_train_bn(net, x, sigma=None, update=True):
@@ -541,7 +585,7 @@ def plan_forward_train_bn(net, x, sigma=None, update=True):
     the biased variance of c = conv(x, W) over the batch, y = gamma (c - mean) / sqrt(var + eps) + beta, the ReLU; FFDNet at the noise level
     sigma through its pixel-(un)shuffle.  update=True moves the module's buffers as torch does: running_mean <- (1 - m) running_mean + m mean,
     running_var <- (1 - m) running_var + m var P / (P - 1), num_batches_tracked += 1.  -> (noise, masks)."""
-    rules, relus, edges, _ = _net_rules("plan_forward_train_bn", net, True, x, update)
+    rules, relus, edges, _ = _net_rules("plan_forward_train_bn", net, GRAD_MODE["train_bn"], x, update)
     tape, used = _taped_forward(rules, relus, _first_input("plan_forward_train_bn", edges, x, sigma))
     return edges[2](rules[-1].forward(tape[-1][0])[0]), used
 
@@ -553,40 +597,19 @@ def plan_param_grads_train_bn(net, x, v, sigma=None, masks=None, input_grad=Fals
     of another forward pass (the device's, unpack_masks).  Returns (gradients in grad_parameters(net, train_bn=True) order, masks) - with
     input_grad=True (gradients, masks, J_D(x)^T v: the true input product, statistic terms included; None for FFDNet, which detaches its
     input)."""
-    out = _net_param_grads("plan_param_grads_train_bn", net, True, x, v, sigma, masks, input_grad)
+    out = _net_param_grads("plan_param_grads_train_bn", net, GRAD_MODE["train_bn"], x, v, sigma, masks, input_grad)
     return out if input_grad else out[:2]
 
 
 def plan_param_grads_realsn(net, x, v, masks=None, input_grad=False, update=False):
     """(dD/dtheta)^T v of a net param_eligibility(net, train_realsn=True) accepts, at x, in x's dtype - the host statement of what
-    DenoiserParamGrads(..., train_realsn=True).grads runs: per RealSNConv2d one call of realsn.power_iteration from the module's weight_u
-    (weight = weight_orig / cur_sigma * sigma; u, v constants), plan_param_grads' walk on the normalised weights, and realsn.weight_grad
-    turning each layer's gradient G_i into that of weight_orig; a plain Conv2d's G_i is its gradient.  update=True writes the new weight_u and
-    weight into the module as its own forward would; otherwise the module is left alone.  masks: those of another forward pass.  Returns
-    (gradients in grad_parameters(net, train_realsn=True) order, masks) - with input_grad=True (gradients, masks, J_D(x)^T v)."""
-    from . import realsn
-    RealSNConv2d = _modules()[2]
-    stack, why = realsn_stack(net)
-    if stack is None:
-        raise ValueError(f"plan_param_grads_realsn: {why}")
-    steps, rules = [], []
+    DenoiserParamGrads(..., train_realsn=True).grads runs: plan_param_grads' walk with _RealSNRule where a layer is a RealSNConv2d; a plain
+    Conv2d's G_i is its gradient.  update=True writes the new weight_u and weight into the module as its own forward would; otherwise the
+    module is left alone.  masks: those of another forward pass.  Returns (gradients in grad_parameters(net, train_realsn=True) order,
+    masks) - with input_grad=True (gradients, masks, J_D(x)^T v)."""
     with torch.no_grad():
-        for conv, _, _ in stack:
-            if isinstance(conv, RealSNConv2d):
-                W = conv.weight_orig.detach()
-                weight, u, vr, cs = realsn.power_iteration(W, conv.weight_u, conv.sigma, conv.n_power_iterations, conv.eps)
-                if update:
-                    conv.weight_u.copy_(u)
-                    conv.weight.copy_(weight)
-                steps.append((W, u, vr, cs, conv.sigma))
-            else:
-                weight = conv.weight.detach()
-                steps.append(None)
-            rules.append(_PlainRule(weight.to(x)))
-        tape, used = _taped_forward(rules, [relu for _, _, relu in stack], x, masks)
-        Gs, gx = _walk_back(rules, tape, used, v, PLAIN_EDGES, input_grad)
-        grads = [G if st is None else realsn.weight_grad(G.to(st[0]), *st).to(x) for G, st in zip(Gs, steps)]
-    return (grads, used, gx) if input_grad else (grads, used)
+        out = _net_param_grads("plan_param_grads_realsn", net, GRAD_MODE["train_realsn"], x, v, None, masks, input_grad, update)
+    return out if input_grad else out[:2]
 
 
 # ----------------------------------------------------------------------------- FFDNet, differentiated through its input
@@ -720,13 +743,28 @@ _FFDNET_KERNELS = (_hip.pack_head_masked_weights, _hip.pack_tail_weights, _hip.f
 # which makes what only the way back needs - no pack: a pack copies from the host, and the stream would wait - behind the whole forward, and
 # .backward(input, g, need) -> ([one gradient or None per parameter], the gradient behind the convolution) for g the gradient masked by the
 # layer's ReLU and need one bool per parameter.  .ws: the scratch buffer of the rule's weight-gradient kernel, which its owner assigns.
+# GradMode.device_rule is the rule of a layer with a BatchNorm, Rule(w, bias, conv, bn, ws_bn) - one without is a _Conv64 - and Rule.build(stack, x,
+# sigma) -> (the _MaskedStack that keeps its activations, the edge layers' realsn steps, R1 / R2's workspace) builds DenoiserParamGrads in every mode.
 class _Conv64:
     """conv [+ folded bias] + ReLU: Winograd F(2x2,3x3) with the bias and the ReLU, relu_mask_pack; W0 if the weight is asked for."""
-    count, bn_workspace = 1, False
+    count, bn_workspace, batch_stats = 1, False, False
 
-    def __init__(self, w, bias=None):
+    def __init__(self, w, bias=None, conv=None, bn=None, ws_bn=None):
         self.u, self.ut, self.ws = _hip.pack_winograd_weights(w), _hip.pack_winograd_weights(_transposed(w)), None
         self.bias = None if bias is None else bias.to(w.device, torch.float32).contiguous()
+
+    @classmethod
+    def build(cls, stack, x, sigma):
+        ffdnet = sigma is not None
+        P = x.shape[0] * x.shape[2] * x.shape[3] // (4 if ffdnet else 1)             # pixels per channel at the 64 -> 64 layers
+        if cls.batch_stats and P < 2:
+            raise ValueError(f"DenoiserParamGrads: expected more than 1 value per channel when training, got {P}")
+        ws_bn = _hip.bn_train_workspace(P, x.device) if cls.batch_stats and any(bn is not None for _, bn, _ in stack[1:-1]) else None
+        layers = [(conv.weight.detach(), None, relu) for conv, _, relu in stack] if cls.batch_stats else folded(stack)
+        f32 = lambda t: t.to(x.device, torch.float32)
+        with torch.no_grad():
+            rules = [(_Conv64 if bn is None else cls)(f32(w), b, conv, bn, ws_bn) for (conv, bn, _), (w, b, _) in zip(stack[1:-1], layers[1:-1])]
+        return _MaskedStack(layers, x, sigma, keep=True, rules=rules, through_input=not ffdnet), None, None
 
     def forward(self, h):
         h = _hip.conv3x3_c64_winograd(h, self.u, self.bias, True)
@@ -747,7 +785,7 @@ class _Frozen64(_Conv64):
     if any of W, gamma, beta is asked for.  W, s fp32 and mean, 1 / sqrt(var + eps) float64 are the unfolded layer's."""
     count, bn_workspace = 3, True
 
-    def __init__(self, w, bias, conv, bn):
+    def __init__(self, w, bias, conv, bn, ws_bn=None):
         super().__init__(w, bias)
         self.conv, self.bn = conv, bn
 
@@ -768,9 +806,9 @@ class _Train64(_Conv64):
     """Train-mode BatchNorm: the raw Winograd convolution c, T1 (batch statistics; the module's running buffers move, once), T2 (normalise +
     ReLU + the mask words); c is kept.  Back: T3 (dgamma, dbeta), T4 (dc, in place), W0 on dc if the weight is asked for; dc goes down
     through the UNFOLDED transposed weight.  ws_bn: bn_train_workspace's buffer."""
-    count = 3
+    count, batch_stats = 3, True
 
-    def __init__(self, w, bn, ws_bn):
+    def __init__(self, w, bias, conv, bn, ws_bn):
         super().__init__(w)
         self.bn, self.ws_bn, self.eps = bn, ws_bn, float(bn.eps)
         self.gamma = bn.weight.detach().to(w.device, torch.float32).contiguous()
@@ -799,6 +837,10 @@ class _RealSN64(_Conv64):
 
     def __init__(self, u, ut, step, rws):
         self.u, self.ut, self.ws, self.bias, self.step, self.rws = u, ut, None, None, step, rws
+
+    @classmethod
+    def build(cls, stack, x, sigma):
+        return _realsn_device_stack(stack, x, True, True)
 
     def backward(self, inp, g, need):
         if not need[0]:
@@ -863,6 +905,21 @@ def _realsn_device_stack(stack, x, keep, step):
     rules = [_RealSN64(p, pt, st, rws) for (p, pt), st in zip(packs[1:-1], steps[1:-1])]
     edges = (packs[0][0], packs[0][1], packs[-1][0], packs[-1][1])
     return _MaskedStack(None, x, keep=keep, rules=rules, edges=edges), steps, rws
+
+
+# ----------------------------------------------------------------------------- the modes, stated once, in the order configure_training tries them
+GRAD_MODES = (
+    GradMode("plain", "device", ("plain",), None, functools.partial(_bn_stack, bn_refusal=_no_bn_refusal, ffdnet_too=False),
+             ("bias-free conv + ReLU stack", None), _PlainRule, _Conv64),
+    GradMode("train_realsn", "device+realsn", ("plain", "train_realsn"), ("train_realsn", "device"), _realsn_mode_stack,
+             (_REALSN_OK, None), _RealSNRule, _RealSN64),
+    GradMode("frozen_bn", "device+bn", ("plain", "frozen_bn"), None, functools.partial(_bn_stack, bn_refusal=_bn_refusal),
+             ("bias-free conv [+ frozen BN] + ReLU stack", "FFDNet with its BatchNorm frozen"), _FrozenRule, _Frozen64),
+    GradMode("train_bn", "device+bn-train", ("plain", "frozen_bn", "train_bn"), ("train_bn", "device"),
+             functools.partial(_bn_stack, bn_refusal=_train_bn_refusal, batch_stats=True),
+             ("bias-free conv [+ train-mode BN] + ReLU stack", "FFDNet with its BatchNorm in train mode"), _TrainRule, _Train64),
+)
+GRAD_MODE = {m.name: m for m in GRAD_MODES}
 
 
 _RELEASED = "DenoiserParamGrads.grads: the activations were released"
@@ -947,74 +1004,41 @@ class DenoiserParamGrads:
     bool per parameter - the walk stops below the lowest layer asked for, the others are None.  .release() drops the activations.
     Everything is enqueued on the current stream with no host synchronisation.  Raises ValueError with param_eligibility()'s reason.
 
-    The default serves the nets param_eligibility(net) accepts and answers for conv_weights(net): every 64 -> 64 layer is _Conv64 (W0).
+    The keywords name the mode (GRAD_MODES): it serves the nets param_eligibility accepts under the same keywords, and .grads answers for
+    the mode's parameters in their order - conv_weights(net) by default (every 64 -> 64 layer is _Conv64: W0), else grad_parameters'.
 
-    frozen_bn=True: the nets param_eligibility(net, frozen_bn=True) accepts; .grads answers for grad_parameters(net) in its order (per
-    layer dW, then dgamma, dbeta).  A 64 -> 64 layer with a BatchNorm is _Frozen64: the BatchNorm folded into the forward and into the
-    walk, csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass) - skipped where none of the three is asked
-    for.  FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
+    frozen_bn=True: a 64 -> 64 layer with a BatchNorm is _Frozen64: the BatchNorm folded into the forward and into the walk,
+    csrc/wgrad_bn.hip's W0-BN (dW = s R, dbeta, and sum W R for dgamma, from one pass) - skipped where none of the three is asked for.
+    FFDNet (sigma: its (1,) or (n,) noise levels, required) reads both edge layers through the pixel-(un)shuffle with W2, .noise is
     ffdnet_tail's, and .vjp is zero: its input is detached.
 
-    train_bn=True: the nets param_eligibility(net, train_bn=True) accepts - the BatchNorms in TRAIN mode, as the reference trains them -
-    and grad_parameters(net, train_bn=True).  A 64 -> 64 layer with a BatchNorm is _Train64: csrc/bn_train.hip's T1 updates the module's
-    running_mean / running_var / num_batches_tracked IN PLACE on the device, exactly once per construction, and the layer keeps its
-    convolution output c beside the post-ReLU activation: (2 (k-2) + 1) n 64 H W 4 bytes for k layers (FFDNet: 27 activations at half
-    resolution), twice the frozen mode's.  T3 and T4 run wherever the walk passes, asked for or not: dc is what goes down, through the
-    plain (unfolded) transposed weight, so .vjp(v) is the true input product, the statistic terms included (FFDNet: zero).
+    train_bn=True - the BatchNorms in TRAIN mode, as the reference trains them: a 64 -> 64 layer with a BatchNorm is _Train64:
+    csrc/bn_train.hip's T1 updates the module's running_mean / running_var / num_batches_tracked IN PLACE on the device, exactly once per
+    construction, and the layer keeps its convolution output c beside the post-ReLU activation: (2 (k-2) + 1) n 64 H W 4 bytes for k
+    layers (FFDNet: 27 activations at half resolution), twice the frozen mode's.  T3 and T4 run wherever the walk passes, asked for or
+    not: dc is what goes down, through the plain (unfolded) transposed weight, so .vjp(v) is the true input product (FFDNet: zero).
 
-    train_realsn=True: the nets param_eligibility(net, train_realsn=True) accepts and grad_parameters(net, train_realsn=True) - see
-    _init_realsn.  The construction takes every RealSNConv2d's power step IN PLACE in the module, exactly once."""
+    train_realsn=True: per RealSNConv2d R1 (the module's weight_u and weight move IN PLACE, exactly once, as its own forward moves them; W,
+    the new u, v and the record are kept as autograd._RealSNWeight keeps them), R3 (both packs, on the device), then the masked stack.
+    Back: W0 / W1 give the NORMALISED weight's gradient and R2 turns it into weight_orig's; a plain Conv2d's is its own.  No atomics."""
 
-    def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False, train_realsn=False):
-        self._steps = None
-        if train_realsn:
-            self._init_realsn(net, x, frozen_bn or train_bn)
-            return
-        train = _bn_mode("DenoiserParamGrads", frozen_bn, train_bn)
-        stack, self.ffdnet, why = bn_stack(net, train)
+    def __init__(self, net, x, sigma=None, frozen_bn=False, train_bn=False, train_realsn=False, *, mode=None):
+        mode = mode or grad_mode("DenoiserParamGrads", frozen_bn, train_bn, train_realsn)          # (mode: a caller's GradMode in hand)
+        stack, self.ffdnet, why = mode.stack(net)
         if stack is None:
             raise ValueError(f"DenoiserParamGrads: {why}")
         self.shape, self._sigma = _image("DenoiserParamGrads", x, sigma, self.ffdnet)
         self._x = _hip.f32c(x.detach())
-        n, H, W = (self.shape[0], self.shape[2] // 2, self.shape[3] // 2) if self.ffdnet else (self.shape[0],) + self.shape[2:]
-        if train and n * H * W < 2:
-            raise ValueError(f"DenoiserParamGrads: expected more than 1 value per channel when training, got {n * H * W}")
-        kinds = [_Conv64 if bn is None else _Train64 if train else _Frozen64 for _, bn, _ in stack[1:-1]]
-        ws_train = _hip.bn_train_workspace(n * H * W, x.device) if _Train64 in kinds else None
-        layers = [(conv.weight.detach(), None, relu) for conv, _, relu in stack] if train else folded(stack)
-        f32 = lambda t: t.to(x.device, torch.float32)
-        with torch.no_grad():
-            rules = [_Conv64(f32(w), b) if kind is _Conv64 else _Train64(f32(w), bn, ws_train) if train else _Frozen64(f32(w), b, conv, bn)
-                     for kind, (conv, bn, _), (w, b, _) in zip(kinds, stack[1:-1], layers[1:-1])]
-        self._stack = _MaskedStack(layers, self._x, self._sigma, keep=True, rules=rules, through_input=not self.ffdnet)
+        self._stack, self._steps, self._rws = mode.device_rule.build(stack, self._x, self._sigma)
+        rules = self._stack.rules
         self._counts = [1] + [r.count for r in rules] + [1]                 # parameters per layer
         self.masks, self.noise = self._stack.masks, self._stack.noise
         # the scratch buffers of the walk's kernels, behind the forward's activations: W1 and W0 share one, W2 and W0-BN the other
-        self._ws = _hip.wgrad_workspace(n, H, W, x.device) if not self.ffdnet or not all(k.bn_workspace for k in kinds) else None
-        self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, x.device) if self.ffdnet or any(k.bn_workspace for k in kinds) else None
+        n, H, W = (self.shape[0], self.shape[2] // 2, self.shape[3] // 2) if self.ffdnet else (self.shape[0],) + self.shape[2:]
+        self._ws = _hip.wgrad_workspace(n, H, W, x.device) if not self.ffdnet or not all(r.bn_workspace for r in rules) else None
+        self._ws_bn = _hip.wgrad_bn_workspace(n, H, W, x.device) if self.ffdnet or any(r.bn_workspace for r in rules) else None
         for rule in rules:
             rule.ws = self._ws_bn if rule.bn_workspace else self._ws
-
-    def _init_realsn(self, net, x, other_mode):
-        """train_realsn=True: the nets param_eligibility(net, train_realsn=True) accepts, answering for grad_parameters(net,
-        train_realsn=True).  Forward: per RealSNConv2d R1 (the module's weight_u and weight move IN PLACE, once, as its own forward moves
-        them; W, the new u, v and the record are kept as autograd._RealSNWeight keeps them), R3 (the forward and transposed packs, on the
-        device), then the masked stack with every activation kept.  Back: W0 / W1 give G_i, the gradient of the NORMALISED weight, and R2
-        (_hip.realsn_grad) turns it into weight_orig's; a plain Conv2d's G_i is its gradient.  No atomics, no host synchronisation."""
-        if other_mode:
-            raise ValueError("DenoiserParamGrads: train_realsn excludes frozen_bn and train_bn")
-        stack, why = realsn_stack(net)
-        if stack is None:
-            raise ValueError(f"DenoiserParamGrads: {why}")
-        self.ffdnet, self._sigma, self._ws_bn = False, None, None
-        self.shape = _image("DenoiserParamGrads", x)[0]
-        self._x = _hip.f32c(x.detach())
-        self._stack, self._steps, self._rws = _realsn_device_stack(stack, self._x, True, True)
-        self._counts = [1] * len(stack)
-        self.masks, self.noise = self._stack.masks, self._stack.noise
-        self._ws = _hip.wgrad_workspace(self.shape[0], self.shape[2], self.shape[3], x.device)
-        for rule in self._stack.rules:
-            rule.ws = self._ws
 
     def _v(self, v, what):
         if tuple(v.shape) != self.shape:

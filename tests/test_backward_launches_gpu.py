@@ -8,7 +8,13 @@ which keeps these lists keeps the device's work.
 
 The images are (2,1,12,20): ragged against the 16 x 16 tile of the F(2x2,3x3) kernel; FFDNet's 64 -> 64 layers run at 6 x 10.  Beside
 the launches: a train-mode construction moves every BatchNorm's buffers exactly once and the walks move nothing, a second grads(v) is
-bit-equal to the first, and the SHA-256 of every result is printed (not asserted) so that two commits can be compared by eye."""
+bit-equal to the first, and the SHA-256 of every result is printed (not asserted) so that two commits can be compared by eye.
+
+The two train_realsn cases (a four-layer all-RealSNConv2d net in train mode, and the same net with a plain bias-free Conv2d in the
+middle) were pinned later, on the commit before the training modes were gathered into vjp.GRAD_MODES - what THAT commit recorded, printed
+and pasted in the same way, never what the code behind it records.  There the construction takes every RealSNConv2d's power step in the
+module's weight_u / weight exactly once - the buffers equal those of a twin whose own forward ran once - and the walks move nothing."""
+import copy
 import hashlib
 import types
 
@@ -17,6 +23,7 @@ import torch
 
 from deqsci_amd import vjp
 from deqsci_amd.networks import DnCNN, FFDNet
+from deqsci_amd.networks.simplecnn import RealSNConv2d
 from test_denoiser_launches_gpu import recording
 from test_wgrad_bn_host import seeded_bn_dncnn, seeded_ffdnet
 
@@ -42,6 +49,15 @@ def _mixed():
     return net
 
 
+def _realsn(mixed=False):
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(13)                 # weight_orig; every weight_u comes from a generator of its module's own, seeded by the layer
+        net = DnCNN(1, num_of_layers=4, lip=1.0, no_bn=True, tag="denoiser")
+        if mixed:
+            net.dncnn[2] = torch.nn.Conv2d(64, 64, 3, padding=1, bias=False)
+    return net.train()
+
+
 # case -> (the net, DenoiserParamGrads' keywords)
 CASES = {
     "plain": (lambda: _plain(), {}),
@@ -52,6 +68,8 @@ CASES = {
     "train-dncnn": (lambda: seeded_bn_dncnn(5, 6).train(), {"train_bn": True}),
     "train-ffdnet": (lambda: seeded_ffdnet(4).train(), {"train_bn": True}),
     "train-mixed": (lambda: _mixed().train(), {"train_bn": True}),
+    "realsn": (lambda: _realsn(), {"train_realsn": True}),
+    "realsn-mixed": (lambda: _realsn(mixed=True), {"train_realsn": True}),
 }
 
 
@@ -68,15 +86,25 @@ def record(name):
     x = torch.rand(SHAPE, generator=g).to(DEV)
     v = torch.randn(SHAPE, generator=g).to(DEV)
     sigma = torch.tensor([0.1, 0.235], device=DEV) if ffdnet else None
-    params = vjp.grad_parameters(net, train_bn=bool(kw.get("train_bn"))) if kw else vjp.conv_weights(net)
-    convs = [m for m in (net.intermediate_dncnn.itermediate_dncnn if ffdnet else net.dncnn) if isinstance(m, torch.nn.Conv2d)]
-    first = [next(j for j, p in enumerate(params) if p is c.weight) for c in convs]
+    realsn = bool(kw.get("train_realsn"))
+    params = (vjp.grad_parameters(net, train_realsn=True) if realsn else
+              vjp.grad_parameters(net, train_bn=bool(kw.get("train_bn"))) if kw else vjp.conv_weights(net))
+    convs = [m for m in (net.intermediate_dncnn.itermediate_dncnn if ffdnet else net.dncnn) if isinstance(m, (torch.nn.Conv2d, RealSNConv2d))]
+    weight_of = lambda c: c.weight_orig if isinstance(c, RealSNConv2d) else c.weight
+    first = [next(j for j, p in enumerate(params) if p is weight_of(c)) for c in convs]
     mid = len(convs) // 2
     has_bn = first[mid + 1] - first[mid] == 3
     only = lambda j: [i == j for i in range(len(params))]
     bns = [m for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)]
-    buffers = lambda: [b.clone() for m in bns for b in (m.running_mean, m.running_var, m.num_batches_tracked)]
+    rsn = lambda of: [m for m in of.modules() if isinstance(m, RealSNConv2d)]
+    buffers = lambda of=net: ([b.clone() for m in bns for b in (m.running_mean, m.running_var, m.num_batches_tracked)]
+                              + [b.clone() for m in rsn(of) for b in (m.weight_u, m.weight)])
     assert all(int(m.num_batches_tracked) == 0 for m in bns)
+    before, twin = buffers(), copy.deepcopy(net)
+    if realsn:
+        assert len(rsn(net)) == (len(convs) - 1 if name == "realsn-mixed" else len(convs)) == len(before) // 2
+        with torch.no_grad():
+            twin(x)                           # the module's own train-mode forward: one power step per RealSNConv2d, on the same kernels
     den, logs = types.SimpleNamespace(ranges=None), {}
     with recording(den) as log:
         pg = vjp.DenoiserParamGrads(net, x, sigma, **kw)
@@ -84,6 +112,9 @@ def record(name):
     moved = 1 if kw.get("train_bn") else 0
     assert all(int(m.num_batches_tracked) == moved for m in bns)
     after = buffers()
+    if realsn:                                # every weight_u and weight moved, and exactly once
+        assert all(not torch.equal(a, b) for a, b in zip(after, before))
+        assert all(torch.equal(a, b) for a, b in zip(after, buffers(twin)))
     with recording(den) as log:
         grads = pg.grads(v)
     logs["grads"] = list(log)
@@ -589,6 +620,98 @@ PINNED = {
             ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
             ('deqsci_bn_train_grad_stats_f32', 'p', 'p', 'p', 1e-05, 'p', 'p', 'p', 480, 'p', None),
             ('deqsci_bn_train_grad_apply_f32', 'p', 'p', 'p', 'p', 'p', 1e-05, 'p', 480, None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 2, 12, 20, None),
+        ],
+    },
+    'realsn': {
+        'construct': [
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 1, 64, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 1, 64, None),
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 64, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 64, None),
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 64, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 64, None),
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 1, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 1, None),
+            ('deqsci_conv3x3_c1_to_64_f32', 'p', 'p', 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 2, 12, 20, None),
+        ],
+        'grads': [
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 1, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 1, 40, 40, 'p', None),
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 64, 40, 40, 'p', None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 64, 40, 40, 'p', None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 0, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 1, 64, 40, 40, 'p', None),
+        ],
+        'grads-middle': [
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 64, 40, 40, 'p', None),
+        ],
+        'grads-last': [
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 1, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 1, 40, 40, 'p', None),
+        ],
+        'vjp': [
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 2, 12, 20, None),
+        ],
+    },
+    'realsn-mixed': {
+        'construct': [
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 1, 64, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 1, 64, None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 64, None),
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 64, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 64, None),
+            ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 1, 40, 40, 'p', None),
+            ('deqsci_realsn_pack_f32', 'p', 'p', None, 'p', 64, 1, None),
+            ('deqsci_conv3x3_c1_to_64_f32', 'p', 'p', 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 2, 12, 20, 1, None),
+            ('deqsci_relu_mask_pack_f32', 'p', 'p', 480, None),
+            ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 2, 12, 20, None),
+        ],
+        'grads': [
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 1, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 1, 40, 40, 'p', None),
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 64, 40, 40, 'p', None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 0, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 1, 64, 40, 40, 'p', None),
+        ],
+        'grads-middle': [
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_wgrad3x3_c64_c64_f32', 'p', 'p', 'p', 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 64, 40, 40, 'p', None),
+        ],
+        'grads-last': [
+            ('deqsci_wgrad3x3_c1_c64_f32', 'p', 'p', 'p', 1, 2, 12, 20, 'p', None),
+            ('deqsci_realsn_grad_f32', 'p', 'p', 'p', 'p', 'p', 'p', 1.0, 64, 1, 40, 40, 'p', None),
+        ],
+        'vjp': [
+            ('deqsci_conv3x3_c1_to_64_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
+            ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
             ('deqsci_conv3x3_c64_winograd_masked_f32', 'p', 'p', 'p', 'p', 2, 12, 20, None),
             ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 2, 12, 20, None),
         ],

@@ -247,7 +247,7 @@ def test_switch_and_engine_option_take_the_new_values():
     eng = DEQSCIEngine(seeded_bn_dncnn(5, 1), train_bn="device")                 # eval mode: the folded kernels' business, no reason to give
     assert eng.den.train is None and eng.den.train_why is None and eng.den.fast is not None
     deq.engine_options = {"train_bn": "device"}
-    assert deq._train_bn_engine() is None                                         # not served here: the solve takes the solver as it always did
+    assert deq._train_solve_engine() is None                                         # not served here: the solve takes the solver as it always did
 
 
 def test_bn_train_entry_points_validate_before_any_launch():

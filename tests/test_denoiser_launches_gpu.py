@@ -11,7 +11,12 @@ The shapes are the smallest that still slice and are ragged against both block t
 Winograd one): three images - stack_per_launch=2 makes the second slice one image at an offset into the batch and its range slots -
 with 64->64 layers of 24 x 40 pixels.  Shapes this small take F(2x2,3x3) under the default policy, so the cases pin the split-fp16
 kernels with _hip.FORCE_CONV64 as tests/test_dncnn17_gpu.py does, unless they say otherwise.  Nothing waits and nothing times out here:
-the state behind a stack time-out is set by hand."""
+the state behind a stack time-out is set by hand.
+
+The three train-mode cases (train_bn="device" on FFDNet and on DnCNN-17, train_realsn="device" on RealSN_SimpleCNN; no kernel pinned:
+_hip.FORCE_CONV64 would override their policy "fast32") were pinned later, on the commit before the engine's two train-mode refreshes
+and routes were gathered into one - what THAT commit recorded, never what the code behind it records.  Each gets a net of its own: these
+f-calls move the module's buffers."""
 import contextlib
 import functools
 import os
@@ -29,15 +34,16 @@ DNCNN17 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dn
 # family -> (build_pipeline's denoiser, weights, shape of z: FFDNet's 64->64 layers run at half resolution)
 FAMILIES = {"ffdnet": ("ffdnet", checkpoint.shipped("ffdnet_gray"), (1, 3, 48, 80)),
             "dncnn17": ("DnCNN", DNCNN17, (1, 3, 24, 40)),
-            "cnn": ("SimpleCNN", checkpoint.shipped("cnn"), (1, 3, 24, 40))}
+            "cnn": ("SimpleCNN", checkpoint.shipped("cnn"), (1, 3, 24, 40)),
+            "rsn": ("RealSN_SimpleCNN", checkpoint.shipped("rsn_cnn"), (1, 3, 24, 40))}
 TIMED_OUT = {"stack": False, "per_layer_w16": True}                 # (what the engine sets behind a stack time-out)
 
 
-def case(family, route, last_path, pin="s16", cal=False, n_img=3, ctor=None, after=None):
+def case(family, route, last_path, pin="s16", cal=False, n_img=3, ctor=None, after=None, train=False):
     """route: what _Denoiser._route answers for the recorded f-call; last_path: den.last_path behind it; pin: _hip.FORCE_CONV64; cal: the
     recorded f-call is the calibrating one (else the one behind it); n_img: prepare()'s (None: a bare prepare(n_calls, device)); ctor:
-    DEQSCIEngine's keywords; after: attributes set on the denoiser after prepare()."""
-    return dict(family=family, route=route, last_path=last_path, pin=pin, cal=cal, n_img=n_img, ctor=ctor or {}, after=after or {})
+    DEQSCIEngine's keywords; after: attributes set on the denoiser after prepare(); train: a fresh net in train mode."""
+    return dict(family=family, route=route, last_path=last_path, pin=pin, cal=cal, n_img=n_img, ctor=ctor or {}, after=after or {}, train=train)
 
 
 CASES = {
@@ -59,6 +65,9 @@ CASES = {
     "cnn-min-layers-2": case("cnn", "w16 per layer", "w16 per layer", after={"STACK_MIN_LAYERS": 2}),
     "cnn-no-pin": case("cnn", "per layer", "per layer", pin=None),
     "cnn-torch-edges": case("cnn", "layers", "per layer", ctor={"fused_edges": False}),
+    "ffdnet-train-bn": case("ffdnet", "train bn per layer", "train bn per layer", pin=None, ctor={"train_bn": "device"}, train=True),
+    "dncnn17-train-bn": case("dncnn17", "train bn per layer", "train bn per layer", pin=None, ctor={"train_bn": "device"}, train=True),
+    "rsn-train-realsn": case("rsn", "train realsn per layer", "train realsn per layer", pin=None, ctor={"train_realsn": "device"}, train=True),
 }
 
 
@@ -104,7 +113,7 @@ def recording(den):
 def run_case(name):
     """-> (the launches of the case's f-call, its output, the denoiser, the route of that f-call)."""
     c = CASES[name]
-    net, shape = _net(c["family"]), FAMILIES[c["family"]][2]
+    net, shape = (_net.__wrapped__(c["family"]).train() if c["train"] else _net(c["family"])), FAMILIES[c["family"]][2]
     z = torch.rand(shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(sum(shape)))
     old, _hip.FORCE_CONV64 = _hip.FORCE_CONV64, c["pin"]
     try:
@@ -375,5 +384,111 @@ PINNED = {
     'cnn-torch-edges': [
         ('deqsci_f32_to_split16', 'p', 'p', 3, 24, 40, 'r+24', 8, None),
         ('deqsci_conv3x3_c64_split16', 'p', 'p', None, 'p', 3, 24, 40, 1, 12, 'r+24', 8, None, 8, None, 1, None, None, None),
+    ],
+    'ffdnet-train-bn': [
+        ('deqsci_ffdnet_head_f32', 'p', 'p', 'p', 0, 'p', 3, 24, 40, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_ffdnet_tail_f32', 'p', 'p', None, 'p', 3, 24, 40, None),
+    ],
+    'dncnn17-train-bn': [
+        ('deqsci_conv3x3_c1_to_64_f32', 'p', 'p', 'p', 3, 24, 40, 1, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 0, None),
+        ('deqsci_bn_train_stats_f32', 'p', 'p', 'p', 'p', 'p', 0.1, 2880, 'p', None),
+        ('deqsci_bn_train_apply_f32', 'p', 'p', 'p', 'p', 1e-05, 'p', None, 1, 2880, None),
+        ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 3, 24, 40, None),
+    ],
+    'rsn-train-realsn': [
+        ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 1, 64, 40, 40, 'p', None),
+        ('deqsci_realsn_pack_f32', 'p', 'p', None, None, 1, 64, None),
+        ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 64, 40, 40, 'p', None),
+        ('deqsci_realsn_pack_f32', 'p', 'p', 'p', None, 64, 64, None),
+        ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 64, 40, 40, 'p', None),
+        ('deqsci_realsn_pack_f32', 'p', 'p', 'p', None, 64, 64, None),
+        ('deqsci_realsn_power_f32', 'p', 'p', 'p', 'p', 'p', 1, 1.0, 1e-12, 64, 1, 40, 40, 'p', None),
+        ('deqsci_realsn_pack_f32', 'p', 'p', None, None, 64, 1, None),
+        ('deqsci_conv3x3_c1_to_64_f32', 'p', 'p', 'p', 3, 24, 40, 1, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 1, None),
+        ('deqsci_conv3x3_c64_winograd_f32', 'p', 'p', None, 'p', 3, 24, 40, 1, None),
+        ('deqsci_conv3x3_c64_to_1_f32', 'p', 'p', None, 'p', 3, 24, 40, None),
     ],
 }

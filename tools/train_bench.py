@@ -88,7 +88,7 @@ def step_parts(kind, backend, bsz, iters, reps, warmup):
             out = real_solver(*a, **k)
         spans.append(s)
         return out
-    eng = deq._train_bn_engine()
+    eng = deq._train_solve_engine()
     if eng is not None:                                          # the train-mode f-calls run on the engine: its solve is the forward's solver call
         real_solve = eng.solve
 
