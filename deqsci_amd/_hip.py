@@ -98,6 +98,9 @@ SIGNATURES = {
     "deqsci_bn_train_grad_apply_f32": [_ptr, _ptr, _ptr, _ptr, _ptr, _f64, _ptr, _i64, _ptr],
     "deqsci_mse_stats_grad_f32": [_ptr, _ptr, _ptr, _ptr, _i64, _f32, _ptr, _ptr],
     "deqsci_adam_step_f32": [_ptr, _int, _f32, _f32, _f32, _f32, _f32, _ptr],
+    "deqsci_adam_step_clipped_f32": [_ptr, _int, _f32, _f32, _f32, _f32, _f32, _ptr, _ptr],
+    "deqsci_grad_norm_f32": [_ptr, _i64, _f64, _ptr, _ptr, _ptr],
+    "deqsci_grad_scale_f32": [_ptr, _i64, _ptr, _ptr],
     "deqsci_synth_batch_u8": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_rgb_to_gray_u8": [_ptr, _ptr, _i64, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
@@ -109,7 +112,7 @@ OTHER_EXPORTS = ("deqsci_version", "deqsci_error_string", "deqsci_anderson_chunk
                  "deqsci_gaptv_workspace_bytes", "deqsci_tv_chambolle_workspace_bytes", "deqsci_sqerr_workspace_bytes", "deqsci_power_workspace_bytes",
                  "deqsci_broyden_workspace_bytes", "deqsci_broyden_chunk", "deqsci_epsilon2_workspace_bytes", "deqsci_epsilon2_chunk",
                  "deqsci_wgrad_workspace_bytes", "deqsci_wgrad_bn_workspace_bytes", "deqsci_realsn_workspace_bytes",
-                 "deqsci_bn_train_workspace_bytes", "deqsci_mse_workspace_bytes")
+                 "deqsci_bn_train_workspace_bytes", "deqsci_mse_workspace_bytes", "deqsci_grad_norm_workspace_bytes")
 
 
 class DeqsciHipError(RuntimeError):
@@ -169,6 +172,8 @@ def load():
     lib.deqsci_bn_train_workspace_bytes.argtypes = [_i64]
     lib.deqsci_mse_workspace_bytes.restype = ctypes.c_size_t
     lib.deqsci_mse_workspace_bytes.argtypes = [_i64]
+    lib.deqsci_grad_norm_workspace_bytes.restype = ctypes.c_size_t
+    lib.deqsci_grad_norm_workspace_bytes.argtypes = [_ptr, _i64]
     lib.deqsci_gaptv_workspace_bytes.restype = _i64
     lib.deqsci_gaptv_workspace_bytes.argtypes = [_i64, _i64, _i64, _i64]
     lib.deqsci_tv_chambolle_workspace_bytes.restype = _i64
@@ -2060,11 +2065,12 @@ def adam_scalars(step, lr, betas):
     return math.sqrt(1.0 - b2 ** step), lr / (1.0 - b1 ** step)
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps):
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps, stats=None):
     """L2: one Adam step (torch-1.9 F.adam, no weight decay, no amsgrad) of the listed tensors, ADAM_MAX_TENSORS per launch -> the number of
     launches.  params, exp_avgs, exp_avg_sqs are updated IN PLACE through raw pointers (the caller bumps the parameters' version
     counters); all fp32 on one device, dense (contiguous; views into a flat buffer will do).  step: the step count being taken (>= 1),
-    one int or one per tensor.  Builds the table on the host each call: no device allocation, no synchronisation."""
+    one int or one per tensor.  Builds the table on the host each call: no device allocation, no synchronisation.
+    stats: grad_norm's words on the parameters' device - L2c: the step on g * stats[1], and nothing written where stats[2] > 0."""
     n = len(params)
     if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
         raise DeqsciHipError("adam_step: params, grads, exp_avgs and exp_avg_sqs must have one length")
@@ -2079,6 +2085,9 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps):
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev
                     and t.numel() == quad[0].numel() and t.numel() > 0):
                 raise DeqsciHipError(f"adam_step: {name} {i} must be a non-empty contiguous float32 tensor of the parameter's size on {dev}")
+    if stats is not None and not (isinstance(stats, torch.Tensor) and stats.dtype == torch.float64 and stats.device == dev and stats.is_contiguous()
+                                  and stats.numel() >= 3):
+        raise DeqsciHipError(f"adam_step: stats must be at least 3 contiguous float64 values on {dev} (grad_norm's)")
     b1, b2 = float(betas[0]), float(betas[1])
     lib, launches = load(), 0
     scalars = {}
@@ -2095,9 +2104,76 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas, eps):
                 e.param, e.grad, e.exp_avg, e.exp_avg_sq = params[j].data_ptr(), grads[j].data_ptr(), exp_avgs[j].data_ptr(), exp_avg_sqs[j].data_ptr()
                 e.numel = params[j].numel()
                 e.bc2s, e.step_size = scalars[t]
-            _check(lib.deqsci_adam_step_f32(ctypes.cast(table, _ptr), hi - lo, b1, 1.0 - b1, b2, 1.0 - b2, float(eps), st), "adam_step")
+            if stats is None:
+                _check(lib.deqsci_adam_step_f32(ctypes.cast(table, _ptr), hi - lo, b1, 1.0 - b1, b2, 1.0 - b2, float(eps), st), "adam_step")
+            else:
+                _check(lib.deqsci_adam_step_clipped_f32(ctypes.cast(table, _ptr), hi - lo, b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
+                                                        stats.data_ptr(), st), "adam_step (clipped)")
             launches += 1
     return launches
+
+
+class GradEntry(ctypes.Structure):
+    """deqsci_grad_entry"""
+    _fields_ = [("grad", _ptr), ("numel", _i64)]
+
+
+def _grad_table(grads, what):
+    """-> (the deqsci_grad_entry table of the listed gradients, their device): fp32, dense, non-empty, on one HIP device"""
+    dev = grads[0].device if grads else None
+    table = (GradEntry * max(len(grads), 1))()
+    for i, g in enumerate(grads):
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == dev and g.numel() > 0):
+            raise DeqsciHipError(f"{what}: gradient {i} must be a non-empty contiguous float32 tensor on {dev}; deqsci_amd has no CPU path")
+        table[i].grad, table[i].numel = g.data_ptr(), g.numel()
+    return table, dev
+
+
+def grad_norm_launches(n_tensors):
+    """The launches of grad_norm for n_tensors gradients: a chunk and a fold kernel per table of ADAM_MAX_TENSORS, one final kernel."""
+    return 2 * -(-n_tensors // ADAM_MAX_TENSORS) + 1
+
+
+def grad_norm_workspace(grads):
+    """The caller-owned workspace of grad_norm for the listed gradients (float64 words; no initialisation needed)."""
+    table, dev = _grad_table(grads, "grad_norm_workspace")
+    return _partials(load().deqsci_grad_norm_workspace_bytes(ctypes.cast(table, _ptr), len(grads)), dev)
+
+
+def grad_norm(grads, max_norm, stats=None, workspace=None):
+    """L3: the global 2-norm of the listed gradients (any number; fp32, dense, on one device - views into a flat buffer will do) ->
+    stats (3 + n,) float64 on their device: the norm, coef = fp32(min(1, max_norm / (norm + 1e-6))), the number of non-finite elements,
+    then every tensor's own norm.  Deterministic (csrc/rows.hpp's order per tensor, then the list order: tests/clip_ref.py);
+    grad_norm_launches(n) launches, no host synchronisation; stats / workspace: given by a caller that must not allocate."""
+    n = len(grads)
+    if n == 0:
+        raise DeqsciHipError("grad_norm: no gradients (and so no device to put the norm on)")
+    if not float(max_norm) >= 0.0:
+        raise DeqsciHipError(f"grad_norm: max_norm must be >= 0, got {max_norm!r}")
+    table, dev = _grad_table(grads, "grad_norm")
+    if stats is None:
+        stats = torch.empty((3 + n,), device=dev, dtype=torch.float64)
+    elif stats.dtype != torch.float64 or stats.numel() != 3 + n or not stats.is_contiguous() or stats.device != dev:
+        raise DeqsciHipError(f"grad_norm: stats must be 3 + {n} contiguous float64 values on {dev}")
+    lib = load()
+    workspace = _partials(lib.deqsci_grad_norm_workspace_bytes(ctypes.cast(table, _ptr), n), dev, workspace,
+                          "grad_norm: workspace too small (grad_norm_workspace(grads))")
+    with _dev(grads[0]):
+        _check(lib.deqsci_grad_norm_f32(ctypes.cast(table, _ptr), n, float(max_norm), stats.data_ptr(), workspace.data_ptr(), _stream()), "grad_norm")
+    return stats
+
+
+def grad_scale_(grads, stats):
+    """L3s: g *= stats[1] in place for the listed gradients (one fp32 rounding); nothing is written where stats[2] > 0 -> the launches."""
+    n = len(grads)
+    if n == 0:
+        return 0
+    table, dev = _grad_table(grads, "grad_scale_")
+    if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.float64 and stats.device == dev and stats.is_contiguous() and stats.numel() >= 3):
+        raise DeqsciHipError(f"grad_scale_: stats must be at least 3 contiguous float64 values on {dev} (grad_norm's)")
+    with _dev(grads[0]):
+        _check(load().deqsci_grad_scale_f32(ctypes.cast(table, _ptr), n, stats.data_ptr(), _stream()), "grad_scale_")
+    return -(-n // ADAM_MAX_TENSORS)
 
 
 # ----------------------------------------------------------------------------- training batches out of raw video (csrc/synth.hip)

@@ -7,7 +7,7 @@ Every flag of the reference parses (so its test_*.sh and train_*.sh command line
 ignored.  `--inference False` trains (deqsci_amd.training.train_solver_sci, the reference's loop): --trainpath DIR/ holds mask.mat, gt/ and
 measurement/; --n_epochs --batch_size --lr --lr_gamma --sched_step --print_every_n_steps --save_every_n_steps as in the reference; resumed
 from --loadpath (a missing file is an error; without the flag: random weights), checkpoints under --savepath + 'model/'.  Single device.  `--train_backend device|autograd`,
-`--seed` and `--max_steps` are this build's ("Training").
+`--seed`, `--max_steps` and `--clip_grad_norm` are this build's ("Training").
 `--trainvideos DIR --trainmask FILE` (this build's) train from raw video in place of --trainpath: patches of --patch_size x --patch_size x
 --frames are cut out of the videos, turned (--augment) and measured on the device, --patches_per_epoch per epoch (deqsci_amd.synth).
 
@@ -204,6 +204,9 @@ def parser():
                             "is served (training.configure_training prints what it chose); autograd = torch's, as the reference")
     train.add_argument('--seed', type=int, default=None, help="(this build) torch.manual_seed before the data loader is built (the shuffle)")
     train.add_argument('--max_steps', type=int, default=None, help="(this build) stop after this many training steps in all")
+    train.add_argument('--clip_grad_norm', type=float, default=None,
+                       help="(this build) clip the global gradient norm to this value and skip a step whose gradient is not finite "
+                            "(deqsci_amd.optim: on the device with --train_backend device); default: no clipping, as the reference")
     ignored = p.add_argument_group("accepted for command-line compatibility, unused")
     ignored.add_argument('--etainit', type=float, default=0.9)
     ignored.add_argument('--sigma', type=int, default=0)
@@ -265,7 +268,7 @@ def train(args):
         use_dataparallel=False, scheduler=scheduler, print_every_n_steps=args.print_every_n_steps,
         save_every_n_steps=args.save_every_n_steps, start_epoch=start_epoch, test_dataloader=test_dataset,
         train_img_path=args.savepath + 'img/train/', test_img_path=args.savepath + 'img/test/', best_img_path=args.savepath + 'img/best/',
-        tflog_path=args.savepath, max_steps=args.max_steps)
+        tflog_path=args.savepath, max_steps=args.max_steps, clip_grad_norm=args.clip_grad_norm)
 
 
 def run(args):

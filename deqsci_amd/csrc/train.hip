@@ -9,13 +9,22 @@
 //                          block_sums_to) -> stats[0..2]
 //   L2  adam_kernel        one Adam step of up to DEQSCI_ADAM_MAX_TENSORS tensors in ONE launch: one workgroup = one chunk of one tensor,
 //                          found by a binary search over the prefix sums of the per-tensor chunk counts
+//   L2c adam_clip_kernel   the same body's second instantiation: g * coef in place of g, coef = stats[1] of L3 read on the device, and not
+//                          a word written where stats[2] > 0 (a non-finite gradient)
+//   L3  grad_norm_*        the global norm of a list of gradients: (a) chunk kernel, one workgroup = one chunk of one tensor, found as L2
+//                          finds it: squares in float64 (exact) and the non-finite count -> part[chunk][2]; (b) fold kernel, one
+//                          workgroup = one tensor: its chunk partials in L1b's order -> tsum[tensor][2]; (c) final kernel, one workgroup:
+//                          thread 0 adds the tensors' sums in list order -> stats[0..2], the per-tensor norms behind them.  (a) and (b)
+//                          once per table of DEQSCI_ADAM_MAX_TENSORS tensors, (c) once: 2 tables + 1 launches.
+//   L3s grad_scale_kernel  g *= coef for a table of tensors; nothing written where stats[2] > 0 or coef == 1
 //
 // Determinism: no atomics, no counters.  L1's sums take the two-stage order of csrc/rows.hpp (tests/rows_order.py: sum_workgroup with
 // P = PER_THREAD), whether a group is read as a float4 (rec, gt and grad all 16-byte aligned) or element by element; a NaN or Inf in d
 // is counted and enters stats[0] as it is (the reference's loss is NaN there too), and the gradient is written all the same.
 // L2 is elementwise: a tensor whose four pointers are all 16-byte aligned is walked as float4 with a scalar tail, any other (a view into
-// a flat buffer: 4-byte aligned only) element by element - the same arithmetic.
-// HBM-streaming: L1 12 bytes per element, L2 28.
+// a flat buffer: 4-byte aligned only) element by element - the same arithmetic.  L3's sums take the same two-stage order per tensor and
+// then the list order, so tests/clip_ref.py restates them on the host bit for bit.
+// HBM-streaming: L1 12 bytes per element, L2 and L2c 28, L3 4, L3s 8.
 #include "rows.hpp"
 
 namespace deqsci {
@@ -104,7 +113,14 @@ __device__ __forceinline__ void adam4(float4& p, float4 g, float4& m, float4& v,
     adam1(p.w, g.w, m.w, v.w, k);
 }
 
-__global__ __launch_bounds__(TB) void adam_kernel(const AdamArgs a) {
+// CLIP: L2c.  stats[1] and stats[2] are wave-uniform scalar loads; the early return leaves every tensor as it was.
+template <bool CLIP>
+__device__ __forceinline__ void adam_body(const AdamArgs& a, const double* __restrict__ stats) {
+    float coef = 1.0f;
+    if (CLIP) {
+        if (stats[2] > 0.0) return;
+        coef = (float)stats[1];                               // (exact: L3 stored an fp32's value)
+    }
     // the tensor of this chunk: the last i with first[i] <= blockIdx.x (wave-uniform: scalar loads from the argument segment)
     const uint32_t b = blockIdx.x;
     int lo = 0, hi = a.n;
@@ -125,22 +141,148 @@ __global__ __launch_bounds__(TB) void adam_kernel(const AdamArgs a) {
         const int64_t e = Ch::elem(base, q, threadIdx.x);
         if (e >= N) continue;
         if (vec && e + 4 <= N) {
-            float4 pv = ld4(p + e), mv = ld4(m + e), vv = ld4(v + e);
-            adam4(pv, ld4(g + e), mv, vv, k);
+            float4 pv = ld4(p + e), mv = ld4(m + e), vv = ld4(v + e), gv = ld4(g + e);
+            if (CLIP) gv = coef * gv;
+            adam4(pv, gv, mv, vv, k);
             st4(p + e, pv);
             st4(m + e, mv);
             st4(v + e, vv);
         } else {
             const int64_t end = e + 4 < N ? e + 4 : N;
             for (int64_t i = e; i < end; ++i) {
-                float pi = p[i], mi = m[i], vi = v[i];
-                adam1(pi, g[i], mi, vi, k);
+                float pi = p[i], mi = m[i], vi = v[i], gi = g[i];
+                if (CLIP) gi = coef * gi;
+                adam1(pi, gi, mi, vi, k);
                 p[i] = pi;
                 m[i] = mi;
                 v[i] = vi;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(TB) void adam_kernel(const AdamArgs a) { adam_body<false>(a, nullptr); }
+__global__ __launch_bounds__(TB) void adam_clip_kernel(const AdamArgs a, const double* __restrict__ stats) { adam_body<true>(a, stats); }
+static_assert(sizeof(AdamArgs) + sizeof(double*) <= 4096, "the Adam table and the stats pointer must fit the kernel-argument segment");
+
+// ---- L3, L3s.  The table of gradients travels by value like AdamArgs (64 x 16 bytes + 65 prefix sums).
+constexpr int NNORM = 2;                                     // the sum of squares, the count of non-finite elements
+struct GradArgs {
+    float* g[DEQSCI_ADAM_MAX_TENSORS];
+    int64_t numel[DEQSCI_ADAM_MAX_TENSORS];
+    uint32_t first[DEQSCI_ADAM_MAX_TENSORS + 1];             // as AdamArgs::first
+    int n;
+};
+static_assert(sizeof(GradArgs) + 3 * sizeof(void*) <= 4096, "the gradient table must fit the kernel-argument segment");
+
+__device__ __forceinline__ int table_find(const uint32_t* first, int n, uint32_t b) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= b) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// (a) part: the table's first chunk partial.  A float squared in double is exact (24-bit significands), so sq4's fma IS square + sum.
+__global__ __launch_bounds__(TB) void grad_norm_chunk_kernel(const GradArgs a, double* __restrict__ part) {
+    __shared__ double wsum[NW][NNORM];
+    const uint32_t b = blockIdx.x;
+    const int lo = table_find(a.first, a.n, b);
+    const float* __restrict__ g = a.g[lo];
+    const int64_t N = a.numel[lo], base = (int64_t)(b - a.first[lo]) * CHUNK;
+    const bool vec = aligned16_all(g);
+    double acc[NNORM] = {0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < PER_THREAD; ++q) {
+        const int64_t e = Ch::elem(base, q, threadIdx.x);
+        if (e >= N) continue;                                 // (what lies beyond adds +0.0 in the restated order: the same bits)
+        const float4 t = load4(g, e, N, vec);                 // zeros beyond N: +0.0 to the sum, finite to the count
+        acc[0] = sq4(t, acc[0]);
+        acc[1] = (((acc[1] + bad(t.x)) + bad(t.y)) + bad(t.z)) + bad(t.w);
+    }
+    block_sums_to(acc, wsum, part + (int64_t)b * NNORM);
+}
+
+// (b) one workgroup = tensor blockIdx.x of the table; part and tsum: the table's first chunk partial and first tensor sum
+__global__ __launch_bounds__(TB) void grad_norm_fold_kernel(const GradArgs a, const double* __restrict__ part, double* __restrict__ tsum) {
+    __shared__ double wsum[NW][NNORM];
+    const int64_t c0 = a.first[blockIdx.x], c1 = a.first[blockIdx.x + 1];
+    double acc[NNORM] = {0.0, 0.0};
+    for (int64_t c = c0 + threadIdx.x; c < c1; c += TB) {
+#pragma unroll
+        for (int k = 0; k < NNORM; ++k) acc[k] += part[c * NNORM + k];
+    }
+    block_sums_to(acc, wsum, tsum + (int64_t)blockIdx.x * NNORM);
+}
+
+// (c) one workgroup.  The division and the square root in double are the correctly rounded ones.
+__global__ __launch_bounds__(TB) void grad_norm_final_kernel(const double* __restrict__ tsum, int64_t n, double max_norm, double* __restrict__ stats) {
+    for (int64_t i = threadIdx.x; i < n; i += TB) stats[3 + i] = sqrt(tsum[i * NNORM]);
+    if (threadIdx.x != 0) return;
+    double sum = 0.0, count = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        sum += tsum[i * NNORM];
+        count += tsum[i * NNORM + 1];
+    }
+    const double norm = sqrt(sum), c = max_norm / (norm + 1e-6);
+    stats[0] = norm;
+    stats[1] = (double)(float)(c >= 1.0 ? 1.0 : c);           // one rounding to fp32; a NaN stays NaN
+    stats[2] = count;
+}
+
+__global__ __launch_bounds__(TB) void grad_scale_kernel(const GradArgs a, const double* __restrict__ stats) {
+    if (stats[2] > 0.0) return;
+    const float coef = (float)stats[1];
+    if (coef == 1.0f) return;                                 // g * 1 is g
+    const uint32_t b = blockIdx.x;
+    const int lo = table_find(a.first, a.n, b);
+    float* __restrict__ g = a.g[lo];
+    const int64_t N = a.numel[lo], base = (int64_t)(b - a.first[lo]) * CHUNK;
+    const bool vec = aligned16_all(g);
+#pragma unroll
+    for (int q = 0; q < PER_THREAD; ++q) {
+        const int64_t e = Ch::elem(base, q, threadIdx.x);
+        if (e >= N) continue;
+        store4(g, e, N, vec, coef * load4(g, e, N, vec));
+    }
+}
+
+// A table of gradients out of entries[0..n): every entry checked (null, shape, alignment), the chunk prefix sums formed.  -> 0 or the error
+inline int grad_table(const deqsci_grad_entry* entries, int n, GradArgs& a, uint64_t& chunks) {
+    a.n = n;
+    chunks = 0;
+    for (int i = 0; i < DEQSCI_ADAM_MAX_TENSORS; ++i) {
+        if (i >= n) {
+            a.g[i] = nullptr;
+            a.numel[i] = 0;
+            a.first[i + 1] = (uint32_t)chunks;
+            continue;
+        }
+        const deqsci_grad_entry& t = entries[i];
+        if (!t.grad) return DEQSCI_ERR_NULL;
+        if (t.numel <= 0 || t.numel > ((int64_t)1 << 40)) return DEQSCI_ERR_SHAPE;
+        if (misaligned(t.grad, 4)) return DEQSCI_ERR_ALIGN;
+        a.g[i] = t.grad;
+        a.numel[i] = t.numel;
+        a.first[i] = (uint32_t)chunks;
+        chunks += (uint64_t)ceil_div(t.numel, CHUNK);
+        if (chunks >= ((uint64_t)1 << 31)) return DEQSCI_ERR_UNSUPPORTED;      // the grid's x extent
+        a.first[i + 1] = (uint32_t)chunks;
+    }
+    return 0;
+}
+
+// the chunks of all n tensors, or -1 where an entry is invalid or the workspace would pass 2^40 chunks
+inline int64_t grad_chunks(const deqsci_grad_entry* entries, int64_t n) {
+    if (n < 0 || n > ((int64_t)1 << 24) || (n > 0 && !entries)) return -1;
+    int64_t chunks = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (entries[i].numel <= 0 || entries[i].numel > ((int64_t)1 << 40)) return -1;
+        chunks += ceil_div(entries[i].numel, CHUNK);
+        if (chunks > ((int64_t)1 << 40)) return -1;
+    }
+    return chunks;
 }
 
 }  // namespace train
@@ -172,11 +314,12 @@ int deqsci_mse_stats_grad_f32(const float* rec, const float* gt, float* grad, do
     return launch_status();
 }
 
-int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
-                         float one_minus_beta2, float eps, deqsci_stream_t stream) {
+static int adam_launch(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                       float eps, const double* stats, bool clip, deqsci_stream_t stream) {
     if (n_tensors < 0 || n_tensors > DEQSCI_ADAM_MAX_TENSORS) return DEQSCI_ERR_UNSUPPORTED;
     if (n_tensors == 0) return 0;
-    if (!entries) return DEQSCI_ERR_NULL;
+    if (!entries || (clip && !stats)) return DEQSCI_ERR_NULL;
+    if (clip && misaligned(stats, 8)) return DEQSCI_ERR_ALIGN;
     train::AdamArgs a;
     a.n = n_tensors;
     a.beta1 = beta1;
@@ -199,14 +342,92 @@ int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float 
         if (overlaps(t.param, bytes, t.grad, bytes) || overlaps(t.param, bytes, t.exp_avg, bytes) || overlaps(t.param, bytes, t.exp_avg_sq, bytes) ||
             overlaps(t.exp_avg, bytes, t.exp_avg_sq, bytes) || overlaps(t.grad, bytes, t.exp_avg, bytes) || overlaps(t.grad, bytes, t.exp_avg_sq, bytes))
             return DEQSCI_ERR_UNSUPPORTED;
+        if (clip && (overlaps(stats, 24, t.param, bytes) || overlaps(stats, 24, t.exp_avg, bytes) || overlaps(stats, 24, t.exp_avg_sq, bytes) ||
+                     overlaps(stats, 24, t.grad, bytes)))
+            return DEQSCI_ERR_UNSUPPORTED;
         a.t[i] = t;
         a.first[i] = (uint32_t)chunks;
         chunks += (uint64_t)ceil_div(t.numel, train::CHUNK);
         if (chunks >= ((uint64_t)1 << 31)) return DEQSCI_ERR_UNSUPPORTED;      // the grid's x extent
         a.first[i + 1] = (uint32_t)chunks;
     }
-    hipLaunchKernelGGL(train::adam_kernel, dim3((unsigned)chunks), dim3(TB), 0, static_cast<hipStream_t>(stream), a);
+    if (clip)
+        hipLaunchKernelGGL(train::adam_clip_kernel, dim3((unsigned)chunks), dim3(TB), 0, static_cast<hipStream_t>(stream), a, stats);
+    else
+        hipLaunchKernelGGL(train::adam_kernel, dim3((unsigned)chunks), dim3(TB), 0, static_cast<hipStream_t>(stream), a);
     return launch_status();
+}
+
+int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
+                         float one_minus_beta2, float eps, deqsci_stream_t stream) {
+    return adam_launch(entries, n_tensors, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, nullptr, false, stream);
+}
+
+int deqsci_adam_step_clipped_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
+                                 float one_minus_beta2, float eps, const double* stats, deqsci_stream_t stream) {
+    return adam_launch(entries, n_tensors, beta1, one_minus_beta1, beta2, one_minus_beta2, eps, stats, true, stream);
+}
+
+size_t deqsci_grad_norm_workspace_bytes(const deqsci_grad_entry* entries, int64_t n_tensors) {
+    const int64_t chunks = train::grad_chunks(entries, n_tensors);
+    if (chunks < 0) return 0;
+    return (size_t)((chunks + n_tensors) * train::NNORM) * sizeof(double);
+}
+
+int deqsci_grad_norm_f32(const deqsci_grad_entry* entries, int64_t n_tensors, double max_norm, double* stats, void* workspace,
+                         deqsci_stream_t stream) {
+    if (n_tensors < 0 || n_tensors > ((int64_t)1 << 24)) return DEQSCI_ERR_SHAPE;
+    if (!stats || (n_tensors > 0 && (!entries || !workspace))) return DEQSCI_ERR_NULL;
+    if (!(max_norm >= 0.0)) return DEQSCI_ERR_UNSUPPORTED;
+    if (misaligned(stats, 8) || misaligned(workspace, 8)) return DEQSCI_ERR_ALIGN;
+    // every table is checked before the first launch
+    const int T = DEQSCI_ADAM_MAX_TENSORS;
+    train::GradArgs a;
+    uint64_t chunks = 0;
+    for (int64_t lo = 0; lo < n_tensors; lo += T)
+        if (int e = train::grad_table(entries + lo, (int)(n_tensors - lo < T ? n_tensors - lo : T), a, chunks)) return e;
+    const int64_t total_chunks = train::grad_chunks(entries, n_tensors);
+    if (total_chunks < 0) return DEQSCI_ERR_SHAPE;
+    const int64_t stats_bytes = (3 + n_tensors) * 8, ws_bytes = (total_chunks + n_tensors) * train::NNORM * 8;
+    if (overlaps(stats, stats_bytes, workspace, ws_bytes)) return DEQSCI_ERR_UNSUPPORTED;
+    for (int64_t i = 0; i < n_tensors; ++i)
+        if (overlaps(stats, stats_bytes, entries[i].grad, entries[i].numel * 4) || overlaps(workspace, ws_bytes, entries[i].grad, entries[i].numel * 4))
+            return DEQSCI_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    double* tsum = part + total_chunks * train::NNORM;
+    int64_t chunk0 = 0;
+    for (int64_t lo = 0; lo < n_tensors; lo += T) {
+        const int n = (int)(n_tensors - lo < T ? n_tensors - lo : T);
+        train::grad_table(entries + lo, n, a, chunks);
+        hipLaunchKernelGGL(train::grad_norm_chunk_kernel, dim3((unsigned)chunks), dim3(TB), 0, st, a, part + chunk0 * train::NNORM);
+        if (int e = launch_status()) return e;
+        hipLaunchKernelGGL(train::grad_norm_fold_kernel, dim3((unsigned)n), dim3(TB), 0, st, a, part + chunk0 * train::NNORM, tsum + lo * train::NNORM);
+        if (int e = launch_status()) return e;
+        chunk0 += (int64_t)chunks;
+    }
+    hipLaunchKernelGGL(train::grad_norm_final_kernel, dim3(1), dim3(TB), 0, st, tsum, n_tensors, max_norm, stats);
+    return launch_status();
+}
+
+int deqsci_grad_scale_f32(const deqsci_grad_entry* entries, int64_t n_tensors, const double* stats, deqsci_stream_t stream) {
+    if (n_tensors < 0 || n_tensors > ((int64_t)1 << 24)) return DEQSCI_ERR_SHAPE;
+    if (n_tensors == 0) return 0;
+    if (!entries || !stats) return DEQSCI_ERR_NULL;
+    if (misaligned(stats, 8)) return DEQSCI_ERR_ALIGN;
+    const int T = DEQSCI_ADAM_MAX_TENSORS;
+    train::GradArgs a;
+    uint64_t chunks = 0;
+    for (int64_t lo = 0; lo < n_tensors; lo += T)
+        if (int e = train::grad_table(entries + lo, (int)(n_tensors - lo < T ? n_tensors - lo : T), a, chunks)) return e;
+    for (int64_t i = 0; i < n_tensors; ++i)
+        if (overlaps(stats, 24, entries[i].grad, entries[i].numel * 4)) return DEQSCI_ERR_UNSUPPORTED;
+    for (int64_t lo = 0; lo < n_tensors; lo += T) {
+        train::grad_table(entries + lo, (int)(n_tensors - lo < T ? n_tensors - lo : T), a, chunks);
+        hipLaunchKernelGGL(train::grad_scale_kernel, dim3((unsigned)chunks), dim3(TB), 0, static_cast<hipStream_t>(stream), a, stats);
+        if (int e = launch_status()) return e;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@ Deviations from the reference, all of them where it could not run here or would 
     this run wrote (none yet: FileNotFoundError).
 loss_function="device" (this build's): deqsci_amd.autograd.mse_loss_stats - loss, gradient, NaN check and the batch PSNR out of ONE pass
 over the reconstruction and ONE read-back of three float64 words per step; nothing else copies the reconstruction to the host.
+clip_grad_norm=MAX (this build's, off by default; the reference trains without clipping): the global gradient norm is clipped to MAX and a
+step whose gradient holds a NaN or an Inf is skipped (deqsci_amd.optim), at the cost of one second read-back of three words per step.
 """
 import json
 import math
@@ -27,6 +29,7 @@ import torch
 
 from . import autograd as _ag
 from . import checkpoint, harness, operators
+from . import optim as _optim
 from . import vjp as _vjp
 
 TrainStep = namedtuple("TrainStep", "epoch step loss psnr lr nonfinite")
@@ -143,16 +146,23 @@ def train_solver_sci(single_iterate_solver, train_dataloader, optimizer,
                      use_dataparallel=False, scheduler=None,
                      print_every_n_steps=100, save_every_n_steps=1000, start_epoch=0,
                      test_dataloader=None, train_img_path=None, test_img_path=None, best_img_path=None,
-                     tflog_path=None, *, max_steps=None, on_step=None):
+                     tflog_path=None, *, max_steps=None, on_step=None, clip_grad_norm=None):
     """training/sci_equilibrium_training.py:28-150 (see the module's docstring for the deviations).  loss_function: a callable
     (rec, gt) -> loss, as nn.MSELoss() - loss.item() and the PSNR on the host, as the reference - or the string "device"
     (autograd.mse_loss_stats).  max_steps: stop after that many steps in all (the epoch it falls in ends there, with the epoch's
-    bookkeeping).  on_step: called with a TrainStep after every optimizer step.  -> the list of the TrainSteps."""
+    bookkeeping).  on_step: called with a TrainStep after every optimizer step.  clip_grad_norm: None, or the largest global gradient
+    norm - with a DeviceAdam its max_grad_norm is set (norm, clipping and step on the device, the statistics read back AFTER
+    optimizer.step()); with any other optimizer optim.clip_grad_norm_ runs before the step and optimizer.step() is not called where the
+    gradient is not finite.  The jsonl row then gains main/grad_norm and main/skipped, the print line the norm, the epoch's end the
+    count of skipped steps.  -> the list of the TrainSteps."""
     if use_dataparallel:
         raise NotImplementedError("train_solver_sci: training is single-device in this build (use_dataparallel=True)")
     if isinstance(loss_function, str) and loss_function != "device":
         raise ValueError(f"loss_function={loss_function!r}: a callable, or the string 'device'")
     device_loss = isinstance(loss_function, str)
+    fused_clip = clip_grad_norm is not None and isinstance(optimizer, _optim.DeviceAdam)
+    if fused_clip:
+        optimizer.max_grad_norm = float(clip_grad_norm)
     device = next(single_iterate_solver.parameters()).device
     start_time = time.time()
     cur_nimg = 0
@@ -185,6 +195,7 @@ def train_solver_sci(single_iterate_solver, train_dataloader, optimizer,
                 reload()
             reset_flag = False
             psnr_sum = 0
+            skipped_steps = 0
             for ii, sample_batch in enumerate(train_dataloader):
                 cur_nimg += sample_batch['gt'].size(0)
                 optimizer.zero_grad()
@@ -210,7 +221,20 @@ def train_solver_sci(single_iterate_solver, train_dataloader, optimizer,
                     reset_flag = True
                     break
                 loss.backward()
-                optimizer.step()
+                grad_norm, skipped = None, False
+                if clip_grad_norm is None:
+                    optimizer.step()
+                elif fused_clip:
+                    optimizer.step()
+                    grad_host = optimizer.last_grad_stats[:3].cpu()       # the step's second read-back, behind the Adam launch
+                    grad_norm, skipped = float(grad_host[0]), float(grad_host[2]) > 0
+                else:
+                    params = [p for group in optimizer.param_groups for p in group["params"]]
+                    grad_host = _optim.clip_grad_norm_(params, clip_grad_norm, return_stats=True)[:3].cpu()
+                    grad_norm, skipped = float(grad_host[0]), float(grad_host[2]) > 0
+                    if not skipped:
+                        optimizer.step()
+                skipped_steps += int(skipped)
                 if ii == 0:
                     previous_loss = loss_value
                 if device_loss:
@@ -221,12 +245,15 @@ def train_solver_sci(single_iterate_solver, train_dataloader, optimizer,
                 psnr_sum += PSNR
                 lr = optimizer.param_groups[0]['lr']
                 stats_dict = OrderedDict([('main/PSNR', PSNR), ('main/loss', loss_value), ('config/lr', lr), ('main/best_PSNR', best_psnr)])
+                if clip_grad_norm is not None:
+                    stats_dict['main/grad_norm'], stats_dict['main/skipped'] = grad_norm, int(skipped)
                 if log is not None:
                     log.write(json.dumps({"global_step": int(cur_nimg), "walltime": time.time() - start_time, **stats_dict}) + "\n")
                     log.flush()
                 if ii % print_every_n_steps == 0:
                     print("Epoch: " + str(epoch) + " Step: " + str(ii) + " Loss: " + str(np.float32(loss_value)) + " PSNR: %2.2f dB" % PSNR +
-                          " best PSNR (test): %2.2f dB" % best_psnr + " lr: %.8f" % lr, flush=True)
+                          " best PSNR (test): %2.2f dB" % best_psnr + " lr: %.8f" % lr +
+                          ("" if clip_grad_norm is None else " grad norm: %.4e" % grad_norm + (" (not finite: step skipped)" if skipped else "")), flush=True)
                 step = TrainStep(epoch, ii, loss_value, PSNR, lr, nonfinite)
                 history.append(step)
                 steps_done += 1
@@ -242,6 +269,8 @@ def train_solver_sci(single_iterate_solver, train_dataloader, optimizer,
                     break
             avg_psnr = psnr_sum / len(train_dataloader)
             print('avg PSNR in epoch %d: %.2f dB' % (epoch, avg_psnr))
+            if clip_grad_norm is not None:
+                print('skipped steps (gradient not finite) in epoch %d: %d' % (epoch, skipped_steps))
             if (previous_loss - loss_value) / previous_loss < -10.0 or np.isnan(loss_value):
                 reset_flag = True
             if scheduler is not None:

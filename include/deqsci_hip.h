@@ -672,6 +672,38 @@ typedef struct {
 int deqsci_adam_step_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
                          float one_minus_beta2, float eps, deqsci_stream_t stream);
 
+/* L3  the global gradient norm of n_tensors >= 0 fp32 tensors (ANY number), the clipping coefficient of torch's clip_grad_norm_ and the
+ *     count of non-finite elements, all left on the device.  entries: n_tensors records in HOST memory, read before the call returns
+ *     (tables of DEQSCI_ADAM_MAX_TENSORS tensors travel by value in the kernels' arguments, as L2's).  The order of summation is fixed:
+ *       1. one workgroup = one chunk of DEQSCI_TRAIN_CHUNK elements of one tensor: every element widened to double and squared there
+ *          (exact), the chunk summed in the stage-1 order of csrc/rows.hpp (4 float4 per thread), the non-finite elements counted beside;
+ *       2. a tensor's chunk partials in L1's stage-2 order (one workgroup per tensor: thread i adds chunks i, i + 256, ..., then the
+ *          workgroup's sum);
+ *       3. the tensors' sums one after the other in list order, in double, across the tables.
+ *     stats (3 + n_tensors float64, 8-byte aligned):
+ *       stats[0] = sqrt(sum);  stats[1] = coef = (float)c where c = max_norm / (stats[0] + 1e-6) in double and c >= 1 gives 1 (a NaN
+ *       stays NaN), stored as that fp32's value;  stats[2] = the number of non-finite elements;  stats[3 + i] = tensor i's own norm.
+ *     A NaN or Inf is counted and enters the sums as it is.  max_norm >= 0 (NaN: -4).  Gradients 4-byte aligned (16-byte aligned ones
+ *     are read as float4: the same sums), numel >= 1.  workspace = deqsci_grad_norm_workspace_bytes(entries, n_tensors) bytes (0 for
+ *     invalid entries), 8-byte aligned, no initialisation needed; stats and workspace must overlap neither each other nor a gradient (-4).
+ *     2 ceil(n_tensors / DEQSCI_ADAM_MAX_TENSORS) + 1 launches on `stream` (chunks and tensors per table, then one workgroup); no
+ *     atomics, no allocation, no host synchronisation, graph-capturable.
+ * L3s grad = grad * coef in place (one fp32 rounding, as clip_grad_norm_'s grad.mul_) for the listed tensors, with coef = stats[1] read on
+ *     the device; nothing is written where stats[2] > 0 (a non-finite gradient) or coef == 1 (the same bits).  One launch per table.
+ * L2c L2 with g' = g * coef (one fp32 rounding) in place of g, coef = stats[1] read on the device by every workgroup; where
+ *     stats[2] > 0 NOTHING is written for any tensor (param, exp_avg and exp_avg_sq stay untouched).  grad is not written.  With
+ *     coef == 1 the step's bits are L2's.  stats: 3 float64, 8-byte aligned, overlapping no tensor of the table (-4); the rest as L2. */
+typedef struct {
+    float* grad;
+    int64_t numel;
+} deqsci_grad_entry;
+size_t deqsci_grad_norm_workspace_bytes(const deqsci_grad_entry* entries, int64_t n_tensors);
+int deqsci_grad_norm_f32(const deqsci_grad_entry* entries, int64_t n_tensors, double max_norm, double* stats, void* workspace,
+                         deqsci_stream_t stream);
+int deqsci_grad_scale_f32(const deqsci_grad_entry* entries, int64_t n_tensors, const double* stats, deqsci_stream_t stream);
+int deqsci_adam_step_clipped_f32(const deqsci_adam_entry* entries, int n_tensors, float beta1, float one_minus_beta1, float beta2,
+                                 float one_minus_beta2, float eps, const double* stats, deqsci_stream_t stream);
+
 /* ---- training batches out of raw video (csrc/synth.hip): crop, augment and snapshot synthesis in one launch per 64 samples ----
  * Y1  pool: `pool_bytes` bytes of uint8 frames on the device, every video a contiguous (T,Hv,Wv) block.  table: bsz rows of
  *     DEQSCI_SYNTH_ROW_WORDS int64 in HOST memory, read before the call returns (the rows travel by value in the kernel's arguments,

@@ -11,9 +11,12 @@ HIP events after warm-up, the median of the repeats.  The parts of a step:
     optimizer  optimizer.step()
 and L1 / L2 alone against what they replace: the composed torch expressions for loss, gradient, clamped squared error and non-finite count,
 and torch.optim.Adam.step() (its default multi-tensor form and foreach=False) on the same parameter tensors.
+Clipping by global norm (--parts clip), on each denoiser's parameter list: L3 alone (_hip.grad_norm); L2c against L2 (_hip.adam_step with and
+without the statistics); and the clipped optimizer step DeviceAdam(max_grad_norm=...).step() against torch.nn.utils.clip_grad_norm_ followed
+by DeviceAdam.step() on the same gradients in the same process, with the launches of each.
 Prints one line per (denoiser, batch, backend) and a JSON line.
 
-    python tools/train_bench.py [--denoisers SimpleCNN,ffdnet] [--batches 1,8] [--iters 30] [--reps 10] [--warmup 2]
+    python tools/train_bench.py [--denoisers SimpleCNN,ffdnet] [--batches 1,8] [--iters 30] [--reps 10] [--warmup 2] [--parts steps,kernels,clip]
 """
 import argparse
 import json
@@ -174,6 +177,48 @@ def kernels_alone(kind, bsz, reps, warmup):
     return out
 
 
+def clip_rows(kind, reps, warmup, max_norm=1e-3):
+    """max_norm far below the gradients' norm: the coefficient is below 1 in every repeat, for torch's in-place scaling too"""
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(5)
+    solver, _ = build_pipeline(kind, checkpoint.shipped(WEIGHTS[kind]), 3)
+    shapes = [p.shape for p in solver.parameters()]
+
+    def params():
+        ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=g)) for s in shapes]
+        for p in ps:
+            p.grad = torch.randn(p.shape, device=dev, generator=g)
+        return ps
+    ps = params()
+    grads = [p.grad for p in ps]
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    stats = torch.empty(3 + len(ps), device=dev, dtype=torch.float64)
+    ws = _hip.grad_norm_workspace(grads)
+    out = {"denoiser": kind, "tensors": len(ps), "weights": sum(p.numel() for p in ps), "max_norm": max_norm,
+           "l3_launches": _hip.grad_norm_launches(len(ps))}
+    out["l3_ms"] = timed(lambda: _hip.grad_norm(grads, max_norm, stats=stats, workspace=ws), reps, warmup)
+    with torch.no_grad():
+        out["l2_ms"] = timed(lambda: _hip.adam_step(ps, grads, ms, vs, 1, 1e-6, (0.9, 0.999), 1e-8), reps, warmup)
+        out["l2c_ms"] = timed(lambda: _hip.adam_step(ps, grads, ms, vs, 1, 1e-6, (0.9, 0.999), 1e-8, stats=stats), reps, warmup)
+    fused = DeviceAdam(params(), lr=1e-6, max_grad_norm=max_norm)
+    pt = params()
+    plain = DeviceAdam(pt, lr=1e-6)
+
+    def composed():
+        torch.nn.utils.clip_grad_norm_(pt, max_norm)
+        plain.step()
+    out["clipped_step_ms"] = timed(fused.step, reps, warmup)
+    out["clipped_step_launches"] = fused.last_launches
+    out["torch_clip_plus_step_ms"] = timed(composed, reps, warmup)
+    out["torch_clip_ms"] = timed(lambda: torch.nn.utils.clip_grad_norm_(pt, max_norm), reps, warmup)
+    # the launches of torch's clip_grad_norm_, counted by the profiler (one step, behind the timed ones)
+    with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) as prof:
+        torch.nn.utils.clip_grad_norm_(pt, max_norm)
+        torch.cuda.synchronize()
+    out["torch_clip_launches"] = sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--denoisers", default="SimpleCNN,ffdnet")
@@ -181,16 +226,26 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--parts", default="steps,kernels,clip")
     a = ap.parse_args()
-    out = {"H": 256, "W": 256, "B": 8, "and_maxiters": a.iters, "reps": a.reps, "steps": [], "kernels": []}
+    parts = a.parts.split(",")
+    out = {"H": 256, "W": 256, "B": 8, "and_maxiters": a.iters, "reps": a.reps, "steps": [], "kernels": [], "clip": []}
     for kind in a.denoisers.split(","):
+        if "clip" in parts:
+            c = clip_rows(kind, a.reps, a.warmup)
+            out["clip"].append(c)
+            print(f"{kind:9s} clip {c['tensors']} tensors, {c['weights']} weights: L3 {c['l3_ms']:.4f} ms ({c['l3_launches']} launches);   L2c {c['l2c_ms']:.4f} ms vs L2 "
+                  f"{c['l2_ms']:.4f} ms;   clipped DeviceAdam.step {c['clipped_step_ms']:.4f} ms ({c['clipped_step_launches']} launches) vs torch clip_grad_norm_ + "
+                  f"DeviceAdam.step {c['torch_clip_plus_step_ms']:.4f} ms (clip_grad_norm_ alone {c['torch_clip_ms']:.4f} ms, {c['torch_clip_launches']} launches)", flush=True)
         for bsz in (int(b) for b in a.batches.split(",")):
-            for backend in ("autograd", "device"):
+            for backend in (("autograd", "device") if "steps" in parts else ()):
                 r = step_parts(kind, backend, bsz, a.iters, a.reps, a.warmup)
                 out["steps"].append(r)
                 print(f"{kind:9s} bsz {bsz} {backend:8s}: step {r['total_ms']:9.2f} ms = solve {r['solve_ms']:8.2f} + taped {r['taped_ms']:7.2f} + hook "
                       f"{r['hook_ms']:8.2f} + param {r['param_ms']:7.2f} + glue {r['glue_ms']:6.3f} + optimizer {r['optimizer_ms']:6.3f}   "
                       f"(implicit {r['implicit_backward']}, parameter {r['parameter_backward']}; loss {r['loss']:.5f})", flush=True)
+            if "kernels" not in parts:
+                continue
             k = kernels_alone(kind, bsz, a.reps, a.warmup)
             out["kernels"].append(k)
             print(f"{kind:9s} bsz {bsz} alone   : L1 {k['l1_ms']:.4f} ms ({k['l1_gbs']:.0f} GB/s) vs composed torch {k['l1_torch_ms']:.4f} ms;   L2 {k['tensors']} tensors "
