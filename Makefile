@@ -3,7 +3,7 @@ HIPCC      ?= /opt/rocm/bin/hipcc
 ARCH       ?= gfx950
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iinclude -Ideqsci_amd/csrc -Wall -Wno-unused-function
 LIB        := deqsci_amd/lib/libdeqsci_hip.so
-SRCS       := deqsci_amd/csrc/conv_w16.hip deqsci_amd/csrc/sci_ops.hip deqsci_amd/csrc/sci_grad.hip deqsci_amd/csrc/anderson.hip deqsci_amd/csrc/epilogue.hip deqsci_amd/csrc/ffdnet_edges.hip deqsci_amd/csrc/winograd.hip deqsci_amd/csrc/winograd44.hip deqsci_amd/csrc/conv_s16.hip deqsci_amd/csrc/ssim.hip deqsci_amd/csrc/trace.hip deqsci_amd/csrc/tv.hip deqsci_amd/csrc/vjp.hip deqsci_amd/csrc/jacobian.hip deqsci_amd/csrc/broyden.hip deqsci_amd/csrc/epsilon2.hip deqsci_amd/csrc/wgrad.hip deqsci_amd/csrc/wgrad_bn.hip deqsci_amd/csrc/realsn.hip deqsci_amd/csrc/bn_train.hip deqsci_amd/csrc/train.hip deqsci_amd/csrc/synth.hip
+SRCS       := deqsci_amd/csrc/conv_w16.hip deqsci_amd/csrc/sci_ops.hip deqsci_amd/csrc/sci_grad.hip deqsci_amd/csrc/anderson.hip deqsci_amd/csrc/epilogue.hip deqsci_amd/csrc/ffdnet_edges.hip deqsci_amd/csrc/winograd.hip deqsci_amd/csrc/winograd44.hip deqsci_amd/csrc/conv_s16.hip deqsci_amd/csrc/ssim.hip deqsci_amd/csrc/trace.hip deqsci_amd/csrc/tv.hip deqsci_amd/csrc/vjp.hip deqsci_amd/csrc/jacobian.hip deqsci_amd/csrc/broyden.hip deqsci_amd/csrc/epsilon2.hip deqsci_amd/csrc/wgrad.hip deqsci_amd/csrc/wgrad_bn.hip deqsci_amd/csrc/realsn.hip deqsci_amd/csrc/bn_train.hip deqsci_amd/csrc/train.hip deqsci_amd/csrc/synth.hip deqsci_amd/csrc/noise.hip
 HDRS       := include/deqsci_hip.h deqsci_amd/csrc/common.hpp deqsci_amd/csrc/rows.hpp deqsci_amd/csrc/wgrad.hpp
 ORACLE_LIB := oracle/libdeqsci_oracle.so
 

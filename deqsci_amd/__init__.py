@@ -12,6 +12,7 @@ from .engine import DEQSCIEngine, sigma_schedule  # noqa: F401
 from .networks import FFDNet, DnCNN  # noqa: F401
 from .autograd import mse_loss_stats  # noqa: F401
 from .optim import DeviceAdam, clip_grad_norm_  # noqa: F401
+from .noise import SensorNoise, normal_host, philox4x32_10  # noqa: F401
 from .training import (SCITrainingDatasetSubset, TrainStep, TrainingConfig, configure_training, load_mat,  # noqa: F401
                        train_solver_sci)
 

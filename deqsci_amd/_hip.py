@@ -23,6 +23,7 @@ _lib = None
 
 _i64, _int, _f32, _ptr = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
 _f64 = ctypes.c_double
+_u64 = ctypes.c_uint64
 
 # name -> argtypes; the single source of truth for tests/test_cabi_exports.py too
 SIGNATURES = {
@@ -103,6 +104,9 @@ SIGNATURES = {
     "deqsci_grad_scale_f32": [_ptr, _i64, _ptr, _ptr],
     "deqsci_synth_batch_u8": [_ptr, _i64, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr],
     "deqsci_rgb_to_gray_u8": [_ptr, _ptr, _i64, _ptr],
+    "deqsci_philox_words_u32": [_ptr, _ptr, _i64, _i64, _u64, _ptr],
+    "deqsci_philox_normal_f32": [_ptr, _ptr, _i64, _i64, _u64, _ptr],
+    "deqsci_sensor_noise_f32": [_ptr, _ptr, _ptr, _i64, _i64, _u64, _f32, _f32, _int, _f32, _ptr],
     "deqsci_event_create": [ctypes.POINTER(_ptr)],
     "deqsci_event_destroy": [_ptr],
     "deqsci_event_elapsed_ms": [_ptr, _ptr, ctypes.POINTER(_f32)],
@@ -2221,6 +2225,67 @@ def rgb_to_gray(rgb, out=None):
         raise DeqsciHipError("rgb_to_gray: out must be a contiguous uint8 tensor of rgb's leading shape on rgb's device")
     with _dev(rgb):
         _check(load().deqsci_rgb_to_gray_u8(rgb.data_ptr(), out.data_ptr(), out.numel(), _stream()), "rgb_to_gray")
+    return out
+
+
+# ----------------------------------------------------------------------------- random source and sensor noise (csrc/noise.hip)
+NOISE_MAX_ROWS = 64      # DEQSCI_NOISE_MAX_ROWS: samples per launch
+_U64 = (1 << 64) - 1
+
+
+def _seq_array(seq, what):
+    """The per-sample sequence numbers as a contiguous uint64 HOST array (python ints of any size below 2^64, or an integer array)."""
+    import numpy as np
+    vals = [int(v) for v in np.asarray(seq, dtype=object).reshape(-1)]
+    if any(v < 0 or v > _U64 for v in vals):
+        raise DeqsciHipError(f"{what}: sequence numbers must lie in 0 .. 2^64 - 1")
+    return np.asarray(vals, dtype=np.uint64)
+
+
+def _noise_out(out, shape, dtype, device, what):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and out.is_contiguous() and tuple(out.shape) == tuple(shape)):
+        raise DeqsciHipError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on a HIP device")
+    return out
+
+
+def philox_words(seq, n, seed, device="cuda", out=None):
+    """N0: the raw Philox4x32-10 words of the groups that serve n elements per sample -> (bsz, ceil(n / 4), 4) int32 holding the uint32 bit
+    patterns (view them with .cpu().numpy().view(numpy.uint32)).  seq: bsz sequence numbers on the HOST; seed: the 64-bit key."""
+    rows = _seq_array(seq, "philox_words")
+    bsz, n = rows.size, int(n)
+    out = _noise_out(out, (bsz, -(-n // 4), 4), torch.int32, device, "philox_words")
+    with _dev(out):
+        _check(load().deqsci_philox_words_u32(out.data_ptr(), rows.ctypes.data, bsz, n, int(seed) & _U64, _stream()), "philox_words")
+    return out
+
+
+def philox_normal(seq, n, seed, device="cuda", out=None):
+    """N1: (bsz, n) fp32 standard normals; element e of the sample with sequence number seq[k] is a function of (seed, seq[k], e) alone."""
+    rows = _seq_array(seq, "philox_normal")
+    bsz, n = rows.size, int(n)
+    out = _noise_out(out, (bsz, n), torch.float32, device, "philox_normal")
+    with _dev(out):
+        _check(load().deqsci_philox_normal_f32(out.data_ptr(), rows.ctypes.data, bsz, n, int(seed) & _U64, _stream()), "philox_normal")
+    return out
+
+
+def sensor_noise(y, seq, seed, sigma, gain, bits, full_scale, out=None):
+    """N2: y (bsz, ...) -> y + sqrt(gain max(y, 0) + sigma^2) normal, quantised to `bits` bits over [0, full_scale] where bits > 0, in the
+    order of operations include/deqsci_hip.h states.  out: None (a new tensor) or y itself (in place)."""
+    rows = _seq_array(seq, "sensor_noise")
+    bsz = rows.size
+    _p(y, "y")
+    if y.dim() < 1 or y.shape[0] != bsz:
+        raise DeqsciHipError(f"sensor_noise: y {tuple(y.shape)} does not hold {bsz} samples")
+    n = y.numel() // bsz if bsz else 1
+    out = _noise_out(out, y.shape, torch.float32, y.device, "sensor_noise")
+    if out.device != y.device:
+        raise DeqsciHipError("sensor_noise: out must be on y's device")
+    with _dev(y):
+        _check(load().deqsci_sensor_noise_f32(y.data_ptr(), out.data_ptr(), rows.ctypes.data, bsz, n, int(seed) & _U64, float(sigma), float(gain),
+                                              int(bits), float(full_scale), _stream()), "sensor_noise")
     return out
 
 

@@ -34,6 +34,10 @@ device): --and_maxiters iterations of two f-calls at most, stopped when |x_new -
 `--eps2_lam` is the regulariser of its denominator.  The generic solver path too: --snapshots / --trace are refused.
 `--solver picard` (this build's) runs the plain iteration z <- f(z) (forward_iteration) on the engine, --and_maxiters iterations at most;
 --snapshots / --trace work with it.
+`--meas_noise_sigma S --meas_noise_gain G --meas_bits N --meas_full_scale F --noise_seed K` (this build's) put read noise (S grey levels),
+shot noise and an N-bit ADC on the measurements (deqsci_amd.noise): the test measurements in inference - one line says so -, the
+synthesised training measurements with --inference False --trainvideos; refused with --trainpath (python -m deqsci_amd.synth write makes
+a noisy directory).  The reference's --sigma stays ignored.
 """
 import argparse
 import os
@@ -46,6 +50,7 @@ from . import checkpoint, distributed
 from .harness import (SCITestDataset, clip_line, evaluate, jacobian_document, png_payloads, print_horizons, print_jacobian_totals,
                       solver_line, trace_document, write_png)
 from .networks import DnCNN, FFDNet
+from .noise import add_noise_arguments, noise_from_arguments
 from .operators import A_torch_, At_torch_
 from .broyden import broyden_fixed_point
 from .epsilon2 import epsilon2
@@ -207,6 +212,12 @@ def parser():
     train.add_argument('--clip_grad_norm', type=float, default=None,
                        help="(this build) clip the global gradient norm to this value and skip a step whose gradient is not finite "
                             "(deqsci_amd.optim: on the device with --train_backend device); default: no clipping, as the reference")
+    add_noise_arguments(p.add_argument_group(
+        "sensor noise (this build)",
+        "read noise, shot noise and an ADC on the measurements (deqsci_amd.noise, csrc/noise.hip): in inference on the test measurements, "
+        "measurement m of clip k under the sequence number (k << 32) | m whatever the batching or the number of GPUs; with --inference False "
+        "--trainvideos on the training measurements (the evaluation on --testpath stays clean).  Refused with --trainpath: write a noisy "
+        "directory with python -m deqsci_amd.synth write"))
     ignored = p.add_argument_group("accepted for command-line compatibility, unused")
     ignored.add_argument('--etainit', type=float, default=0.9)
     ignored.add_argument('--sigma', type=int, default=0)
@@ -247,9 +258,12 @@ def train(args):
         pool = synth.VideoPool(synth.list_videos(args.trainvideos), dev)
         mask = synth.load_mask(args.trainmask, args.patch_size, args.patch_size, args.frames)
         dataloader = synth.SynthTrainLoader(pool, mask, args.batch_size, args.patches_per_epoch, args.patch_size, args.patch_size, args.frames,
-                                            seed=0 if args.seed is None else args.seed, start_epoch=start_epoch, augment=synth.parse_augment(args.augment))
+                                            seed=0 if args.seed is None else args.seed, start_epoch=start_epoch, noise=noise_from_arguments(args, args.seed),
+                                            augment=synth.parse_augment(args.augment))
         print(f"training from {len(pool)} videos ({pool.nbytes / 1e6:.1f} MB on {dev}): {len(dataloader)} batches of {args.batch_size} patches "
               f"{args.patch_size}x{args.patch_size}x{args.frames} per epoch")
+        if dataloader.noise is not None:
+            print(f"sensor noise on the training measurements: {dataloader.noise.describe(args.frames)}")
     opts = {}
     if args.conv64 != 'auto':
         opts["conv64"] = args.conv64
@@ -300,6 +314,9 @@ def run(args):
             if args.solver != 'anderson':
                 print(solver_line(deq))
         os.makedirs(args.savepath, exist_ok=True)
+    noise = noise_from_arguments(args, args.seed)
+    if noise is not None and rank == 0:
+        print(f"sensor noise on the test measurements: {noise.describe()}")
     images = {}
     ssim = bool(args.ssim or args.ssim_mode)
 
@@ -313,7 +330,7 @@ def run(args):
                             ssim=ssim, ssim_mode=args.ssim_mode or "same", init=args.init_point,
                             method="deq" if args.baseline is None else args.baseline,
                             **({"snapshots": args.snapshots, "trace": bool(args.trace)} if (args.snapshots is not None or args.trace) else {}),
-                            **({} if jac is None else {"jacobian": jac}))
+                            **({} if jac is None else {"jacobian": jac}), **({} if noise is None else {"noise": noise}))
     dt = time.time() - t0
     if rank == 0:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
@@ -347,6 +364,13 @@ def main(argv=None):
     if args.denoiser not in SHIPPED and args.denoiser not in NO_DEFAULT:
         raise NotImplementedError('unknown denoiser!')
     training = str(args.inference).lower() in ('false', '0', '')
+    try:
+        noisy = noise_from_arguments(args, args.seed) is not None
+    except ValueError as e:
+        p.error(f"sensor noise: {e}")
+    if training and noisy and not args.trainvideos:
+        p.error("the sensor-noise flags act on the samples --trainvideos synthesises; a --trainpath directory holds its measurements already: "
+                "write a noisy one with python -m deqsci_amd.synth write --meas_noise_sigma ... and train on that")
     if training:
         if args.trainvideos and args.trainpath:
             p.error("--trainvideos and --trainpath exclude one another: one source of training samples")

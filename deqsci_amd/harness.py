@@ -303,6 +303,21 @@ def _start(init, y, Phi, Phi_sum):
     raise ValueError(f"init must be 'At' or 'gaptv', got {init!r}")
 
 
+def noise_seq(clip_index, measurement):
+    """The sequence number a scored measurement is noised under: (position of its clip in evaluate's order << 32) | measurement index."""
+    return (int(clip_index) << 32) | int(measurement)
+
+
+def _noisy(noise, y, seqs, B):
+    """The measurements y (M,H,W) through the sensor model (noise.SensorNoise), measurement i under seqs[i]: done once, on the full set
+    and before anything reads y, so what a measurement becomes depends on (seed, clip, measurement) only - not on how the harness batches
+    or shards.  None or a disabled model: y itself."""
+    if noise is None or not noise.enabled or y.shape[0] == 0:
+        return y
+    with torch.no_grad():
+        return noise.apply(y, seqs, frames=B)
+
+
 def _shard_start(M, group):
     """Index of the first of M measurements that this rank reconstructs (distributed.sharded_reconstruct); 0 without a process group."""
     if not distributed._active(group):
@@ -318,7 +333,7 @@ def _check_method(method, init):
 
 
 def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None, ssim=False, ssim_mode="same", init="At", method="deq",
-                     snapshots=None, trace=False, jacobian=None):
+                     snapshots=None, trace=False, jacobian=None, noise=None, clip_index=0):
     """All scored measurements of one clip through `deep_eq_module.forward(y, Phi, Phi_sum, initial_point=, train_flag=False)`.
     batch=True: one call with y (M,H,W) and the shared mask (1,H,W,B); batch=False: M calls of batch 1 (the reference's
     schedule).  With a process group the measurements are sharded over its ranks and all-gathered.  ssim=True: also the
@@ -328,13 +343,16 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
     (DEQSCIEngine.reconstruct); trace=True: ClipResult.trace = PSNR and residual of every f-call, per measurement.
     jacobian=dict(n_iters=, window=, seed=): ClipResult.jacobian = the local Lipschitz constant and spectral radius of f and the Lipschitz
     constant of the noise predictor at every measurement's reconstruction (DEQFixedPoint.jacobian_report, outside the timed part's meaning:
-    it is added to `seconds`)."""
+    it is added to `seconds`).
+    noise: a noise.SensorNoise (this build's); measurement m goes through it under the sequence number noise_seq(clip_index, m) before
+    the starting point, GAP-TV or anything else reads it; the score is against the clean ground truth."""
     import time
     clip = as_clip(clip)
     Phi = clip['mask'].to(device)[None].contiguous()                  # (1,H,W,B)
     B = Phi.shape[-1]
     ids = scored_measurements(clip['file'], clip['meas'].shape[-1])
     y = clip['meas'].to(device).permute(2, 0, 1)[ids].contiguous()    # (M,H,W)
+    y = _noisy(noise, y, [noise_seq(clip_index, m) for m in ids], B)
     Phi_sum = operators.phi_sum(Phi)
     _check_method(method, init)
     hz = _Horizons(deep_eq_module, snapshots, trace, method)
@@ -379,19 +397,21 @@ def reconstruct_clip(deep_eq_module, clip, device="cuda", batch=True, group=None
 
 
 def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None, ssim=False, ssim_mode="same", init="At", method="deq",
-                               snapshots=None, trace=False, jacobian=None):
+                               snapshots=None, trace=False, jacobian=None, noise=None, clip_index=0):
     """The scored measurements of SEVERAL clips of one frame size as ONE engine batch, every measurement with its own clip's mask
     ((M,H,W,B) masks: nothing couples the measurements of a batch - alpha, residual, the ranges of the split-fp16 activations are all per
     measurement - so a measurement's reconstruction is the one it gets in any other batch, bit for bit).  What the reference's loop over
     clips and measurements (training/sci_equilibrium_training.py:157,171) becomes when the device wants eight measurements per call: the
     three shipped clips (1 + 1 + 6 measurements) are one call.  -> [ClipResult] in the clips' order; a clip's `seconds` is its share of
-    the call by frames.  ssim=True: also the per-measurement SSIM; init, method, snapshots, trace and jacobian as in reconstruct_clip."""
+    the call by frames.  ssim=True: also the per-measurement SSIM; init, method, snapshots, trace and jacobian as in reconstruct_clip.
+    noise: as in reconstruct_clip, clip_index the position of the FIRST of these clips (the others follow it)."""
     import time
     clips = [as_clip(c) for c in clips]
     ids = [scored_measurements(c['file'], c['meas'].shape[-1]) for c in clips]
     Phi = torch.cat([c['mask'].to(device)[None].expand(len(i), -1, -1, -1) for c, i in zip(clips, ids)]).contiguous()      # (M,H,W,B)
     y = torch.cat([c['meas'].to(device).permute(2, 0, 1)[i] for c, i in zip(clips, ids)]).contiguous()                        # (M,H,W)
     B = Phi.shape[-1]
+    y = _noisy(noise, y, [noise_seq(clip_index + k, m) for k, i in enumerate(ids) for m in i], B)
     res = []
     _check_method(method, init)
     hz = _Horizons(deep_eq_module, snapshots, trace, method)
@@ -431,7 +451,7 @@ def reconstruct_clips_together(deep_eq_module, clips, device="cuda", group=None,
 
 
 def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_clip=None, ssim=False, ssim_mode="same", init="At",
-             method="deq", snapshots=None, trace=False, jacobian=None):
+             method="deq", snapshots=None, trace=False, jacobian=None, noise=None):
     """-> (mean over clips of the clip's mean PSNR, [ClipResult]).  batch: False = one measurement per call (the reference's schedule),
     True = a clip's measurements per call, "all" = the measurements of consecutive clips of one frame size per call
     (reconstruct_clips_together: the three shipped clips are ONE call of eight measurements).  ssim=True fills every ClipResult.ssim
@@ -439,7 +459,10 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
     init: the DEQ's start, "At" (default) or "gaptv"; method="gaptv": reconstruct by GAP-TV alone (deep_eq_module may be None).
     snapshots=(K1, ...) fills every ClipResult.snapshots (the clip at and_maxiters=K, out of the same run), trace=True every
     ClipResult.trace; `horizon_means(results)` is the mean over clips per horizon.  jacobian=dict(n_iters=, window=, seed=) fills every
-    ClipResult.jacobian (ValueError with method="gaptv")."""
+    ClipResult.jacobian (ValueError with method="gaptv").
+    noise: a noise.SensorNoise; scored measurement m of the clip at position k of `clips` is noised under the sequence number
+    (k << 32) | m, so its noisy value depends on (noise.seed, k, m) alone - not on `batch`, not on the number of ranks; method="gaptv"
+    sees the same noisy measurement."""
     _check_method(method, init)
     kw = dict(ssim=ssim, ssim_mode=ssim_mode, init=init, method=method)
     if jacobian is not None:
@@ -448,13 +471,17 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
         kw.update(jacobian=jacobian)
     if snapshots is not None or trace:
         kw.update(snapshots=snapshots, trace=trace)
+    noisy = noise is not None and noise.enabled
+
+    def at(k):
+        return dict(kw, noise=noise, clip_index=k) if noisy else kw
     results = []
     if batch == "all":
         pending = []
 
         def flush():
             if pending:
-                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group, **kw):
+                for r in reconstruct_clips_together(deep_eq_module, pending, device=device, group=group, **at(len(results))):
                     results.append(r)
                     if on_clip is not None:
                         on_clip(r)
@@ -466,8 +493,8 @@ def evaluate(deep_eq_module, clips, device="cuda", batch=True, group=None, on_cl
             pending.append(c)
         flush()
         return sum(r.mean_psnr for r in results) / len(results), results
-    for sample in clips:
-        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group, **kw)
+    for k, sample in enumerate(clips):
+        r = reconstruct_clip(deep_eq_module, sample, device=device, batch=batch, group=group, **at(k))
         results.append(r)
         if on_clip is not None:
             on_clip(r)
@@ -552,7 +579,7 @@ def png_payloads(result, prefix=""):
 
 def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, verbose=True, save_image=True,
                     device="cuda", records=None, batch_measurements=False, ssim=False, init="At", method="deq", snapshots=None, trace=False,
-                    jacobian=None):
+                    jacobian=None, noise=None):
     """Adapter with the reference's signature (training/sci_equilibrium_training.py:152): returns
     (average PSNR, {png path: float image}); prints one line per clip and the total; writes the PNGs.
     Default = the reference's schedule, one measurement per call (:171-181); batch_measurements="all" hands the measurements of all clips of
@@ -564,8 +591,11 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
     snapshots=(K1, ...) / trace=True (this build's, as in evaluate): every record gains "snapshots" ({K: {"psnr", "res", "ssim", "rec"}}) /
     "trace" ({"psnr", "res"} per f-call), and one '[and_maxiters K] Total Average PSNR' line per horizon follows the totals.
     jacobian=dict(n_iters=, window=, seed=) (this build's): every record gains "jacobian" ({"lipschitz_f", "rho_f", "lipschitz_denoiser"}),
-    every clip line '  Lip(f): %.4f  rho(f): %.4f  Lip(D): %.4f' (means over the clip's measurements), and one 'Total Average' line per quantity follows."""
+    every clip line '  Lip(f): %.4f  rho(f): %.4f  Lip(D): %.4f' (means over the clip's measurements), and one 'Total Average' line per quantity follows.
+    noise (this build's): a noise.SensorNoise for the test measurements, as in evaluate; one 'sensor noise on the test measurements' line says so."""
     images = {}
+    if verbose and noise is not None and noise.enabled:
+        print('sensor noise on the test measurements: %s' % noise.describe())
 
     def on_clip(r):
         images.update(png_payloads(r, save_img_path or ""))
@@ -584,7 +614,8 @@ def test_solver_sci(deep_eq_module, test_dataloader=None, save_img_path=None, ve
         if verbose:
             print(*clip_line(r, ssim))
     avg, results = evaluate(deep_eq_module, test_dataloader, device=device, batch=batch_measurements, on_clip=on_clip, ssim=ssim, init=init,
-                            method=method, snapshots=snapshots, trace=trace, **({} if jacobian is None else {"jacobian": jacobian}))
+                            method=method, snapshots=snapshots, trace=trace, **({} if jacobian is None else {"jacobian": jacobian}),
+                            **({} if noise is None else {"noise": noise}))
     if verbose:
         print('---------------------------------', 'Total Average PSNR: %.2f dB' % avg)
         if ssim:

@@ -12,6 +12,10 @@ measurement/*.mat under --trainpath), made per batch from a pool of uint8 frames
     write_training_directory(...)    the same samples in the reference's directory format (what SCITrainingDatasetSubset reads)
 
     python -m deqsci_amd.synth write --videos DIR --mask FILE --out DIR --n N --seed S [--patch_size 256] [--frames 8] [--augment ...]
+                                     [--meas_noise_sigma S --meas_noise_gain G --meas_bits N --meas_full_scale F --noise_seed K]
+
+synthesize, SynthTrainLoader and write_training_directory take noise=, a noise.SensorNoise: the measurement (never gt) goes through the
+sensor model of csrc/noise.hip, each sample under a sequence number that names it whatever the batch size.
 
 A sample is a choice of crop and orientation; the stored measurement is redundant (meas = sum_b mask_b gt_b).  The arithmetic is pinned
 (include/deqsci_hip.h, Y1): fp32 s <- s + mask_b u_b for b ascending, one fp32 division by 255.  With a mask of zeros and ones and
@@ -219,19 +223,36 @@ def _mask_for(mask, n, H, W, B):
     return len(shape) == 4
 
 
-def synthesize(pool, specs, mask):
+def _noise_seq(noise, seq, n, what):
+    """None where `noise` draws nothing; otherwise the n sequence numbers, which the caller must have given."""
+    if noise is None or not noise.enabled or n == 0:
+        return None
+    if seq is None or len(seq) != n:
+        raise ValueError(f"{what}: an enabled noise model needs seq, one sequence number per sample ({n})")
+    return [int(v) for v in seq]
+
+
+def synthesize(pool, specs, mask, noise=None, seq=None):
     """-> (gt (n,H,W,B), meas (n,H,W)) fp32: torch tensors on a device pool's device (csrc/synth.hip, one launch per 64 samples, no host
-    round trip), numpy arrays from a CPU pool (the restatement).  mask: (H,W,B) for all samples or (n,H,W,B); its shape sets the patch."""
+    round trip), numpy arrays from a CPU pool (the restatement).  mask: (H,W,B) for all samples or (n,H,W,B); its shape sets the patch.
+    noise: a noise.SensorNoise; where it is enabled, meas goes through it after Y1 - in place, as a launch of its own (csrc/noise.hip,
+    N2), sample k drawn with sequence number seq[k]; gt stays clean.  None or a disabled model: no launch, the same bits as ever."""
     n = len(specs)
     H, W, B = (int(x) for x in mask.shape[-3:])
     per_sample = _mask_for(mask, n, H, W, B)
+    seq = _noise_seq(noise, seq, n, "synthesize")
     if pool.device.type != "cpu":
         m = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32))
-        return _hip.synth_batch(pool.data, spec_table(specs), m.to(pool.device, torch.float32).contiguous(), H, W, B)
+        gt, meas = _hip.synth_batch(pool.data, spec_table(specs), m.to(pool.device, torch.float32).contiguous(), H, W, B)
+        if seq is not None:
+            noise.apply(meas, seq, frames=B, out=meas)
+        return gt, meas
     mask = mask.cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
     gt, meas = np.empty((n, H, W, B), np.float32), np.empty((n, H, W), np.float32)
     for k, s in enumerate(specs):
         gt[k], meas[k] = snapshot_f32(gather_u8(pool, s, H, W, B), mask[k] if per_sample else mask)
+    if seq is not None:
+        meas = noise.apply(meas, seq, frames=B)
     return gt, meas
 
 
@@ -240,9 +261,11 @@ class SynthTrainLoader:
     {'gt' (bsz,H,W,B), 'meas' (bsz,H,W), 'mask' (bsz,H,W,B)} of fp32 tensors on the pool's device.  Every __iter__ draws its epoch's
     descriptors from np.random.default_rng([seed, epoch]) and advances the epoch, so a run resumed with start_epoch=e draws what the
     uninterrupted run drew in epoch e.  mask: (H,W,B) zeros and ones (anything else trains too, but then a written directory would not
-    hold the same bits).  **sampling: sample_specs' augment, max_dt, max_ds."""
+    hold the same bits).  **sampling: sample_specs' augment, max_dt, max_ds.
+    noise: a noise.SensorNoise for the measurements (gt stays clean).  Sample i of epoch e - i its position in epoch_specs(e) - is drawn
+    with sequence number e * patches_per_epoch + i: its noise depends neither on batch_size nor on where a run was resumed."""
 
-    def __init__(self, pool, mask, batch_size, patches_per_epoch, H, W, B, seed, start_epoch=0, **sampling):
+    def __init__(self, pool, mask, batch_size, patches_per_epoch, H, W, B, seed, start_epoch=0, noise=None, **sampling):
         mask = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32))
         if tuple(mask.shape) != (H, W, B):
             raise ValueError(f"SynthTrainLoader: mask {tuple(mask.shape)} is not the patch ({H},{W},{B})")
@@ -250,6 +273,7 @@ class SynthTrainLoader:
             raise ValueError(f"SynthTrainLoader: batch_size {batch_size} >= 1 and patches_per_epoch {patches_per_epoch} >= batch_size expected")
         self.pool, self.batch_size, self.patches_per_epoch = pool, int(batch_size), int(patches_per_epoch)
         self.H, self.W, self.B, self.seed, self.epoch, self.sampling = int(H), int(W), int(B), int(seed), int(start_epoch), dict(sampling)
+        self.noise = noise if noise is not None and noise.enabled else None
         self.mask = mask.to(pool.device, torch.float32).contiguous()
         self.mask_batch = self.mask[None].repeat(self.batch_size, 1, 1, 1).contiguous()          # what a DataLoader's collate would build
         sample_specs(pool, 0, self.H, self.W, self.B, np.random.default_rng(0), **self.sampling)  # a pool nothing fits in fails here, by name
@@ -262,26 +286,36 @@ class SynthTrainLoader:
         return sample_specs(self.pool, len(self) * self.batch_size, self.H, self.W, self.B, np.random.default_rng([self.seed, int(epoch)]),
                             **self.sampling)
 
-    def batch(self, specs):
-        gt, meas = synthesize(self.pool, specs, self.mask)
+    def epoch_seq(self, epoch):
+        """The sequence numbers of an epoch's samples, in epoch_specs' order."""
+        first = int(epoch) * self.patches_per_epoch
+        return list(range(first, first + len(self) * self.batch_size))
+
+    def batch(self, specs, seq=None):
+        gt, meas = synthesize(self.pool, specs, self.mask, self.noise, seq)
         if self.pool.device.type == "cpu":
             gt, meas = torch.from_numpy(gt), torch.from_numpy(meas)
         return {'gt': gt, 'meas': meas, 'mask': self.mask_batch}
 
     def __iter__(self):
-        specs = self.epoch_specs(self.epoch)
+        specs, seq = self.epoch_specs(self.epoch), self.epoch_seq(self.epoch)
         self.epoch += 1
         bsz = self.batch_size
-        return (self.batch(specs[k * bsz:(k + 1) * bsz]) for k in range(len(self)))
+        return (self.batch(specs[k * bsz:(k + 1) * bsz], seq[k * bsz:(k + 1) * bsz]) for k in range(len(self)))
 
 
-def write_training_directory(out_dir, pool, mask, specs):
+def write_training_directory(out_dir, pool, mask, specs, noise=None, seq=None):
     """The reference's training directory for these samples: mask.mat (key 'mask'), gt/%06d.mat (key 'patch_save', uint8 (H,W,B)),
     measurement/%06d.mat (key 'meas', float64 sum_b mask_b u_b) - sample k in file k, so a sorted listing keeps the order of `specs`.
-    -> the directory with the trailing '/' SCITrainingDatasetSubset's string joins need."""
+    -> the directory with the trailing '/' SCITrainingDatasetSubset's string joins need.
+    noise (a noise.SensorNoise) and seq (one sequence number per sample): the measurement written is the noisy one, from the HOST
+    restatement - Y1's fp32 snapshot through SensorNoise.apply on a CPU array, stored as float64(meas_fp32) * 255.  It equals what a
+    SynthTrainLoader with the same model and sequence numbers yields to within the tolerance of the normals (the device's logf and
+    sincospif against float64), NOT bit for bit; gt stays clean."""
     import scipy.io as sio
     mask = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask, dtype=np.float64)
     H, W, B = mask.shape
+    seq = _noise_seq(noise, seq, len(specs), "write_training_directory")
     host = pool if pool.device.type == "cpu" else _host_view(pool)
     out_dir = str(out_dir)
     os.makedirs(os.path.join(out_dir, "gt"), exist_ok=True)
@@ -290,7 +324,12 @@ def write_training_directory(out_dir, pool, mask, specs):
     for k, s in enumerate(specs):
         u = gather_u8(host, s, H, W, B)
         sio.savemat(os.path.join(out_dir, "gt", "%06d.mat" % k), {"patch_save": u})
-        sio.savemat(os.path.join(out_dir, "measurement", "%06d.mat" % k), {"meas": (mask * u.astype(np.float64)).sum(axis=2)})
+        if seq is None:
+            meas = (mask * u.astype(np.float64)).sum(axis=2)
+        else:
+            clean = snapshot_f32(u, mask.astype(np.float32))[1]
+            meas = noise.apply(clean[None], seq[k:k + 1], frames=B)[0].astype(np.float64) * 255.0
+        sio.savemat(os.path.join(out_dir, "measurement", "%06d.mat" % k), {"meas": meas})
     return out_dir.rstrip("/") + "/"
 
 
@@ -336,13 +375,18 @@ def main(argv=None):
     w.add_argument("--augment", default=",".join(AUGMENT_ALL))
     w.add_argument("--max_dt", type=int, default=1)
     w.add_argument("--max_ds", type=int, default=1)
+    from .noise import add_noise_arguments, noise_from_arguments
+    add_noise_arguments(w.add_argument_group("sensor noise", "the measurements written are noisy; sample k is drawn with sequence number k"))
     a = p.parse_args(argv)
     pool = VideoPool(list_videos(a.videos), "cpu")
     mask = load_mask(a.mask, a.patch_size, a.patch_size, a.frames)
     specs = sample_specs(pool, a.n, a.patch_size, a.patch_size, a.frames, np.random.default_rng([a.seed, 0]), augment=parse_augment(a.augment),
                          max_dt=a.max_dt, max_ds=a.max_ds)
-    out = write_training_directory(a.out, pool, mask, specs)
+    noise = noise_from_arguments(a, a.seed)
+    out = write_training_directory(a.out, pool, mask, specs, noise, list(range(len(specs))))
     print(f"{len(specs)} samples of {a.patch_size}x{a.patch_size}x{a.frames} from {len(pool)} videos -> {out}")
+    if noise is not None:
+        print(f"sensor noise on the measurements: {noise.describe(a.frames)}")
     return out
 
 

@@ -735,6 +735,36 @@ int deqsci_synth_batch_u8(const uint8_t* pool, int64_t pool_bytes, const int64_t
  *     n = 0: nothing is launched. */
 int deqsci_rgb_to_gray_u8(const uint8_t* rgb, uint8_t* gray, int64_t n, deqsci_stream_t stream);
 
+/* ---- a reproducible random source and the sensor-noise model on it (csrc/noise.hip) ----
+ * The generator is Philox4x32-10 in integer arithmetic.  M0 = 0xD2511F53, M1 = 0xCD9E8D57, W0 = 0x9E3779B9, W1 = 0xBB67AE85; one round:
+ *         (c0,c1,c2,c3) <- (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0)),  then (k0,k1) += (W0,W1);  ten rounds.
+ *     The key (k0,k1) is the 64-bit `seed` (low word, high word).  Counter words 0 and 1 are the 64-bit group index g = e >> 2, e the flat
+ *     element index inside ONE sample; words 2 and 3 are the sample's 64-bit sequence number seq[sample].  The four output words
+ *     x0..x3 of a group serve the elements 4g .. 4g+3, so a value is a function of (seed, seq, e) and of nothing else: not of bsz, not
+ *     of the launch geometry, not of which call or which device draws it.
+ *     Normals, fp32, with the accurate library functions (logf, sqrtf, sincospif - not the fast intrinsics):
+ *         u(x) = ((x >> 9) + 0.5f) * 2^-23   (exact, strictly inside (0,1));   r = sqrtf(-2.0f * logf(u(x0)));   sincospif(2.0f * u(x1), &s, &c)
+ *         element 4g = r * c, element 4g+1 = r * s;  x2, x3 give elements 4g+2 and 4g+3 the same way.  |normal| <= sqrt(48 ln 2) < 5.77.
+ *     seq: bsz uint64 in HOST memory, read before the call returns (by value in the kernel's arguments, DEQSCI_NOISE_MAX_ROWS samples per
+ *     launch); nothing allocated, nothing synchronised, no atomics, every output element written once.  Pointers 4-byte aligned (float4 /
+ *     uint4 accesses where n % 4 == 0 and the pointers are 16-byte aligned: the same values).  NULL: -1; bsz < 0, n < 1 or more than 2^40
+ *     elements: -2; misaligned: -3; bsz = 0: nothing is launched.
+ * N0  out (bsz, ceil(n / 4), 4) uint32: the raw words of every group that serves one of the n elements of a sample.
+ * N1  out (bsz, n) fp32 standard normals.
+ * N2  out (bsz, n) = y (bsz, n) under the Gaussian approximation of Poisson-Gaussian noise (variance gain y + sigma^2) followed by an ADC of
+ *     `bits` bits over [0, full_scale].  fp32, every operation rounded on its own, both divisions and the square root correctly rounded,
+ *     in THIS order, nrm the element's normal of N1:
+ *         if y is not finite:  o = y                       (NaN and +-Inf pass through untouched, also through the quantiser)
+ *         else:  p = fmaxf(y, 0);  v = gain * p;  v = v + sigma * sigma;  d = sqrtf(v);  t = d * nrm;  o = y + t
+ *                if bits > 0:  L = 2^bits - 1;  c = o / full_scale;  c = fminf(fmaxf(c, 0), 1);  q = rintf(c * L);  o = (q / L) * full_scale
+ *     out == y (exactly in place) is allowed, any other overlap is refused (-4); bits outside 0..16, sigma or gain negative or not finite,
+ *     full_scale not positive and finite: -4.  bits = 0: no quantiser (full_scale is then only checked). */
+#define DEQSCI_NOISE_MAX_ROWS 64
+int deqsci_philox_words_u32(uint32_t* out, const uint64_t* seq, int64_t bsz, int64_t n, uint64_t seed, deqsci_stream_t stream);
+int deqsci_philox_normal_f32(float* out, const uint64_t* seq, int64_t bsz, int64_t n, uint64_t seed, deqsci_stream_t stream);
+int deqsci_sensor_noise_f32(const float* y, float* out, const uint64_t* seq, int64_t bsz, int64_t n, uint64_t seed, float sigma, float gain,
+                            int bits, float full_scale, deqsci_stream_t stream);
+
 /* ---- measurement only (bench.py): the same launch with the dispatch's own begin/end timestamps
  * written to two raw hipEvent_t handles (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 reports,
  * without the marker-packet overhead of events recorded around a launch. */

@@ -13,6 +13,8 @@ The median of `--reps` after `--warmup`.  Prints one line per measurement and a 
 threshold: the feature is that training from video is possible at all.
 
     python tools/synth_bench.py [--reps 10] [--warmup 2] [--iters 30] [--kernel-only]
+    python tools/synth_bench.py --noise      N1 / N2 of csrc/noise.hip beside Y1, and a loader batch with and without sensor noise
+                                             (profiles/noise.md)
 """
 import argparse
 import json
@@ -60,6 +62,50 @@ def kernel_alone(pool, mask, bsz, reps, warmup, augment=synth.AUGMENT_ALL):
     return {"ms": med, "min_ms": min(ms), "bytes": bsz * sample_bytes(), "GBps": bsz * sample_bytes() / med / 1e6}
 
 
+def event_timed(call, reps, warmup):
+    """(median, min) ms of HIP events around one call on an idle stream."""
+    ms = []
+    for i in range(warmup + reps):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= warmup:
+            ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms), min(ms)
+
+
+def noise_alone(pool, mask_host, reps, warmup):
+    """--noise: N1 and N2 (csrc/noise.hip) alone beside Y1, at 8 and 64 samples of 256 x 256, and one loader batch with and without the
+    sensor model.  Bytes: N1 writes 4 per pixel, N2 reads 4 and writes 4; both do the 40 integer multiplies of Philox per four pixels."""
+    from deqsci_amd.noise import SensorNoise
+    model = SensorNoise(sigma=5 / 255, gain=0.01, bits=10, seed=1)
+    mask = torch.from_numpy(mask_host).cuda()
+    out = {}
+    for bsz in (8, 64):
+        n, seq = H * W, list(range(bsz))
+        nrm = torch.empty(bsz, n, device="cuda")
+        y = torch.rand(bsz, H, W, device="cuda") * B
+        o = torch.empty_like(y)
+        r = {"Y1": kernel_alone(pool, mask, bsz, reps, warmup)}
+        for name, nbytes, call in (("N1", 4 * bsz * n, lambda: _hip.philox_normal(seq, n, 1, out=nrm)),
+                                   ("N2", 8 * bsz * n, lambda: model.apply(y, seq, frames=B, out=o)),
+                                   ("N2_in_place", 8 * bsz * n, lambda: model.apply(o, seq, frames=B, out=o))):
+            med, lo = event_timed(call, reps, warmup)
+            r[name] = {"ms": med, "min_ms": lo, "bytes": nbytes, "GBps": nbytes / med / 1e6}
+        for name in ("Y1", "N1", "N2", "N2_in_place"):
+            print(f"bsz {bsz}: {name} events around the call {r[name]['ms'] * 1e3:.1f} us (min {r[name]['min_ms'] * 1e3:.1f}), "
+                  f"{r[name]['bytes'] / 1e6:.2f} MB -> {r[name]['GBps']:.0f} GB/s", flush=True)
+        for name, noise in (("batch_clean_ms", None), ("batch_noisy_ms", model)):
+            loader = synth.SynthTrainLoader(pool, mask_host, bsz, (warmup + reps + 1) * bsz, H, W, B, seed=5, noise=noise)
+            r[name] = host_timed(loader, reps, warmup)
+        print(f"bsz {bsz}: one batch  clean {r['batch_clean_ms']:.3f} ms | with sensor noise {r['batch_noisy_ms']:.3f} ms", flush=True)
+        out[f"bsz{bsz}"] = r
+    return out
+
+
 def host_timed(batches, reps, warmup):
     """Median ms per batch of an iterator whose batches end on the device."""
     ms = []
@@ -101,12 +147,19 @@ def main():
     ap.add_argument("--kernel-only", action="store_true",
                     help="only Y1, at batch 1, 8 and 64, plain crops and augmented ones: the launches of a kernel trace "
                          "(rocprofv3 --kernel-trace --stats -- python tools/synth_bench.py --kernel-only --reps 18)")
+    ap.add_argument("--noise", action="store_true",
+                    help="only the random source and the sensor model (csrc/noise.hip): N1 and N2 alone beside Y1 at batch 8 and 64, and one "
+                         "loader batch with and without noise; the numbers go to profiles/noise.md")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "synth_bench needs an MI355X"
     pool = synth.VideoPool(synth.list_videos(CLIPS), "cuda")
     mask_host = synth.load_mask(os.path.join(CLIPS, "traffic_cacti.mat"), H, W, B)
     mask = torch.from_numpy(mask_host).cuda()
     out = {"device": torch.cuda.get_device_name(0), "shape": [H, W, B], "reps": a.reps, "warmup": a.warmup, "and_maxiters": a.iters}
+    if a.noise:
+        out.update(noise_alone(pool, mask_host, a.reps, a.warmup))
+        print(json.dumps(out))
+        return
     if a.kernel_only:
         for bsz in (1, 8, 64):
             for augment in ((), synth.AUGMENT_ALL):
